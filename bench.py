@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- pre-train images/sec of the data2vec ViT-B/16 step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N=1; N>1 launches its own ranks (below)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]      # N=1; N>1 launches its own ranks (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 With --gpus N > 1 and no RANK / WORLD_SIZE in the environment, bench.py starts N ranks itself (one process per GPU,
@@ -9,7 +9,8 @@ With --gpus N > 1 and no RANK / WORLD_SIZE in the environment, bench.py starts N
 torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE as usual.
 
 A "step" is one full iteration of engine_for_cyclical.train_one_epoch on one synthetic batch that
-is already resident in HBM: teacher forward -> targets -> student forward (attn-drop 0.05,
+is already resident in HBM, from the seeded initial weights, EMA teacher and AdamW state (restored, untimed, before every step):
+teacher forward -> targets -> student forward (attn-drop 0.05,
 drop-path 0.25) -> SmoothL1 -> backward -> [gradient all-reduce] -> clip + AdamW -> EMA.
 Rank 0 prints ONE JSON line.  `roofline` is for the largest kernel by time (the bf16 MFMA GEMM
 gemm_nt256_kernel in its residual-epilogue instantiation: attention proj + MLP fc2; the fc1 launches ride along per
@@ -92,6 +93,27 @@ def rocprof_avg_us(path=KERNEL_STATS):
 # reference cannot travel to the GPU box): bs=4, 8 threads, 3 timed steps -- quoted beside the port's figure
 REFERENCE_ENGINE_BUILD_CONTAINER = {"img_per_s": 2.292, "s_per_step": 1.745, "threads": 8, "batch": 4, "timed_steps": 3,
                                     "source": "profiles/round2_reference_engine_cpu.json"}
+
+
+DUMP_SAMPLE = 1 << 21            # --dump-outputs: elements kept per arena (5 arenas x 8 MB float32, under the 64 MB cap)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(path, loss, grad_norm, arenas, sample=DUMP_SAMPLE, seed=DUMP_SEED):
+    """--dump-outputs DIR: what the last timed step hands its caller -- its loss and gradient norm, and the fp32 arenas it updated
+    (`arenas`: name -> flat tensor) -- as DIR/<name>.npy in float32.  An arena longer than `sample` is cut to the same seeded,
+    sorted element indices in every run, so two builds of the project can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"loss": np.float32(loss), "grad_norm": np.float32(grad_norm)}
+    for name, t in arenas.items():
+        if t.numel() > sample:
+            g = torch.Generator().manual_seed(seed)
+            t = t[torch.randint(t.numel(), (sample,), generator=g).sort().values.to(t.device)]
+        out[name] = t.detach().float().cpu().numpy()
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return sorted(out)
 
 
 def synthetic_batch(B, seed, device):
@@ -225,6 +247,9 @@ def main():
     ap.add_argument("--model", default="beit_base_patch16_224",
                     help="beit_base_patch16_224 (headline) | dist_beit_base_patch16_224 (--stochastic two-stream, BASELINE config 3) | "
                          "beit_large_patch16_224 | dist_beit_large_patch16_224 (config 5 model)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, grad_norm, weights, EMA teacher, gradients, AdamW "
+                         "moments; arenas as a fixed seeded sample) as DIR/<name>.npy in float32")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -304,20 +329,44 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # Every warm-up and timed step starts from the seeded initial state.  The step's fp32 atomic reductions (split-K weight gradients,
+    # column sums) differ from run to run in the last bits, and consecutive steps compound that -- AdamW moves a weight by about lr
+    # whatever the size of its gradient -- so after a few steps two runs no longer compute the same thing.  From the same state one
+    # step differs by rounding only.  The restore is enqueued on the step's stream (the step ends there) and is not timed.
+    state = (model._arena, engine.ema, engine.adam_m, engine.adam_v)
+    init, step_count0 = [t.clone() for t in state], opt.step_count
+
+    def restore():
+        for t, src in zip(state, init):
+            t.copy_(src)
+        engine.sync_shadows(3)           # bf16 copies of the weights and the EMA teacher the step's GEMMs read
+        opt.step_count = step_count0
+
     if a.single_stream:
         check(L.uvit_engine_set_streams(engine.h, 0), "set_streams")
     for i in range(a.warmup):
+        restore()
         step(i)
     fence()
-    # timed region: K steps.  The dominant kernel's launches are bracketed with HIP events on their own stream;
-    # in the default two-stream schedule other kernels share the GPU with it, so that duration is "overlapped".
+    # timed region: K steps, each between two HIP events on the step's stream.  The dominant kernel's launches are bracketed with HIP
+    # events on their own stream; in the default two-stream schedule other kernels share the GPU with it, so that duration is "overlapped".
     check(L.uvit_engine_profile(engine.h, 1, 4096), "profile on")
-    t0 = time.perf_counter()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
     for i in range(a.steps):
+        restore()
+        ev[i][0].record()
         step(a.warmup + i)
+        ev[i][1].record()
     fence()
-    dt = time.perf_counter() - t0
+    dt = sum(s.elapsed_time(e) for s, e in ev) / 1e3
     check(L.uvit_engine_profile(engine.h, 0, 0), "profile off")
+    if a.dump_outputs and rank == 0:
+        # before any later step: the untimed regions below keep training the same weights
+        last = torch.zeros(2).pin_memory()
+        check(L.uvit_engine_read_stats(engine.h, C.c_void_p(last.data_ptr()), cur_stream()), "stats")
+        dump_outputs(a.dump_outputs, float(last[0]), float(last[1]),
+                     {"params": model._arena, "ema_params": engine.ema, "grads": engine.grads,
+                      "adam_exp_avg": engine.adam_m, "adam_exp_avg_sq": engine.adam_v})
     def read_kinds():
         """{name: (avg ms per launch, launches, flops per launch, algorithmic bytes per launch)} of the bracketed Linears"""
         res = {}

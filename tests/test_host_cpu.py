@@ -328,6 +328,28 @@ def test_bench_self_launch_command_and_clean_failure_without_gpus():
         assert r.returncode == 2 and "WORLD_SIZE=4" in r.stderr
 
 
+def test_bench_dump_outputs_fixed_sample_under_cap(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per output, short arenas whole, long ones cut to the same seeded indices in every
+    run and for every arena, and the five arenas of the flagship step at the default sample size stay under 64 MB."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert 5 * bench.DUMP_SAMPLE * 4 + 2 * 4 <= 64 * 2 ** 20
+    big = torch.arange(1000, dtype=torch.float32)
+    arenas = {"params": big, "grads": -big, "small": torch.linspace(0, 1, 7)}
+    for d in ("a", "b"):
+        names = bench.dump_outputs(str(tmp_path / d), 1.5, 0.25, arenas, sample=64)
+        assert names == ["grad_norm", "grads", "loss", "params", "small"]
+    load = lambda d, n: np.load(tmp_path / d / (n + ".npy"))  # noqa: E731
+    for n in names:
+        assert load("a", n).dtype == np.float32 and np.array_equal(load("a", n), load("b", n)), n
+    assert float(load("a", "loss")) == 1.5 and float(load("a", "grad_norm")) == 0.25
+    p = load("a", "params")
+    assert p.shape == (64,) and np.all(np.diff(p) >= 0) and np.array_equal(load("a", "grads"), -p)
+    assert np.array_equal(load("a", "small"), arenas["small"].numpy())
+
+
 def test_reducer_waits_for_the_collective_on_the_stream_that_consumes_it(monkeypatch):
     """Over RCCL Work.wait() only makes the CURRENT stream wait for the collective.  GradReducer.finish() enqueues the widening
     copy of a bf16 bucket on its communication stream, so the wait must be issued with THAT stream current (with the
