@@ -318,6 +318,46 @@ int uvit_op_droppath(float* scales, const float* rates_dev, int depth, int B, ui
                      uvit_stream stream);
 int uvit_op_cast_bf16(const float* src, void* dst_bf16, int64_t n, uvit_stream stream);
 
+/* BEiT pre-training augmentation of a batch of decoded images (the reference's DataAugmentationForBEiT, datasets.py:31-117,
+ * ImageFolder data sets): per sample, in this order and with Pillow's integer / float32 arithmetic bit for bit
+ *   1. ColorJitter on the whole image: jitter_op[0..n_jitter) in order, each Image.blend(degenerate, img, factor) (Blend.c) with
+ *      degenerate = black (brightness), the constant int(mean(L) + 0.5) of the image as it stands (contrast), per-pixel L
+ *      (saturation); L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16;
+ *   2. horizontal flip (flip = 1);
+ *   3. crop (crop_x, crop_y, crop_w, crop_h) of the flipped image, resize to (resize_w, resize_h) with Resample.c's 8-bit separable
+ *      resampler (taps clipped to the crop; a pass whose size is unchanged is skipped), evaluated on the S x S window at
+ *      (win_x, win_y) of the resized image; window positions outside it are 0 (CenterCrop's padding);
+ *   4. ToTensor + Normalize: ((u8 / 255) - mean[c]) / std[c] in float32 into out (B, 3, S, S).
+ * pixels: ONE device buffer of pixel_bytes bytes holding every image as HWC uint8 RGB (rows of w * 3 bytes) at desc[b].offset.
+ * desc: HOST memory (B entries), validated here and copied into the workspace by an asynchronous copy on `stream`: keep it
+ * unchanged until the stream has passed this call (pinned memory, like any hipMemcpyAsync source).  mean / std: HOST, 3 floats.
+ * workspace: uvit_op_augment_ws_bytes(desc, B, S) bytes (depends on the descriptors: filter taps and source rows).
+ * Errors (nothing launched): UVIT_ERR_SHAPE for an image, crop, resize or window outside its bounds or an image that does not fit
+ * in pixel_bytes; UVIT_ERR_ARG for a bad filter, flip or jitter entry (an op listed twice included); UVIT_ERR_WORKSPACE. */
+#define UVIT_AUG_LANCZOS 1      /* filter ids = PIL.Image.Resampling */
+#define UVIT_AUG_BILINEAR 2
+#define UVIT_AUG_BICUBIC 3
+#define UVIT_AUG_HAMMING 5
+#define UVIT_AUG_BRIGHTNESS 0   /* jitter op ids = torchvision ColorJitter's fn_idx */
+#define UVIT_AUG_CONTRAST 1
+#define UVIT_AUG_SATURATION 2
+typedef struct uvit_augment_desc {
+    int64_t offset;                            /* byte offset of the image in `pixels` */
+    int32_t h, w;                              /* decoded size */
+    int32_t flip;
+    int32_t crop_x, crop_y, crop_w, crop_h;    /* inside [0, w) x [0, h), in flipped coordinates */
+    int32_t resize_w, resize_h;
+    int32_t win_x, win_y;                      /* origin of the S x S output window in the resized image (may be negative) */
+    int32_t filter;                            /* UVIT_AUG_{BILINEAR, BICUBIC, HAMMING, LANCZOS} */
+    int32_t n_jitter;                          /* 0..3 */
+    int32_t jitter_op[3];                      /* UVIT_AUG_{BRIGHTNESS, CONTRAST, SATURATION}, distinct */
+    float jitter_factor[3];
+    int32_t reserved;                          /* 0 */
+} uvit_augment_desc;
+int64_t uvit_op_augment_ws_bytes(const uvit_augment_desc* desc, int B, int S);   /* < 0: the UVIT_ERR_* of the batch call */
+int uvit_op_augment_batch(const uint8_t* pixels, int64_t pixel_bytes, const uvit_augment_desc* desc, int B, int S, const float* mean,
+                          const float* std, float* out, void* workspace, int64_t ws_bytes, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,9 +9,13 @@ The step itself runs as HIP kernels (uncertainty-vit_amd/).  One process per GPU
 torch.distributed.run (RANK / WORLD_SIZE / LOCAL_RANK); gradients are all-reduced by the native
 engine's reducer over RCCL, so the model is NOT wrapped in torch DDP.
 
-New (not in the reference): `--data_set SYNTHETIC` (seeded N(0,1) images + exactly
-`--num_mask_patches` masked patches per image; there is no dataset / network in this image) and
-`--synthetic_len`.  Real-data pipelines (datasets.py, transforms.py) are out of scope.
+Data: `--data_set IMNET | image_folder | tiny_IMNET` read `--data_path` as the reference's ImageFolder does
+(uncertainty-vit_amd/datasets.py): PIL decodes in the loader workers, the workers draw the augmentation parameters of
+`--aug_level` / `--input_size` / `--train_interpolation`, and the augmentation itself (color jitter, flip, resized crop,
+normalize) runs as one HIP launch per batch on the prefetcher's side stream, byte-identical to the reference's PIL pipeline.
+CIFAR10 / CIFAR100 need torchvision's archive formats and are not available.
+New (not in the reference): `--data_set SYNTHETIC` (seeded N(0,1) images + exactly `--num_mask_patches` masked patches per
+image) and `--synthetic_len`.
 """
 import argparse
 import datetime
@@ -65,7 +69,7 @@ def get_args(argv=None):
     a("--tri_phase_schedule", type=str, default=None)
     a("--warmup_epochs", type=int, default=5, metavar="N")
     a("--warmup_steps", type=int, default=-1, metavar="N")
-    # augmentation (accepted for command-line compatibility; the data pipeline is out of scope)
+    # augmentation of the image-folder data sets (uncertainty-vit_amd/datasets.py)
     a("--color_jitter", type=float, default=0.4, metavar="PCT")
     a("--train_interpolation", type=str, default="bicubic")
     a("--aug_level", default=-1, type=int)
@@ -184,11 +188,15 @@ def main(args):
     args.patch_size = patch_size
     if args.seed_model:
         raise NotImplementedError("--seed_model (checkpoint surgery with rel-pos interpolation) is out of scope")
-    if args.data_set != "SYNTHETIC":
-        raise NotImplementedError("only --data_set SYNTHETIC is available here: the image pipelines of datasets.py are out of scope")
-
-    block = (args.min_mask_patches_per_block, args.max_mask_patches_per_block) if args.synthetic_masks == "block" else None
-    dataset_train = SyntheticPretrainSet(args.synthetic_len, args.input_size, args.window_size, args.num_mask_patches, args.seed, block)
+    collate_fn = None
+    if args.data_set == "SYNTHETIC":
+        block = (args.min_mask_patches_per_block, args.max_mask_patches_per_block) if args.synthetic_masks == "block" else None
+        dataset_train = SyntheticPretrainSet(args.synthetic_len, args.input_size, args.window_size, args.num_mask_patches, args.seed,
+                                             block)
+    else:
+        from uncertainty_vit_amd.datasets import build_pretraining_dataset, collate_packed
+        dataset_train = build_pretraining_dataset(args)      # CIFAR10 / CIFAR100 raise NotImplementedError
+        collate_fn = collate_packed
     num_tasks, global_rank = utils.get_world_size(), utils.get_rank()
     num_training_steps_per_epoch = len(dataset_train) // args.batch_size // num_tasks
     sampler_train = torch.utils.data.DistributedSampler(dataset_train, num_replicas=num_tasks, rank=global_rank, shuffle=True)
@@ -197,7 +205,8 @@ def main(args):
         os.makedirs(args.log_dir, exist_ok=True)
         log_writer = utils.TensorboardLogger(log_dir=args.log_dir)
     data_loader_train = torch.utils.data.DataLoader(dataset_train, sampler=sampler_train, batch_size=args.batch_size,
-                                                    num_workers=args.num_workers, pin_memory=args.pin_mem, drop_last=True)
+                                                    num_workers=args.num_workers, pin_memory=args.pin_mem, drop_last=True,
+                                                    collate_fn=collate_fn)
 
     model.to(device)
     model_without_ddp = model

@@ -14,6 +14,10 @@ for f in gemm attention attention2 norm elementwise optim engine; do
   ( hipcc $FLAGS -c $f.hip -o obj/$f.o ) &
   pids+=($!)
 done
+# augment.hip reproduces Pillow's arithmetic bit for bit: IEEE float semantics, no fast-math, no FMA contraction
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function \
+    -c augment.hip -o obj/augment.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

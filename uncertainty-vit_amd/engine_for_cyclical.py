@@ -8,6 +8,7 @@ each iteration runs as hand-written HIP kernels through libuvit:
 Data parallelism: one process per GPU; gradients are averaged with torch.distributed
 (`nccl` = RCCL over xGMI) on a side stream while the compute stream keeps running backward.
 """
+import collections
 import ctypes as C
 import math
 import sys
@@ -17,7 +18,8 @@ import torch
 import torch.distributed as dist
 
 from . import utils
-from .native import MAX_DEPTH, StepParams, check, cur_stream, lib, ptr
+from .datasets import PackedBatch
+from .native import MAX_DEPTH, StepParams, augment_batch, augment_ws_bytes, check, cur_stream, lib, ptr
 
 
 def _unwrap(model):
@@ -101,18 +103,45 @@ class GradReducer:
 class DevicePrefetcher:
     """Keeps one batch ahead of the step in HBM: the host->device copy of batch i+1 runs on a side HIP stream (from
     pinned memory when the loader pins) while step i computes.  The reference copies inside the step loop on the
-    compute stream (engine_for_cyclical.py:58-59); the tensors handed out are the same.  CPU devices pass through."""
+    compute stream (engine_for_cyclical.py:58-59); the tensors handed out are the same.  CPU devices pass through.
+
+    A `datasets.PackedBatch` (image-folder data sets) is augmented on the same side stream: its raw pixels are uploaded and
+    uvit_op_augment_batch writes the normalized (B, 3, S, S) images; ((samples, mask), labels) are handed out as for a tensor
+    batch.  There is no host fallback for it."""
 
     def __init__(self, loader, device):
         self.loader, self.device = loader, torch.device(device)
         self.on_gpu = self.device.type == "cuda"
         self.stream = torch.cuda.Stream(self.device) if self.on_gpu else None
         self.mask_rows = 0     # masked patches of the batch being handed out, counted on the host before its upload (0 = unknown)
+        self._aug_ws = None    # augmentation workspace (grown on demand, used on self.stream only)
+        self._in_flight = collections.deque()   # (packed batch, event): host descriptors the side stream still copies from
 
     def __len__(self):
         return len(self.loader)
 
+    def _augment(self, item):
+        if not self.on_gpu:
+            raise RuntimeError("image-folder batches are augmented by the HIP kernel uvit_op_augment_batch: a GPU device is required")
+        rows = int(item.mask.sum())
+        while self._in_flight and self._in_flight[0][1].query():
+            self._in_flight.popleft()
+        need = augment_ws_bytes(item.desc, item.size)
+        with torch.cuda.stream(self.stream):
+            if self._aug_ws is None or self._aug_ws.numel() < need:
+                self._aug_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            pixels = item.pixels.to(self.device, non_blocking=True)
+            mask = item.mask.to(self.device, non_blocking=True)
+            samples = torch.empty((len(item), 3, item.size, item.size), dtype=torch.float32, device=self.device)
+            augment_batch(pixels, item.desc, item.size, item.mean, item.std, samples, self._aug_ws, C.c_void_p(self.stream.cuda_stream))
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self._in_flight.append((item, ev))
+        return ((samples, mask), item.labels), rows
+
     def _upload(self, item):
+        if isinstance(item, PackedBatch):
+            return self._augment(item)
         (samples, mask), label = item
         rows = int(mask.sum()) if (torch.is_tensor(mask) and not mask.is_cuda) else 0      # free on the host; a device mask would need a sync
         if not self.on_gpu:

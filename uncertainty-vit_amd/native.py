@@ -84,6 +84,14 @@ class Tuning(C.Structure):
         return t
 
 
+class AugmentDesc(C.Structure):
+    """uvit_augment_desc (include/uvit.h): one sample of uvit_op_augment_batch."""
+    _fields_ = [("offset", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("h", "w", "flip", "crop_x", "crop_y", "crop_w", "crop_h", "resize_w", "resize_h", "win_x",
+                                          "win_y", "filter", "n_jitter")] + \
+               [("jitter_op", C.c_int32 * 3), ("jitter_factor", C.c_float * 3), ("reserved", C.c_int32)]
+
+
 _vp, _i, _i64, _f, _u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
 # prototypes of every symbol include/uvit.h declares (argtypes matter: int64 / float arguments)
 _PROTOTYPES = {
@@ -144,6 +152,8 @@ _PROTOTYPES = {
     "uvit_op_synth_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _u32, _u32, _vp]),
     "uvit_op_droppath": (_i, [_vp, _vp, _i, _i, _u32, _u32, _vp]),
     "uvit_op_cast_bf16": (_i, [_vp, _vp, _i64, _vp]),
+    "uvit_op_augment_ws_bytes": (_i64, [_vp, _i, _i]),
+    "uvit_op_augment_batch": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
@@ -201,6 +211,25 @@ def lib():
                         "Run `python -c 'import __graft_entry__ as g; g.build()'`.")
     _lib = L
     return L
+
+
+def augment_ws_bytes(desc, size):
+    """Workspace of uvit_op_augment_batch for a batch's descriptors (uint8 CPU tensor of B uvit_augment_desc records)."""
+    n = lib().uvit_op_augment_ws_bytes(C.c_void_p(desc.data_ptr()), desc.numel() // C.sizeof(AugmentDesc), int(size))
+    if n < 0:
+        check(n, "uvit_op_augment_ws_bytes")
+    return n
+
+
+def augment_batch(pixels, desc, size, mean, std, out, workspace, stream):
+    """uvit_op_augment_batch: pixels (device uint8), desc (CPU uint8 tensor, pinned for an asynchronous copy; must stay alive
+    until `stream` passes the call), out (B, 3, size, size) fp32 on the device."""
+    B = desc.numel() // C.sizeof(AugmentDesc)
+    if out.shape != (B, 3, size, size) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise UvitError(f"augment output must be a contiguous float32 ({B}, 3, {size}, {size}) tensor")
+    m, sd = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    check(lib().uvit_op_augment_batch(ptr(pixels), pixels.numel(), C.c_void_p(desc.data_ptr()), B, int(size), m, sd, ptr(out),
+                                      ptr(workspace), workspace.numel(), stream), "uvit_op_augment_batch")
 
 
 def ptr(t):
