@@ -174,12 +174,12 @@ struct uvit_engine {
     size_t n_nd;           // floats in the live (not frozen) part of the no-decay region
     bool slab_started;
     bool last_dropout; uint32_t last_seed, last_it;
-    int ls_prefused = -1;   // layer whose MLP-branch LayerScale backward was already done by layer+1's fused LayerNorm backward
+    int bwd_next = -1;      // the layer uvit_step_backward_layer takes next: depth-1 after uvit_step_begin, then down to 0 (-1: none)
     int compact_R = 0;      // > 0: this step runs the last block's MLP on the masked rows only, in R (multiple of 64) compact rows (uvit_step_params.n_rows_hint)
     // second stream: teacher forward beside student forward; wgrad GEMMs beside the dgrad chain
     bool dual = true;
     hipStream_t aux = nullptr, aux_eq = nullptr, aux_lo = nullptr;     // aux = the one in use (uvit_engine_set_streams)
-    hipEvent_t ev_fork = nullptr, ev_teacher = nullptr, ev_x[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_fork = nullptr, ev_teacher = nullptr, ev_x = nullptr;
     hipEvent_t ev_wdone[UVIT_MAX_DEPTH] = {};
     hipEvent_t ev_ds = nullptr;             // dS of the current layer is complete (main stream -> second stream)
     // optional HIP-event bracketing of the dominant kernel (fc1 GEMM, EPI_GELU) for bench.py's roofline
@@ -387,8 +387,7 @@ extern "C" uvit_engine* uvit_engine_create(const uvit_config* cfg, const uvit_bu
                   hipStreamCreateWithPriority(&e->aux_lo, hipStreamNonBlocking, lo) == hipSuccess;
         e->aux = e->aux_eq;
         auto mk = [&](hipEvent_t* ev) { ok = ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess; };
-        mk(&e->ev_fork); mk(&e->ev_teacher); mk(&e->ev_ds);
-        for (int i = 0; i < 4; ++i) mk(&e->ev_x[i]);
+        mk(&e->ev_fork); mk(&e->ev_teacher); mk(&e->ev_ds); mk(&e->ev_x);
         for (int i = 0; i < cfg->depth; ++i) mk(&e->ev_wdone[i]);
         if (!ok) { uvit_engine_destroy(e); return fail(UVIT_ERR_LAUNCH); }
     }
@@ -404,7 +403,7 @@ extern "C" void uvit_engine_destroy(uvit_engine* e) {
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_teacher) (void)hipEventDestroy(e->ev_teacher);
     if (e->ev_ds) (void)hipEventDestroy(e->ev_ds);
-    for (int i = 0; i < 4; ++i) if (e->ev_x[i]) (void)hipEventDestroy(e->ev_x[i]);
+    if (e->ev_x) (void)hipEventDestroy(e->ev_x);
     for (int i = 0; i < UVIT_MAX_DEPTH; ++i) if (e->ev_wdone[i]) (void)hipEventDestroy(e->ev_wdone[i]);
     delete e;
 }
@@ -536,19 +535,6 @@ static void dp_list_get(const uvit_engine* e, int l, int st, int branch, DpList&
     d.pos = e->dpl_pos + (size_t)lb * e->B; d.bmap = e->dpl_bmap + (size_t)lb * e->B;
     d.rows = e->dpl_rows + (size_t)lb * e->dpl_stride; d.cnt = e->dpl_cnt + lb; d.K = e->dpl_K[lb];
 }
-// base model: the list of (layer, branch) when it drops somebody (nobody dropped: the dense launches; everybody dropped: dense too, 0 * branch)
-static bool dp_list(const uvit_engine* e, int l, int branch, DpList& d) {
-    if (!e->dpl_on || e->S != 1) return false;
-    dp_list_get(e, l, 0, branch, d);
-    return d.K > 0 && d.K < e->B;
-}
-// two-stream model: the MLP branch of a layer runs compact when either stream dropped somebody and neither dropped everybody; the kept rows of
-// the mean stream, then those of the covariance stream, are stacked without a gap (fc1 / fc2 share their weights between the streams)
-static bool dp_list2(const uvit_engine* e, int l, DpList (&d)[2]) {
-    if (!e->dpl_on || e->S != 2) return false;
-    dp_list_get(e, l, 0, 1, d[0]); dp_list_get(e, l, 1, 1, d[1]);
-    return d[0].K > 0 && d[1].K > 0 && (d[0].K < e->B || d[1].K < e->B);
-}
 // The host's evaluation of droppath_kernel (elementwise.hip): kept samples per (layer, draw), draws = 2 (base: attn, mlp) or 4 (two-stream).
 // Pure host code -- no device call -- so the CPU test suite pins it against the oracle's drop_path_scales.
 static void dp_kept_counts(const float* rates, int depth, int nbr, int B, uint32_t seed, uint32_t it, int* out) {
@@ -593,35 +579,72 @@ static int dp_lists_begin(uvit_engine* e, uint32_t seed, uint32_t it, int Bc, hi
                                       (int)e->dpl_stride, e->dpl_K, s);
 }
 
-// R > 0 (base model, student's last block of a training step): the MLP branch runs on the R compact rows of the masked-patch list only --
-// LN2 gathers them, fc1 / fc2 are R-row GEMMs and the residual epilogue of fc2 reads x_mid and writes x_out / the saved branch output at the
-// listed rows (the other rows of x_out are never read: the head and the final-norm backward go through the same list).
+// Which rows a Block branch runs on -- one answer for the forward and the backward of a pass:
+//   ROWS_ALL     every row, stacked over the S streams (stream st from row st * Mpad);
+//   ROWS_LIST    base model, student step: the branch's drop-path sample list, K x tokens compact rows (attention: K samples);
+//   ROWS_LIST2   two-stream model, student step, MLP branch: the kept rows of the mean stream, then those of the covariance stream, stacked
+//                without a gap (fc1 / fc2 share their weights between the streams; the two-stream attention needs both streams of a sample);
+//   ROWS_MASKED  the last block's MLP on the R compact rows of the masked-patch list (base model; student step, and the teacher of a step
+//                whose targets take the masked rows only): LN2 gathers them, fc1 / fc2 are R-row GEMMs, the residual epilogue of fc2 reads
+//                x_mid and writes x_out / the saved branch output at the listed rows (the other rows of x_out are never read: the head and the
+//                final-norm backward go through the same list).
+// A list runs when it drops somebody and nobody's list drops everybody (nobody dropped: the dense launches; everybody: dense too, 0 x branch).
+enum RowMode { ROWS_ALL, ROWS_LIST, ROWS_LIST2, ROWS_MASKED };
+enum Pass { PASS_DENSE, PASS_TEACHER, PASS_STUDENT };     // drop-in forward or dense-target teacher / teacher of a step / student of a step
+struct BranchRows {
+    RowMode mode = ROWS_ALL;
+    int K = 0;                    // samples of the attention core
+    int n[2] = {0, 0};            // rows of each stream
+    size_t off[2] = {0, 0};       // first row of each stream in the branch's buffers
+    int rows = 0;                 // rows of a launch over the stacked streams: off[S-1] + n[S-1]
+    int red = 0;                  // reduction length of the wgrads: rows to the next multiple of 64 (pad rows of every dY are zero)
+    DpList d[2] = {};             // ROWS_LIST / ROWS_LIST2: each stream's sample list (zero otherwise)
+    const int* rowmap[2] = {nullptr, nullptr};    // row list of each stream's residual epilogue / row-list kernels (null: dense)
+    const int* rowcnt[2] = {nullptr, nullptr};
+};
+static BranchRows branch_rows(const uvit_engine* e, int l, int branch, Pass pass, int Bc) {
+    const int S = e->S;
+    BranchRows r;
+    r.K = Bc; r.n[0] = r.n[1] = Bc * e->N; r.off[1] = e->Mpad;
+    if (pass != PASS_DENSE && branch == 1 && l == e->cfg.depth - 1 && e->compact_R > 0) {
+        r.mode = ROWS_MASKED; r.n[0] = e->compact_R; r.rowmap[0] = e->rowidx; r.rowcnt[0] = e->count;
+    } else if (pass == PASS_STUDENT && e->dpl_on && (S == 1 || branch == 1)) {
+        DpList d[2] = {};
+        bool none = false, some = false;
+        for (int st = 0; st < S; ++st) {
+            dp_list_get(e, l, st, branch, d[st]);
+            none = none || d[st].K == 0; some = some || d[st].K < e->B;
+        }
+        if (!none && some) {
+            r.mode = S == 1 ? ROWS_LIST : ROWS_LIST2;
+            r.K = d[0].K;
+            for (int st = 0; st < S; ++st) { r.d[st] = d[st]; r.n[st] = d[st].K * e->N; r.rowmap[st] = d[st].rows; r.rowcnt[st] = d[st].cnt; }
+            r.off[1] = r.n[0];
+        }
+    }
+    r.rows = (int)(r.off[S - 1] + r.n[S - 1]);
+    r.red = (int)roundup(r.rows, 64);
+    return r;
+}
+
 static int forward_layer(uvit_engine* e, const Weights& w, int l, const float* x_in, float* x_mid, float* x_out,
-                         LayerActs& a, bool save, const float* biasP, bool dp_on, float pdrop, uint32_t seed, int Bc,
-                         hipStream_t s, int R = 0, bool lists = false) {
+                         LayerActs& a, const float* biasP, bool dp_on, float pdrop, uint32_t seed, int Bc, Pass pass, hipStream_t s) {
     const LayerOff& o = e->lo.L[l];
     const int M = Bc * e->N, C = e->C, Hd = e->Hd, S = e->S;
-    const size_t Mp = e->Mpad;                                   // row offset of stream 1
-    const int Mall = (int)((size_t)(S - 1) * Mp + M);
+    const size_t Mp = e->Mpad;                                   // row offset of stream 1 in the residual stream
+    const bool save = pass == PASS_STUDENT;                      // keep what backward needs
+    const BranchRows at = branch_rows(e, l, 0, pass, Bc), ml = branch_rows(e, l, 1, pass, Bc);
     // counters of the persistent GEMMs' dynamic tile assignment: one block per stream (the teacher and student forwards run side by side)
-    static const bool dyn_tiles = !(getenv("UVIT_DYN_TILES") && getenv("UVIT_DYN_TILES")[0] == '0');     // A/B switch
-    unsigned* const tcnt = (e->tile_cnt && dyn_tiles) ? e->tile_cnt + ((e->dual && s == e->aux) ? 16 : 0) : nullptr;
-    // drop-path sample lists of the two branches of the base model: Ma / Mm rows instead of M (the masked-row last block keeps its own row list
-    // for the MLP and takes the sample list for the attention branch)
-    DpList da{}, dm{};
-    const bool la = lists && S == 1 && Bc == e->B && dp_list(e, l, 0, da);     // (also in the masked-row last block: only its MLP keeps the row list)
-    const bool lm = lists && R == 0 && S == 1 && Bc == e->B && dp_list(e, l, 1, dm);
-    const int Ma = la ? da.K * e->N : M;
-    if (la) CHECK(uvit_ln_fwd_keep_launch(x_in, da.pos, w.f + o.n1w, w.f + o.n1b, a.ln1, a.mean1, a.rstd1, x_mid, M, C, e->N, e->cfg.ln_eps, s));
-    else CHECK(uvit_ln_fwd_launch(x_in, w.f + o.n1w, w.f + o.n1b, a.ln1, a.mean1, a.rstd1, Mall, C, e->cfg.ln_eps, s));
+    unsigned* const tcnt = e->tile_cnt + ((e->dual && s == e->aux) ? 16 : 0);
+    if (at.mode == ROWS_LIST) CHECK(uvit_ln_fwd_keep_launch(x_in, at.d[0].pos, w.f + o.n1w, w.f + o.n1b, a.ln1, a.mean1, a.rstd1, x_mid, M, C, e->N, e->cfg.ln_eps, s));
+    else CHECK(uvit_ln_fwd_launch(x_in, w.f + o.n1w, w.f + o.n1b, a.ln1, a.mean1, a.rstd1, at.rows, C, e->cfg.ln_eps, s));
     for (int st = 0; st < S; ++st) {     // same qkv.weight for both streams (modeling_finetune_dist.py:121,127)
-        GemmEpi q; q.out = a.qkv + st * Mp * 3 * C; q.bias = w.f + off_qb(o, st); q.bias2 = w.f + off_vb(o, st); q.ldo = 3 * C;
+        GemmEpi q; q.out = a.qkv + at.off[st] * 3 * C; q.bias = w.f + off_qb(o, st); q.bias2 = w.f + off_vb(o, st); q.ldo = 3 * C;
         q.tile_counter = tcnt;
-        CHECK(GEMM_NT(st ? EPI_QKV_ELU : EPI_QKV, a.ln1 + st * Mp * C, w.b + o.qkvw, Ma, 3 * C, C, C, C, &q, s));
+        CHECK(GEMM_NT(st ? EPI_QKV_ELU : EPI_QKV, a.ln1 + at.off[st] * C, w.b + o.qkvw, at.n[st], 3 * C, C, C, C, &q, s));
     }
     if (S == 1) {
-        CHECK(uvit_attn_fwd_launch(a.qkv, biasP, a.attn, a.lse, la ? da.K : Bc, e->H, e->N, e->NP, 0.125f, pdrop, seed, (uint32_t)l, s,
-                                   la ? da.bmap : nullptr));
+        CHECK(uvit_attn_fwd_launch(a.qkv, biasP, a.attn, a.lse, at.K, e->H, e->N, e->NP, 0.125f, pdrop, seed, (uint32_t)l, s, at.d[0].bmap));
     } else {
         CHECK(uvit_attn2_fwd_launch(a.qkv, a.qkv + Mp * 3 * C, biasP, a.attn, a.attn + Mp * C, a.lse, Bc, e->H, e->N, e->NP, 0.125f,
                                     pdrop, seed, (uint32_t)l, s));
@@ -637,37 +660,35 @@ static int forward_layer(uvit_engine* e, const Weights& w, int l, const float* x
     for (int st = 0; st < S; ++st) {
         GemmEpi p; p.out = x_mid + st * Mp * C; p.out2 = save ? a.projout + st * Mp * C : nullptr; p.bias = w.f + off_projb(o, st);
         p.gamma = w.f + o.g1; p.resid = x_in + st * Mp * C; p.rowscale = dp_ptr(e, dp_on, l, st, 0, Bc); p.ldo = C; p.tokens = e->N;
-        if (la) { p.rowmap = da.rows; p.rowcount = da.cnt; }
-        const bool pp = prof_begin(UVIT_PROF_PROJ, Ma);
-        CHECK(GEMM_NT(EPI_RESID, a.attn + st * Mp * C, w.b + off_projw(o, st), Ma, C, C, C, C, &p, s));
+        p.rowmap = at.rowmap[st]; p.rowcount = at.rowcnt[st];
+        const bool pp = prof_begin(UVIT_PROF_PROJ, at.n[st]);
+        CHECK(GEMM_NT(EPI_RESID, a.attn + at.off[st] * C, w.b + off_projw(o, st), at.n[st], C, C, C, C, &p, s));
         prof_end(pp);
     }
-    DpList d2[2] = {};
-    const bool lm2 = lists && S == 2 && Bc == e->B && dp_list2(e, l, d2);
-    const size_t off2[2] = {0, lm2 ? (size_t)d2[0].K * e->N : Mp};       // first compact row of each stream's MLP rows
-    const int Mm = lm ? dm.K * e->N : (lm2 ? (d2[0].K + d2[1].K) * e->N : (R > 0 ? R : Mall));
-    if (lm2) {
-        for (int st = 0; st < 2; ++st)
-            CHECK(uvit_ln_fwd_keep_launch(x_mid + st * Mp * C, d2[st].pos, w.f + o.n2w, w.f + o.n2b, a.ln2 + off2[st] * C, a.mean2 + off2[st],
-                                          a.rstd2 + off2[st], x_out + st * Mp * C, M, C, e->N, e->cfg.ln_eps, s));
-    } else
-    if (R > 0) CHECK(uvit_ln_fwd_gather_launch(x_mid, e->rowidx, e->count, w.f + o.n2w, w.f + o.n2b, a.ln2, a.mean2, a.rstd2, R, C, e->cfg.ln_eps, s));
-    else if (lm) CHECK(uvit_ln_fwd_keep_launch(x_mid, dm.pos, w.f + o.n2w, w.f + o.n2b, a.ln2, a.mean2, a.rstd2, x_out, M, C, e->N, e->cfg.ln_eps, s));
-    else CHECK(uvit_ln_fwd_launch(x_mid, w.f + o.n2w, w.f + o.n2b, a.ln2, a.mean2, a.rstd2, Mall, C, e->cfg.ln_eps, s));
+    switch (ml.mode) {
+    case ROWS_LIST: case ROWS_LIST2:     // each stream's kept rows to its compact rows; the dropped rows copied to x_out
+        for (int st = 0; st < S; ++st)
+            CHECK(uvit_ln_fwd_keep_launch(x_mid + st * Mp * C, ml.d[st].pos, w.f + o.n2w, w.f + o.n2b, a.ln2 + ml.off[st] * C, a.mean2 + ml.off[st],
+                                          a.rstd2 + ml.off[st], x_out + st * Mp * C, M, C, e->N, e->cfg.ln_eps, s));
+        break;
+    case ROWS_MASKED:
+        CHECK(uvit_ln_fwd_gather_launch(x_mid, e->rowidx, e->count, w.f + o.n2w, w.f + o.n2b, a.ln2, a.mean2, a.rstd2, ml.rows, C, e->cfg.ln_eps, s));
+        break;
+    case ROWS_ALL:
+        CHECK(uvit_ln_fwd_launch(x_mid, w.f + o.n2w, w.f + o.n2b, a.ln2, a.mean2, a.rstd2, ml.rows, C, e->cfg.ln_eps, s));
+        break;
+    }
     GemmEpi f1; f1.out = a.a; f1.out2 = save ? a.h : nullptr; f1.bias = w.f + o.fc1b; f1.ldo = Hd; f1.tile_counter = tcnt;
-    const bool prof = prof_begin(save ? UVIT_PROF_FC1_S : UVIT_PROF_FC1_T, Mm);
+    const bool prof = prof_begin(save ? UVIT_PROF_FC1_S : UVIT_PROF_FC1_T, ml.rows);
     // student (save): a.h receives gelu'(h) -- all that backward needs of h -- computed beside gelu(h)
-    CHECK(GEMM_NT(save ? EPI_GELU_DG : EPI_GELU, a.ln2, w.b + o.fc1w, Mm, Hd, C, C, C, &f1, s));
+    CHECK(GEMM_NT(save ? EPI_GELU_DG : EPI_GELU, a.ln2, w.b + o.fc1w, ml.rows, Hd, C, C, C, &f1, s));
     prof_end(prof);
     for (int st = 0; st < S; ++st) {
         GemmEpi f2; f2.out = x_out + st * Mp * C; f2.out2 = save ? a.mlpout + st * Mp * C : nullptr; f2.bias = w.f + o.fc2b;
         f2.gamma = w.f + o.g2; f2.resid = x_mid + st * Mp * C; f2.rowscale = dp_ptr(e, dp_on, l, st, 1, Bc); f2.ldo = C; f2.tokens = e->N;
-        if (R > 0) { f2.rowmap = e->rowidx; f2.rowcount = e->count; }
-        else if (lm) { f2.rowmap = dm.rows; f2.rowcount = dm.cnt; }
-        else if (lm2) { f2.rowmap = d2[st].rows; f2.rowcount = d2[st].cnt; }
-        const int M2 = R > 0 ? R : (lm ? Mm : (lm2 ? d2[st].K * e->N : M));
-        const bool pf2 = prof_begin(UVIT_PROF_FC2, M2);
-        CHECK(GEMM_NT(EPI_RESID, a.a + (lm2 ? off2[st] : st * Mp) * Hd, w.b + o.fc2w, M2, C, Hd, Hd, Hd, &f2, s));
+        f2.rowmap = ml.rowmap[st]; f2.rowcount = ml.rowcnt[st];
+        const bool pf2 = prof_begin(UVIT_PROF_FC2, ml.n[st]);
+        CHECK(GEMM_NT(EPI_RESID, a.a + ml.off[st] * Hd, w.b + o.fc2w, ml.n[st], C, Hd, Hd, Hd, &f2, s));
         prof_end(pf2);
     }
     return UVIT_OK;
@@ -712,9 +733,8 @@ static int run_forward(uvit_engine* e, int which, const float* images, const int
     int n_t = 0;
     for (int l = 0; l < e->cfg.depth; ++l) {
         if (use_saved) {
-            const bool last_compact = save_student && !teacher && l == e->cfg.depth - 1 && e->compact_R > 0;
-            CHECK(forward_layer(e, w, l, e->X[l], e->XM[l], e->X[l + 1], e->acts[l], save_student && !teacher, biasP, dp_on,
-                                pdrop, aseed, Bc, s, last_compact ? e->compact_R : 0, !teacher && e->dpl_on));
+            CHECK(forward_layer(e, w, l, e->X[l], e->XM[l], e->X[l + 1], e->acts[l], biasP, dp_on, pdrop, aseed, Bc,
+                                save_student && !teacher ? PASS_STUDENT : PASS_DENSE, s));
         } else {
             float* xin = e->tX[l & 1]; float* xout = e->tX[(l + 1) & 1];
             // `[targets[i] for i in target_layers]` (engine_for_cyclical.py:92): a layer listed twice is summed twice and the
@@ -722,8 +742,7 @@ static int run_forward(uvit_engine* e, int which, const float* images, const int
             const bool dense = hp_targets->target_batch_norm || hp_targets->target_instance_norm ||
                                hp_targets->post_target_instance_norm || !hp_targets->target_layer_norm_last;
             // the teacher's last block feeds nothing but the target rows: with a masked-row bound its MLP runs on those rows only
-            const int Rt = (l == e->cfg.depth - 1 && !dense) ? e->compact_R : 0;
-            CHECK(forward_layer(e, w, l, xin, e->tXM, xout, e->tacts, false, biasP, false, 0.f, 0, Bc, s, Rt));
+            CHECK(forward_layer(e, w, l, xin, e->tXM, xout, e->tacts, biasP, false, 0.f, 0, Bc, dense ? PASS_DENSE : PASS_TEACHER, s));
             if (dense && Bc != e->B) return UVIT_ERR_ARG;
             for (int k = 0; k < hp_targets->n_target_layers; ++k) {
                 if (hp_targets->target_layers[k] != l) continue;
@@ -834,6 +853,25 @@ extern "C" void* uvit_engine_ws_ptr(uvit_engine* e, const char* name, int layer)
 }
 
 // ---- training step ----
+// Weight gradients dW += dY^T X of n Linears with their bias column sums: ONE launch of the grouped wgrad kernel when every problem
+// qualifies (uvit_gemm_tn_group_ok: dimensions multiples of 256, >= 512 reduction rows); otherwise, problem by problem in list order,
+// the bias column sums (a two-stream problem's rows from s1_row on into the *_s1 biases) and the plain TN GEMM.  Every bias is a
+// replicated no-decay accumulator; the rows between the real tokens and the reduction length are zero in dY, so both paths sum the same.
+static int wgrad(uvit_engine* e, const TnProb* p, int n, hipStream_t s) {
+    if (uvit_gemm_tn_group_ok(p, n, &e->tune)) return GEMM_TN_GROUP(p, n, s);
+    for (int i = 0; i < n; ++i) {
+        const TnProb& q = p[i];
+        const int r0 = q.s1_row ? q.s1_row : q.M;
+        const bf16* y1 = (const bf16*)q.Y + (size_t)r0 * q.ldy;
+        if (q.bias) CHECK(uvit_colsum_launch(q.Y, q.ldy, 0, q.bias_end, r0, q.bias, NREP, e->n_nd, s));
+        if (q.bias2) CHECK(uvit_colsum_launch(q.Y, q.ldy, q.bias2_begin, q.Nn - q.bias2_begin, r0, q.bias2, NREP, e->n_nd, s));
+        if (q.s1_row && q.bias_s1) CHECK(uvit_colsum_launch(y1, q.ldy, 0, q.bias_end, q.M - r0, q.bias_s1, NREP, e->n_nd, s));
+        if (q.s1_row && q.bias2_s1) CHECK(uvit_colsum_launch(y1, q.ldy, q.bias2_begin, q.Nn - q.bias2_begin, q.M - r0, q.bias2_s1, NREP, e->n_nd, s));
+        CHECK(GEMM_TN(q.Y, q.X, q.M, q.Nn, q.Kk, q.ldy, q.ldx, q.C, q.ldc, 1, s));
+    }
+    return UVIT_OK;
+}
+
 extern "C" int uvit_step_begin(uvit_engine* e, const float* images, const int64_t* mask, const uvit_step_params* hp,
                                uvit_stream stream) {
     if (!e || !images || !mask || !hp || hp->n_target_layers < 1 || hp->n_target_layers > UVIT_MAX_DEPTH) return UVIT_ERR_ARG;
@@ -849,7 +887,7 @@ extern "C" int uvit_step_begin(uvit_engine* e, const float* images, const int64_
     CHECK(uvit_zero_launch(e->grep, (size_t)NREP * e->n_nd * sizeof(float), ts));
     CHECK(uvit_zero_launch(e->loss, 64 * sizeof(float), ts));
     CHECK(uvit_zero_launch(e->dXa, e->rows_alloc() * C * sizeof(float), ts));
-    e->slab_started = false; e->ls_prefused = -1;
+    e->slab_started = false; e->bwd_next = e->cfg.depth - 1;
     // the last block's MLP on the masked rows only (see forward_layer): base model, a row bound from the host, and fewer rows than tokens
     e->compact_R = 0;
     if (e->S == 1 && hp->n_rows_hint > 0) {
@@ -894,11 +932,7 @@ extern "C" int uvit_step_begin(uvit_engine* e, const float* images, const int64_
         // and the plain TN kernel, 50 us, on the critical chain between the loss and the first dgrad)
         TnProb hw; hw.Y = e->dout[st]; hw.X = e->normed[st]; hw.C = g + lmw; hw.M = e->compact_R > 0 ? e->compact_R : e->BPpad; hw.Nn = C; hw.Kk = C;
         hw.ldy = C; hw.ldx = C; hw.ldc = C; hw.bias = RP(lmb); hw.bias_end = C;
-        if (uvit_gemm_tn_group_ok(&hw, 1, &e->tune)) CHECK(GEMM_TN_GROUP(&hw, 1, s));
-        else {
-            CHECK(uvit_colsum_launch(e->dout[st], C, 0, C, Rh, RP(lmb), NREP, e->n_nd, s));
-            CHECK(GEMM_TN(e->dout[st], e->normed[st], e->compact_R > 0 ? e->compact_R : e->BPpad, C, C, C, C, g + lmw, C, 1, s));
-        }
+        CHECK(wgrad(e, &hw, 1, s));
         GemmEpi d; d.out = e->dnormed[st]; d.ldo = C;
         CHECK(GEMM_NT(EPI_BF16, e->dout[st], wt + lmw, Rh, C, C, C, C, &d, s));
         // final LayerNorm backward scattered into the (zeroed) residual-stream gradient
@@ -910,16 +944,14 @@ extern "C" int uvit_step_begin(uvit_engine* e, const float* images, const int64_
 }
 
 extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_params* hp, uvit_stream stream) {
-    if (!e || l < 0 || l >= e->cfg.depth) return UVIT_ERR_ARG;
+    if (!e || l < 0 || l >= e->cfg.depth || l != e->bwd_next) return UVIT_ERR_ARG;     // depth-1 .. 0 after uvit_step_begin
     (void)hp;
+    e->bwd_next = l - 1;
     hipStream_t s = (hipStream_t)stream;
     const LayerOff& o = e->lo.L[l];
     LayerActs& a = e->acts[l];
     const int M = e->M, C = e->C, Hd = e->Hd, S = e->S;
     const size_t Mp = e->Mpad;
-    const int Mall = (int)e->rows_all();                      // stacked rows of a row-wise op
-    const int Mred = (int)roundup(e->rows_all(), 64);          // stacked reduction length of a wgrad (pad rows are zero in dY)
-    const int Mred1 = (int)roundup(M, 64);                     // one stream
     float* g = e->buf.grads;
     const float* pf = e->buf.params;
     const bf16* wt = (const bf16*)e->buf.params_bf16_t;
@@ -930,117 +962,68 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
     // main stream waits for the wgrad work of layer l+2.
     const int par = l & 1;
     hipStream_t ws = e->dual ? e->aux : s;
-    auto handoff = [&](int k) -> int {          // work enqueued on `s` so far is visible to the wgrad stream
-        if (!e->dual) return UVIT_OK;
-        HIPCHECK(hipEventRecord(e->ev_x[k], s));
-        HIPCHECK(hipStreamWaitEvent(ws, e->ev_x[k], 0));
-        return UVIT_OK;
-    };
     if (e->dual && l + 2 < e->cfg.depth) HIPCHECK(hipStreamWaitEvent(s, e->ev_wdone[l + 2], 0));
     bf16 *dY1 = e->dY1[par], *dY2 = e->dY2[par], *dH = e->dH[par], *dqkv = e->dqkv[par];
-    // last block with a masked-row list (see forward_layer): its MLP branch -- LayerScale backward, both dgrads, both wgrads, LN2 backward --
-    // runs on the R compact rows; dY1 / dH / dLN are compact, the LN2 backward scatters into the (zeroed) dense dXb / dY2
-    const int R = (l == e->cfg.depth - 1) ? e->compact_R : 0;
-    // drop-path sample lists (see forward_layer): the attention branch on Ma = Ka tokens rows, the MLP branch on Km tokens rows; the wgrad
-    // reductions run to the next multiple of 64 (pad rows of the dY operands are zero)
-    DpList da{}, dm{}, dm1{};
-    const bool la = S == 1 && dp_list(e, l, 0, da);
-    const bool lm = R == 0 && S == 1 && dp_list(e, l, 1, dm);
-    const bool lm1 = l > 0 && S == 1 && dp_list(e, l - 1, 1, dm1);          // the MLP branch of the layer below (its LayerScale backward rides here)
-    const int Ma = la ? da.K * e->N : M, Mac = la ? (int)roundup(Ma, 64) : Mred1;
-    // two-stream model: the MLP branch on the kept rows of both streams, stacked without a gap (see forward_layer)
-    DpList dl2[2] = {}, dl21[2] = {};
-    const bool lm2 = dp_list2(e, l, dl2), lm21 = l > 0 && dp_list2(e, l - 1, dl21);
-    const size_t off2[2] = {0, lm2 ? (size_t)dl2[0].K * e->N : Mp}, off21[2] = {0, lm21 ? (size_t)dl21[0].K * e->N : Mp};
-    const int Mmlp = R > 0 ? R : (lm ? (int)roundup((size_t)dm.K * e->N, 64) : (lm2 ? (int)roundup((size_t)(dl2[0].K + dl2[1].K) * e->N, 64) : Mall));
-    const int Mmlp_red = (R > 0 || lm || lm2) ? Mmlp : Mred;
-    // weight gradients: one grouped launch per layer (bias column sums of fc1 / q / v fused) when every Linear has
-    // 256-multiple dimensions; otherwise one launch per Linear as the operands become available
+    // the rows of each branch, as the forward ran them (branch_rows); compact branches run their row-wise launches to the reduction length,
+    // so that the pad rows of the compact dY they write are zero.  The layer below's MLP rows: its LayerScale backward rides in this layer's
+    // LayerNorm 1 backward
+    const BranchRows at = branch_rows(e, l, 0, PASS_STUDENT, e->B), ml = branch_rows(e, l, 1, PASS_STUDENT, e->B);
+    const BranchRows nx = l > 0 ? branch_rows(e, l - 1, 1, PASS_STUDENT, e->B) : BranchRows{};
+    const int Mmlp = ml.mode == ROWS_ALL ? ml.rows : ml.red;
+    // weight gradients of the block, launched once the dgrad chain has produced every dY (wgrad)
     TnProb wg[UVIT_TN_GROUP_MAX];
     int nwg = 0;
     {
-        TnProb& f2 = wg[nwg++]; f2.Y = dY1; f2.X = a.a; f2.C = g + o.fc2w; f2.M = Mmlp_red; f2.Nn = C; f2.Kk = Hd; f2.ldy = C; f2.ldx = Hd; f2.ldc = Hd;
-        TnProb& f1 = wg[nwg++]; f1.Y = dH; f1.X = a.ln2; f1.C = g + o.fc1w; f1.M = Mmlp_red; f1.Nn = Hd; f1.Kk = C; f1.ldy = Hd; f1.ldx = C; f1.ldc = C;
+        TnProb& f2 = wg[nwg++]; f2.Y = dY1; f2.X = a.a; f2.C = g + o.fc2w; f2.M = ml.red; f2.Nn = C; f2.Kk = Hd; f2.ldy = C; f2.ldx = Hd; f2.ldc = Hd;
+        TnProb& f1 = wg[nwg++]; f1.Y = dH; f1.X = a.ln2; f1.C = g + o.fc1w; f1.M = ml.red; f1.Nn = Hd; f1.Kk = C; f1.ldy = Hd; f1.ldx = C; f1.ldc = C;
         f1.bias = RP(o.fc1b); f1.bias_end = Hd;
         for (int st = 0; st < S; ++st) {
-            TnProb& pj = wg[nwg++]; pj.Y = dY2 + st * Mp * C; pj.X = a.attn + st * Mp * C; pj.C = g + off_projw(o, st);
-            pj.M = Mac; pj.Nn = C; pj.Kk = C; pj.ldy = C; pj.ldx = C; pj.ldc = C;
+            TnProb& pj = wg[nwg++]; pj.Y = dY2 + at.off[st] * C; pj.X = a.attn + at.off[st] * C; pj.C = g + off_projw(o, st);
+            pj.M = (int)roundup(at.n[st], 64); pj.Nn = C; pj.Kk = C; pj.ldy = C; pj.ldx = C; pj.ldc = C;
         }
-        TnProb& qk = wg[nwg++]; qk.Y = dqkv; qk.X = a.ln1; qk.C = g + o.qkvw; qk.M = la ? Mac : Mred; qk.Nn = 3 * C; qk.Kk = C; qk.ldy = 3 * C; qk.ldx = C; qk.ldc = C;
+        TnProb& qk = wg[nwg++]; qk.Y = dqkv; qk.X = a.ln1; qk.C = g + o.qkvw; qk.M = at.red; qk.Nn = 3 * C; qk.Kk = C; qk.ldy = 3 * C; qk.ldx = C; qk.ldc = C;
         qk.bias = RP(off_qb(o, 0)); qk.bias_end = C; qk.bias2 = RP(off_vb(o, 0)); qk.bias2_begin = 2 * C;
         // two-stream: the q / v biases differ per stream while the stacked wgrad reduces over both: the token chunks of stream 1
         // (rows from Mpad on) sum into the covariance stream's biases (round 4; was 4 colsum launches per layer)
         if (S == 2) { qk.bias_s1 = RP(off_qb(o, 1)); qk.bias2_s1 = RP(off_vb(o, 1)); qk.s1_row = (int)Mp; }
     }
-    const bool grouped = uvit_gemm_tn_group_ok(wg, nwg, &e->tune);
     // --- MLP branch: x_out = x_mid + dp * gamma2 * fc2(gelu(fc1(ln2(x_mid))))   (weights shared by the streams)
-    // (the LayerScale backward of a branch rides in the LayerNorm backward that produces its input; in the two-stream
-    //  model that kernel is launched once per stream, because drop-path scales and the proj bias differ per stream)
-    const bool fuse_ls = true;
-    if (R > 0)       // compact dY1 from the residual-stream gradient and the saved branch output at the listed rows (S == 1)
-        CHECK(uvit_ls_bwd_launch(e->dXa, a.mlpout, pf + o.g2, dp_ptr(e, dp_on, l, 0, 1, e->B), dY1, RP(o.g2), RP(o.fc2b), R, C, e->N, NREP,
-                                 e->n_nd, s, e->rowidx, e->count));
-    else if (e->ls_prefused != l && lm2)   // two-stream: compact dY1 of each stream's kept samples, stacked; the second launch zero-fills the pad rows
-        for (int st = 0; st < 2; ++st)
-            CHECK(uvit_ls_bwd_launch(e->dXa + st * Mp * C, a.mlpout + st * Mp * C, pf + o.g2, dp_ptr(e, dp_on, l, st, 1, e->B), dY1 + off2[st] * C,
-                                     RP(o.g2), RP(o.fc2b), st == 0 ? dl2[0].K * e->N : Mmlp - dl2[0].K * e->N, C, e->N, NREP, e->n_nd, s,
-                                     dl2[st].rows, dl2[st].cnt));
-    else if (e->ls_prefused != l && lm)    // compact dY1 of the kept samples (pad rows zero)
-        CHECK(uvit_ls_bwd_launch(e->dXa, a.mlpout, pf + o.g2, dp_ptr(e, dp_on, l, 0, 1, e->B), dY1, RP(o.g2), RP(o.fc2b), Mmlp, C, e->N, NREP,
-                                 e->n_nd, s, dm.rows, dm.cnt));
-    else if (e->ls_prefused != l)
-        for (int st = 0; st < S; ++st)
-            CHECK(uvit_ls_bwd_launch(e->dXa + st * Mp * C, a.mlpout + st * Mp * C, pf + o.g2, dp_ptr(e, dp_on, l, st, 1, e->B), dY1 + st * Mp * C,
-                                     RP(o.g2), RP(o.fc2b), M, C, e->N, NREP, e->n_nd, s));
-    e->ls_prefused = -1;
-    if (!grouped) {
-        CHECK(handoff(0));
-        CHECK(GEMM_TN(dY1, a.a, Mmlp_red, C, Hd, C, Hd, g + o.fc2w, Hd, 1, ws));
-    }
+    // (the LayerScale backward of a branch rides in the LayerNorm backward that produces its input -- below the top layer, the MLP branch's
+    //  rides in the LayerNorm 1 backward of the layer above; in the two-stream model that kernel is launched once per stream, because
+    //  drop-path scales and the proj bias differ per stream)
+    if (l == e->cfg.depth - 1)
+        for (int st = 0; st < S; ++st)      // a compact branch's last stream runs to the reduction length: the kernel zero-fills the pad rows
+            CHECK(uvit_ls_bwd_launch(e->dXa + st * Mp * C, a.mlpout + st * Mp * C, pf + o.g2, dp_ptr(e, dp_on, l, st, 1, e->B), dY1 + ml.off[st] * C,
+                                     RP(o.g2), RP(o.fc2b), (ml.mode == ROWS_ALL || st + 1 < S) ? ml.n[st] : ml.red - (int)ml.off[st], C, e->N,
+                                     NREP, e->n_nd, s, ml.rowmap[st], ml.rowcnt[st]));
     GemmEpi d1; d1.out = dH; d1.aux = a.h; d1.ldo = Hd;
     CHECK(GEMM_NT(EPI_MULAUX, dY1, wt + o.fc2w, Mmlp, Hd, C, C, C, &d1, s));      // dH = (dY.W2) * gelu'(h)
-    if (!grouped) {
-        CHECK(handoff(1));
-        CHECK(uvit_colsum_launch(dH, Hd, 0, Hd, Mmlp, RP(o.fc1b), NREP, e->n_nd, ws));
-        CHECK(GEMM_TN(dH, a.ln2, Mmlp_red, Hd, C, Hd, C, g + o.fc1w, C, 1, ws));
-    }
     GemmEpi d2; d2.out = e->dLN; d2.ldo = C;
     CHECK(GEMM_NT(EPI_BF16, dH, wt + o.fc1w, Mmlp, C, Hd, Hd, Hd, &d2, s));
     // --- attention branch: x_mid = x_in + dp * gamma1 * proj(attn(ln1(x_in)))   (proj differs per stream)
-    if (lm2) {
-        // two-stream: LayerNorm 2 backward through each stream's MLP list; the attention branch's LayerScale backward stays dense
-        for (int st = 0; st < 2; ++st) {
-            const size_t ro = st * Mp, eo = ro * C;
-            CHECK(uvit_ln_bwd_keep_launch(e->dLN + off2[st] * C, e->XM[l] + eo, dl2[st].pos, a.mean2 + off2[st], a.rstd2 + off2[st], pf + o.n2w,
+    // LayerNorm 2 backward + the attention branch's LayerScale backward
+    if (ml.mode != ROWS_MASKED && (ml.mode != ROWS_ALL || at.mode == ROWS_LIST)) {
+        // dense walk with each branch's sample list (also zero-fills the pad rows of dqkv: the attention backward writes K samples)
+        for (int st = 0; st < S; ++st) {
+            const size_t eo = st * Mp * C;
+            CHECK(uvit_ln_bwd_keep_launch(e->dLN + ml.off[st] * C, e->XM[l] + eo, ml.d[st].pos, a.mean2 + ml.off[st], a.rstd2 + ml.off[st], pf + o.n2w,
                                           e->dXa + eo, e->dXb + eo, RP(o.n2w), RP(o.n2b), a.projout + eo, pf + o.g1, dp_ptr(e, dp_on, l, st, 0, e->B),
-                                          dY2 + eo, RP(o.g1), RP(off_projb(o, st)), nullptr, nullptr, e->N, M, C, NREP, e->n_nd, s));
+                                          dY2 + eo, RP(o.g1), RP(off_projb(o, st)), at.d[st].pos, at.d[st].cnt, e->N, M, C, NREP, e->n_nd, s, 0,
+                                          at.mode == ROWS_LIST ? dqkv : nullptr, 3 * C));
         }
-    } else if (R == 0 && (la || lm)) {
-        // LayerNorm 2 backward (MLP list) + the attention branch's LayerScale backward (attention list) over the dense rows
-        CHECK(uvit_ln_bwd_keep_launch(e->dLN, e->XM[l], lm ? dm.pos : nullptr, a.mean2, a.rstd2, pf + o.n2w, e->dXa, e->dXb, RP(o.n2w), RP(o.n2b),
-                                      a.projout, pf + o.g1, dp_ptr(e, dp_on, l, 0, 0, e->B), dY2, RP(o.g1), RP(off_projb(o, 0)),
-                                      la ? da.pos : nullptr, la ? da.cnt : nullptr, e->N, M, C, NREP, e->n_nd, s, 0,
-                                      la ? dqkv : nullptr, 3 * C));      // (also zero-fills the pad rows of dqkv: the attention backward writes Ka samples)
-    } else if (fuse_ls) {
+    } else {
+        // dense, or the row-list kernel of the masked-row last block: dY1 / mean / rstd compact, the (zeroed) dense dXb / dY2 written at the
+        // listed rows, dY2 compact by the attention list when there is one
         for (int st = 0; st < S; ++st) {
             const size_t ro = st * Mp, eo = ro * C;
             CHECK(uvit_ln_bwd_ls_launch(e->dLN + eo, e->XM[l] + eo, a.mean2 + ro, a.rstd2 + ro, pf + o.n2w, e->dXa + eo, e->dXb + eo,
                                         RP(o.n2w), RP(o.n2b), a.projout + eo, pf + o.g1, dp_ptr(e, dp_on, l, st, 0, e->B), dY2 + eo,
-                                        RP(o.g1), RP(off_projb(o, st)), e->N, R > 0 ? R : M, C, NREP, e->n_nd, s,
-                                        R > 0 ? e->rowidx : nullptr, R > 0 ? e->count : nullptr,
-                                        (R > 0 && la) ? da.pos : nullptr));      // masked-row last block: dY2 compact by the attention list (rest pre-zeroed)
+                                        RP(o.g1), RP(off_projb(o, st)), e->N, ml.n[st], C, NREP, e->n_nd, s, ml.rowmap[st], ml.rowcnt[st], at.d[st].pos));
         }
-    } else {
-        CHECK(uvit_ln_bwd_launch(e->dLN, e->XM[l], a.mean2, a.rstd2, pf + o.n2w, e->dXa, e->dXb, RP(o.n2w), RP(o.n2b), Mall, C, NREP, e->n_nd, s));
-        for (int st = 0; st < S; ++st)
-            CHECK(uvit_ls_bwd_launch(e->dXb + st * Mp * C, a.projout + st * Mp * C, pf + o.g1, dp_ptr(e, dp_on, l, st, 0, e->B), dY2 + st * Mp * C,
-                                     RP(o.g1), RP(off_projb(o, st)), M, C, e->N, NREP, e->n_nd, s));
     }
-    if (!grouped) CHECK(handoff(2));
     for (int st = 0; st < S; ++st) {
-        if (!grouped) CHECK(GEMM_TN(dY2 + st * Mp * C, a.attn + st * Mp * C, Mac, C, C, C, C, g + off_projw(o, st), C, 1, ws));
-        GemmEpi d3; d3.out = e->dAttn + st * Mp * C; d3.ldo = C;
-        CHECK(GEMM_NT(EPI_BF16, dY2 + st * Mp * C, wt + off_projw(o, st), Ma, C, C, C, C, &d3, s));
+        GemmEpi d3; d3.out = e->dAttn + at.off[st] * C; d3.ldo = C;
+        CHECK(GEMM_NT(EPI_BF16, dY2 + at.off[st] * C, wt + off_projw(o, st), at.n[st], C, C, C, C, &d3, s));
     }
     const float* biasP = e->biasP_s;
     float* slabs = e->cfg.use_shared_rel_pos_bias ? e->slabs : nullptr;
@@ -1050,11 +1033,12 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
         // of layer l was last read by the reduction of layer l + 2, which precedes ev_wdone[l + 2] on that stream (waited for above).
         void* dsw = slabs ? e->ds_ws[par] : nullptr;
         if (S == 1) {
-            // (a compact launch writes Ka samples: the rows up to the wgrad's reduction length are zero-filled by the LayerNorm 2 backward above,
+            // (a compact launch writes K samples: the rows up to the wgrad's reduction length are zero-filled by the LayerNorm 2 backward above,
             //  or here in the masked-row last block, whose LayerNorm 2 backward is the row-list kernel)
-            if (la && R > 0 && Mac > Ma) CHECK(uvit_zero_launch(dqkv + (size_t)Ma * 3 * C, (size_t)(Mac - Ma) * 3 * C * sizeof(bf16), s));
-            CHECK(uvit_attn_bwd_fused_launch(a.qkv, a.attn, e->dAttn, biasP, a.lse, e->delta, dqkv, dsw, dsw != nullptr, la ? da.K : e->B, e->H,
-                                             e->N, e->NP, 0.125f, pdrop, e->last_seed, (uint32_t)l, s, la ? da.bmap : nullptr));
+            if (at.mode == ROWS_LIST && ml.mode == ROWS_MASKED && at.red > at.rows)
+                CHECK(uvit_zero_launch(dqkv + (size_t)at.rows * 3 * C, (size_t)(at.red - at.rows) * 3 * C * sizeof(bf16), s));
+            CHECK(uvit_attn_bwd_fused_launch(a.qkv, a.attn, e->dAttn, biasP, a.lse, e->delta, dqkv, dsw, dsw != nullptr, at.K, e->H,
+                                             e->N, e->NP, 0.125f, pdrop, e->last_seed, (uint32_t)l, s, at.d[0].bmap));
         } else {
             CHECK(uvit_attn2_bwd_launch(a.qkv, a.qkv + Mp * 3 * C, a.attn, a.attn + Mp * C, e->dAttn, e->dAttn + Mp * C, biasP, a.lse,
                                         e->delta, dqkv, dqkv + Mp * 3 * C, dsw, dsw != nullptr, e->B, e->H, e->N, e->NP, 0.125f, pdrop,
@@ -1062,57 +1046,42 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
         }
         if (dsw) {
             if (e->dual) { HIPCHECK(hipEventRecord(e->ev_ds, s)); HIPCHECK(hipStreamWaitEvent(ws, e->ev_ds, 0)); }
-            if (S == 1) CHECK(uvit_attn_dbias_reduce_launch(dsw, slabs, e->slab_started ? 1 : 0, la ? da.K : e->B, e->H, e->N, e->NP, ws));
+            if (S == 1) CHECK(uvit_attn_dbias_reduce_launch(dsw, slabs, e->slab_started ? 1 : 0, at.K, e->H, e->N, e->NP, ws));
             else CHECK(uvit_attn2_dbias_reduce_launch(dsw, slabs, e->slab_started ? 1 : 0, e->B, e->H, e->N, e->NP, ws));
         }
     }
     e->slab_started = true;
-    CHECK(handoff(3));
-    if (!grouped)
-        for (int st = 0; st < S; ++st) {
-            CHECK(uvit_colsum_launch(dqkv + st * Mp * 3 * C, 3 * C, 0, C, Ma, RP(off_qb(o, st)), NREP, e->n_nd, ws));
-            CHECK(uvit_colsum_launch(dqkv + st * Mp * 3 * C, 3 * C, 2 * C, C, Ma, RP(off_vb(o, st)), NREP, e->n_nd, ws));
-        }
-    if (grouped) CHECK(GEMM_TN_GROUP(wg, nwg, ws));
-    else CHECK(GEMM_TN(dqkv, a.ln1, la ? Mac : Mred, 3 * C, C, 3 * C, C, g + o.qkvw, C, 1, ws));
+    if (e->dual) { HIPCHECK(hipEventRecord(e->ev_x, s)); HIPCHECK(hipStreamWaitEvent(ws, e->ev_x, 0)); }    // every dY of the block is there
+    CHECK(wgrad(e, wg, nwg, ws));
     if (e->dual) HIPCHECK(hipEventRecord(e->ev_wdone[l], ws));
     GemmEpi d4; d4.out = e->dLN; d4.ldo = C;
-    CHECK(GEMM_NT(EPI_BF16, dqkv, wt + o.qkvw, la ? Ma : Mall, C, 3 * C, 3 * C, 3 * C, &d4, s));
-    if (lm21) {
-        // two-stream: LayerNorm 1 backward (dense) + the LayerScale backward of layer l-1's MLP branch into its stacked compact dY1
-        if (e->dual && l + 1 < e->cfg.depth) HIPCHECK(hipStreamWaitEvent(s, e->ev_wdone[l + 1], 0));
-        const LayerOff& on = e->lo.L[l - 1];
-        for (int st = 0; st < 2; ++st) {
+    CHECK(GEMM_NT(EPI_BF16, dqkv, wt + o.qkvw, at.rows, C, 3 * C, 3 * C, 3 * C, &d4, s));
+    // LayerNorm 1 backward + the LayerScale backward of layer l-1's MLP branch into its dY1, of parity (l-1) & 1, last read by the wgrad of
+    // layer l+1
+    if (l > 0 && e->dual && l + 1 < e->cfg.depth) HIPCHECK(hipStreamWaitEvent(s, e->ev_wdone[l + 1], 0));
+    const LayerOff& on = e->lo.L[l > 0 ? l - 1 : 0];
+    bf16* dYn = l > 0 ? e->dY1[(l - 1) & 1] : nullptr;
+    if (at.mode == ROWS_LIST || nx.mode != ROWS_ALL) {
+        // dense walk with the attention list and the list of layer l-1's MLP (two-stream: its stacked compact dY1, the second launch zero-fills the pad rows)
+        for (int st = 0; st < S; ++st) {
             const size_t ro = st * Mp, eo = ro * C;
-            CHECK(uvit_ln_bwd_keep_launch(e->dLN + eo, e->X[l] + eo, nullptr, a.mean1 + ro, a.rstd1 + ro, pf + o.n1w, e->dXb + eo, e->dXa + eo,
-                                          RP(o.n1w), RP(o.n1b), e->acts[l - 1].mlpout + eo, pf + on.g2, dp_ptr(e, dp_on, l - 1, st, 1, e->B),
-                                          e->dY1[(l - 1) & 1] + off21[st] * C, RP(on.g2), RP(on.fc2b), dl21[st].pos, st == 1 ? dl21[1].cnt : nullptr,
-                                          e->N, M, C, NREP, e->n_nd, s, st == 1 ? dl21[0].K * e->N : 0));
+            const bool last = st + 1 == S;
+            CHECK(uvit_ln_bwd_keep_launch(e->dLN + eo, e->X[l] + eo, at.d[st].pos, a.mean1 + ro, a.rstd1 + ro, pf + o.n1w, e->dXb + eo, e->dXa + eo,
+                                          RP(o.n1w), RP(o.n1b), l > 0 ? e->acts[l - 1].mlpout + eo : nullptr, l > 0 ? pf + on.g2 : nullptr,
+                                          l > 0 ? dp_ptr(e, dp_on, l - 1, st, 1, e->B) : nullptr, l > 0 ? dYn + nx.off[st] * C : nullptr,
+                                          l > 0 ? RP(on.g2) : nullptr, l > 0 ? RP(on.fc2b) : nullptr, nx.d[st].pos, last ? nx.d[st].cnt : nullptr,
+                                          e->N, M, C, NREP, e->n_nd, s, last ? (int)nx.off[st] : 0));
         }
-        e->ls_prefused = l - 1;
-    } else if (la || lm1) {
-        // LayerNorm 1 backward (attention list) + the LayerScale backward of layer l-1's MLP branch (its list), dense rows
-        if (l > 0 && e->dual && l + 1 < e->cfg.depth) HIPCHECK(hipStreamWaitEvent(s, e->ev_wdone[l + 1], 0));
-        const LayerOff& on = e->lo.L[l > 0 ? l - 1 : 0];
-        CHECK(uvit_ln_bwd_keep_launch(e->dLN, e->X[l], la ? da.pos : nullptr, a.mean1, a.rstd1, pf + o.n1w, e->dXb, e->dXa, RP(o.n1w), RP(o.n1b),
-                                      l > 0 ? e->acts[l - 1].mlpout : nullptr, l > 0 ? pf + on.g2 : nullptr,
-                                      l > 0 ? dp_ptr(e, dp_on, l - 1, 0, 1, e->B) : nullptr, l > 0 ? e->dY1[(l - 1) & 1] : nullptr,
-                                      l > 0 ? RP(on.g2) : nullptr, l > 0 ? RP(on.fc2b) : nullptr, lm1 ? dm1.pos : nullptr, lm1 ? dm1.cnt : nullptr,
-                                      e->N, M, C, NREP, e->n_nd, s));
-        if (l > 0) e->ls_prefused = l - 1;
-    } else if (fuse_ls && l > 0) {
-        // the MLP-branch LayerScale backward of layer l-1 writes dY1 of parity (l-1) & 1, last read by the wgrad of layer l+1
-        if (e->dual && l + 1 < e->cfg.depth) HIPCHECK(hipStreamWaitEvent(s, e->ev_wdone[l + 1], 0));
-        const LayerOff& on = e->lo.L[l - 1];
+    } else if (l > 0) {
         for (int st = 0; st < S; ++st) {
             const size_t ro = st * Mp, eo = ro * C;
             CHECK(uvit_ln_bwd_ls_launch(e->dLN + eo, e->X[l] + eo, a.mean1 + ro, a.rstd1 + ro, pf + o.n1w, e->dXb + eo, e->dXa + eo,
                                         RP(o.n1w), RP(o.n1b), e->acts[l - 1].mlpout + eo, pf + on.g2, dp_ptr(e, dp_on, l - 1, st, 1, e->B),
-                                        e->dY1[(l - 1) & 1] + eo, RP(on.g2), RP(on.fc2b), e->N, M, C, NREP, e->n_nd, s));
+                                        dYn + eo, RP(on.g2), RP(on.fc2b), e->N, M, C, NREP, e->n_nd, s));
         }
-        e->ls_prefused = l - 1;
     } else {
-        CHECK(uvit_ln_bwd_launch(e->dLN, e->X[l], a.mean1, a.rstd1, pf + o.n1w, e->dXb, e->dXa, RP(o.n1w), RP(o.n1b), Mall, C, NREP, e->n_nd, s));
+        CHECK(uvit_ln_bwd_launch(e->dLN, e->X[l], a.mean1, a.rstd1, pf + o.n1w, e->dXb, e->dXa, RP(o.n1w), RP(o.n1b), (int)e->rows_all(), C,
+                                 NREP, e->n_nd, s));
     }
     return UVIT_OK;
 }
@@ -1133,12 +1102,7 @@ extern "C" int uvit_step_backward_embed(uvit_engine* e, uvit_stream stream) {
         TnProb& q = pe[st]; q.Y = e->dpatch[st]; q.X = e->cols; q.C = g + (st ? lo.cpew : lo.pew); q.M = (int)roundup(BP, 64); q.Nn = C; q.Kk = e->Kpe;
         q.ldy = C; q.ldx = e->Kpe; q.ldc = e->Kpe; q.bias = RP(st ? lo.cpeb : lo.peb); q.bias_end = C;
     }
-    if (uvit_gemm_tn_group_ok(pe, e->S, &e->tune)) CHECK(GEMM_TN_GROUP(pe, e->S, s));
-    else
-        for (int st = 0; st < e->S; ++st) {
-            CHECK(uvit_colsum_launch(e->dpatch[st], C, 0, C, BP, RP(st ? lo.cpeb : lo.peb), NREP, e->n_nd, s));
-            CHECK(GEMM_TN(e->dpatch[st], e->cols, (int)roundup(BP, 64), C, e->Kpe, C, e->Kpe, g + (st ? lo.cpew : lo.pew), e->Kpe, 1, s));
-        }
+    CHECK(wgrad(e, pe, e->S, s));
     if (e->cfg.use_abs_pos_emb) CHECK(uvit_pos_bwd_launch(e->dXa, g + lo.pos, e->B, e->N, C, s));     // d pos_embed = sum_b dX[b]
     if (e->dual) HIPCHECK(hipStreamWaitEvent(s, e->ev_wdone[0], 0));   // every wgrad / bias sum / bias-gradient reduction has landed
     if (e->cfg.use_shared_rel_pos_bias && e->slab_started)
