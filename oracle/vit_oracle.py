@@ -98,6 +98,11 @@ class StepHParams:
     post_target_instance_norm: bool = False   # :112-115
 
 
+def _at_least_f32(t: Tensor) -> Tensor:
+    """The reference's `.float()` (its autocast outputs are bf16 / fp16), leaving an fp64 oracle run in fp64."""
+    return t if t.dtype == torch.float64 else t.float()
+
+
 # --------------------------------------------------------------------------------------
 # parameters
 # --------------------------------------------------------------------------------------
@@ -219,9 +224,10 @@ def rel_pos_bias(p: Dict[str, Tensor], cfg: VitConfig) -> Optional[Tensor]:
     """Gather table -> (H, N, N): modeling_finetune.py:359-364."""
     if not cfg.use_shared_rel_pos_bias:
         return None
-    idx = torch.from_numpy(relative_position_index(cfg.grid)).reshape(-1)
+    table = p["rel_pos_bias.relative_position_bias_table"]
+    idx = torch.from_numpy(relative_position_index(cfg.grid)).reshape(-1).to(table.device)
     N = cfg.num_tokens
-    return p["rel_pos_bias.relative_position_bias_table"][idx].reshape(N, N, -1).permute(2, 0, 1)
+    return table[idx].reshape(N, N, -1).permute(2, 0, 1)
 
 
 def attention(p: Dict[str, Tensor], pre: str, cfg: VitConfig, x: Tensor, bias: Optional[Tensor],
@@ -239,7 +245,7 @@ def attention(p: Dict[str, Tensor], pre: str, cfg: VitConfig, x: Tensor, bias: O
         s = s + bias
     a = s.softmax(dim=-1)
     if keep is not None:
-        a = a * keep
+        a = a * keep.to(a.device)
     o = (a @ v).transpose(1, 2).reshape(B, N, C)
     return o @ p[pre + "proj.weight"].t() + p[pre + "proj.bias"]
 
@@ -278,17 +284,18 @@ def block(p: Dict[str, Tensor], i: int, cfg: VitConfig, x: Tensor, bias: Optiona
                   bias, keep)
     a = p[b + "gamma_1"] * a
     if drop and drop.path1 and drop.path1[i] is not None:
-        a = a * drop.path1[i].reshape(-1, 1, 1)
+        a = a * drop.path1[i].to(a).reshape(-1, 1, 1)
     x = x + a
     f = p[b + "gamma_2"] * mlp(p, b + "mlp.", layer_norm(x, p[b + "norm2.weight"], p[b + "norm2.bias"], cfg.ln_eps))
     if drop and drop.path2 and drop.path2[i] is not None:
-        f = f * drop.path2[i].reshape(-1, 1, 1)
+        f = f * drop.path2[i].to(f).reshape(-1, 1, 1)
     return x + f, f
 
 
 def forward_features(p: Dict[str, Tensor], cfg: VitConfig, x: Tensor, mask: Optional[Tensor],
-                     layer_results: Optional[str], drop: Optional[DropState] = None):
-    """modeling_cyclical.py:170-207."""
+                     layer_results: Optional[str], drop: Optional[DropState] = None, record: Optional[dict] = None):
+    """modeling_cyclical.py:170-207.  `record` (a dict), when given, receives the block-0 input as "x0" with its gradient
+    retained: the token-assembly output, whose gradient is dL/dx of the whole stack of blocks."""
     x = patch_embed(p, cfg, x)
     B = x.shape[0]
     if mask is not None:
@@ -297,6 +304,9 @@ def forward_features(p: Dict[str, Tensor], cfg: VitConfig, x: Tensor, mask: Opti
     x = torch.cat((p["cls_token"].expand(B, -1, -1), x), dim=1)
     if cfg.use_abs_pos_emb:
         x = x + p["pos_embed"]
+    if record is not None and x.requires_grad:
+        x.retain_grad()
+        record["x0"] = x
     bias = rel_pos_bias(p, cfg)
     z = []
     for i in range(cfg.depth):
@@ -312,9 +322,9 @@ def forward_features(p: Dict[str, Tensor], cfg: VitConfig, x: Tensor, mask: Opti
 
 def forward(p: Dict[str, Tensor], cfg: VitConfig, x: Tensor, mask: Optional[Tensor],
             return_all_tokens: bool = False, layer_results: Optional[str] = None,
-            drop: Optional[DropState] = None):
+            drop: Optional[DropState] = None, record: Optional[dict] = None):
     """The three return modes of modeling_cyclical.py:209-225."""
-    out = forward_features(p, cfg, x, mask, layer_results, drop)
+    out = forward_features(p, cfg, x, mask, layer_results, drop, record)
     if layer_results:
         return [z[:, 1:] for z in out]
     out = out[:, 1:]
@@ -328,7 +338,7 @@ def build_targets(layer_outs: List[Tensor], mask: Tensor, hp: StepHParams) -> Te
     (sample, channel)] (both affine-free, biased variance, eps 1e-5) [affine-free LayerNorm (eps 1e-5)]; mean over the
     layers; [post instance norm] [post LayerNorm]; gather the masked rows."""
     C = layer_outs[0].shape[-1]
-    vals = [layer_outs[i].float() for i in hp.target_layers]
+    vals = [_at_least_f32(layer_outs[i]) for i in hp.target_layers]
     if hp.target_batch_norm or hp.target_instance_norm:
         vals = [v.permute(0, 2, 1) for v in vals]                      # btc -> bct
         if hp.target_batch_norm:
@@ -340,24 +350,24 @@ def build_targets(layer_outs: List[Tensor], mask: Tensor, hp: StepHParams) -> Te
         vals = [F.layer_norm(v, (C,)) for v in vals]
     t = sum(vals) / len(hp.target_layers)
     if hp.post_target_instance_norm:
-        t = F.instance_norm(t.permute(0, 2, 1).float()).permute(0, 2, 1)
+        t = F.instance_norm(_at_least_f32(t.permute(0, 2, 1))).permute(0, 2, 1)
     if hp.post_target_layer_norm:
-        t = F.layer_norm(t.float(), (C,))
+        t = F.layer_norm(_at_least_f32(t), (C,))
     return t.reshape(-1, C)[mask.flatten().bool()]
 
 
 def variance_term(outputs: Tensor, hp: StepHParams) -> Tensor:
     """engine_for_cyclical.py:130-139: z0 = sqrt(var over the masked rows (unbiased) + 1e-6) per channel;
     std_loss0 = sum(relu(var_margin0 - z0)) / channels when var_w0 > 0, else 0."""
-    z0 = torch.sqrt(outputs.float().reshape(-1, outputs.shape[-1]).var(dim=0) + 1e-6)
+    z0 = torch.sqrt(_at_least_f32(outputs).reshape(-1, outputs.shape[-1]).var(dim=0) + 1e-6)
     if hp.var_w0 > 0:
         return torch.sum(F.relu(hp.var_margin0 - z0)) / z0.shape[0]
-    return torch.zeros((), dtype=torch.float32)
+    return torch.zeros((), dtype=z0.dtype, device=z0.device)
 
 
 def regression_loss(outputs: Tensor, targets: Tensor, hp: StepHParams) -> Tensor:
     """engine_for_cyclical.py:130-163: smooth-L1 / MSE + var_w0 * std_loss0, then loss_scale."""
-    outputs = outputs.float()
+    outputs = _at_least_f32(outputs)
     assert outputs.shape == targets.shape
     if hp.l2_loss:
         loss = F.mse_loss(outputs, targets)
@@ -376,7 +386,9 @@ def regression_loss(outputs: Tensor, targets: Tensor, hp: StepHParams) -> Tensor
 def clip_grad_norm(grads: Dict[str, Tensor], max_norm: float) -> Tensor:
     """torch.nn.utils.clip_grad_norm_ semantics (utils.py:375-376): global L2 norm, scale by
     min(1, max_norm / (norm + 1e-6)); returns the unclipped norm."""
-    total = torch.sqrt(sum((g.double() ** 2).sum() for g in grads.values())).float()
+    total = torch.sqrt(sum((g.double() ** 2).sum() for g in grads.values()))
+    if next(iter(grads.values())).dtype != torch.float64:
+        total = total.float()
     coef = torch.clamp(max_norm / (total + 1e-6), max=1.0)
     for g in grads.values():
         g.mul_(coef)
@@ -427,14 +439,14 @@ def train_step(params: Dict[str, Tensor], ema: Dict[str, Tensor], m: Dict[str, T
                v: Dict[str, Tensor], cfg: VitConfig, hp: StepHParams, samples: Tensor,
                mask: Tensor, step: int, drop: Optional[DropState] = None,
                lr: Optional[float] = None, wd: Optional[float] = None,
-               decay: Optional[float] = None) -> StepResult:
+               decay: Optional[float] = None, record: Optional[dict] = None) -> StepResult:
     """One iteration of engine_for_cyclical.py:45-186 (non-stochastic branch): teacher forward
-    under no_grad -> targets; student forward; loss; backward; clip; AdamW; EMA."""
+    under no_grad -> targets; student forward; loss; backward; clip; AdamW; EMA.  `record`: see forward_features."""
     with torch.no_grad():
         t_layers = forward(ema, cfg, samples, None, True, hp.layer_results)
         targets = build_targets(t_layers, mask, hp)
     leaves = {k: t.detach().clone().requires_grad_(True) for k, t in params.items()}
-    outputs = forward(leaves, cfg, samples, mask, False, None, drop)
+    outputs = forward(leaves, cfg, samples, mask, False, None, drop, record)
     loss = regression_loss(outputs, targets, hp)
     loss.backward()
     grads = {k: t.grad.detach() for k, t in leaves.items() if t.grad is not None}

@@ -86,7 +86,7 @@ def attention(p, pre, cfg, x, cov_x, bias, keep=None):
     a = torch.sigmoid(-wasserstein_distance_matmul(q, cq, k, ck) + 1e-24)
     a = (a + bias).softmax(dim=-1)
     if keep is not None:
-        a = a * keep
+        a = a * keep.to(a.device)
     mean = (a @ v).transpose(1, 2).reshape(B, N, C)
     cov = ((a ** 2) @ cv).transpose(1, 2).reshape(B, N, C)
     return (mean @ p[pre + "proj.weight"].t() + p[pre + "proj.bias"],
@@ -99,7 +99,7 @@ def block(p, i, cfg, xm, xc, bias, drop: Optional["DistDropState"]):
     ln = lambda t, n: vo.layer_norm(t, p[b + n + ".weight"], p[b + n + ".bias"], cfg.ln_eps)  # noqa: E731
     keep = drop.attn[i] if drop and drop.attn else None
     m, c = attention(p, b + "attn.", cfg, ln(xm, "norm1"), ln(xc, "norm1"), bias, keep)
-    dp = (lambda k: drop.path[k][i].reshape(-1, 1, 1) if drop and drop.path and drop.path[k][i] is not None else 1.0)
+    dp = (lambda k: drop.path[k][i].to(xm).reshape(-1, 1, 1) if drop and drop.path and drop.path[k][i] is not None else 1.0)
     xm = xm + dp(0) * (p[b + "gamma_1"] * m)
     fm = dp(1) * (p[b + "gamma_2"] * vo.mlp(p, b + "mlp.", ln(xm, "norm2")))
     xc = xc + dp(2) * (p[b + "gamma_1"] * c)
@@ -115,8 +115,9 @@ class DistDropState:
         self.path, self.attn = path, attn
 
 
-def forward_features(p, cfg, x, mask, layer_results, drop=None):
-    """modeling_cyclical_dist.py:106-144."""
+def forward_features(p, cfg, x, mask, layer_results, drop=None, record=None):
+    """modeling_cyclical_dist.py:106-144.  `record` (a dict), when given, receives the block-0 inputs of both streams as "x0" and
+    "x0_cov" with their gradients retained (vit_oracle.forward_features)."""
     B = x.shape[0]
     pe = {"patch_embed.proj.weight": p["patch_embed.proj.weight"], "patch_embed.proj.bias": p["patch_embed.proj.bias"]}
     xm = vo.patch_embed(pe, cfg, x)
@@ -128,6 +129,10 @@ def forward_features(p, cfg, x, mask, layer_results, drop=None):
         xc = xc * (1 - w) + p["cov_mask_token"] * w
     xm = torch.cat((p["cls_token"].expand(B, -1, -1), xm), dim=1)
     xc = torch.cat((p["cov_cls_token"].expand(B, -1, -1), xc), dim=1)
+    if record is not None and xm.requires_grad:
+        xm.retain_grad()
+        xc.retain_grad()
+        record["x0"], record["x0_cov"] = xm, xc
     bias = vo.rel_pos_bias(p, cfg)
     zm, zc = [], []
     for i in range(cfg.depth):
@@ -141,9 +146,9 @@ def forward_features(p, cfg, x, mask, layer_results, drop=None):
     return n(xm), n(xc)
 
 
-def forward(p, cfg, x, mask, return_all_tokens=False, layer_results=None, drop=None):
+def forward(p, cfg, x, mask, return_all_tokens=False, layer_results=None, drop=None, record=None):
     """modeling_cyclical_dist.py:146-165."""
-    m, c = forward_features(p, cfg, x, mask, layer_results, drop)
+    m, c = forward_features(p, cfg, x, mask, layer_results, drop, record)
     if layer_results:
         return [z[:, 1:] for z in m], [z[:, 1:] for z in c]
     m, c = m[:, 1:], c[:, 1:]
@@ -165,8 +170,8 @@ def wasserstein_loss(mean_out, cov_out, mean_t, cov_t, lam):
     return loss.sum() * lam
 
 
-def train_step(params, ema, m, v, cfg, hp: vo.StepHParams, samples, mask, step, lam=1e-5, drop=None):
-    """engine_for_cyclical.py:45-186 with stochastic=True."""
+def train_step(params, ema, m, v, cfg, hp: vo.StepHParams, samples, mask, step, lam=1e-5, drop=None, record=None):
+    """engine_for_cyclical.py:45-186 with stochastic=True.  `record`: see forward_features."""
     with torch.no_grad():
         tm, tc = forward(ema, cfg, samples, None, True, hp.layer_results)
         # the batch- / instance-norm variants act on the MEAN targets only (engine_for_cyclical.py:93-118); the covariance targets
@@ -175,10 +180,10 @@ def train_step(params, ema, m, v, cfg, hp: vo.StepHParams, samples, mask, step, 
         hp_cov = dataclasses.replace(hp, target_batch_norm=False, target_instance_norm=False, post_target_instance_norm=False)
         targets, cov_targets = vo.build_targets(tm, mask, hp), vo.build_targets(tc, mask, hp_cov)
     leaves = {k: t.detach().clone().requires_grad_(True) for k, t in params.items()}
-    out, cov_out = forward(leaves, cfg, samples, mask, False, None, drop)
+    out, cov_out = forward(leaves, cfg, samples, mask, False, None, drop, record)
     # loss = loss_cyc + std_loss0 * var_w0 + loss_stochastic (engine_for_cyclical.py:130-139, 161): the variance term acts on the MEAN outputs
     loss_cyc = vo.regression_loss(out, targets, vo.StepHParams(l1_beta=hp.l1_beta, l2_loss=hp.l2_loss, var_w0=hp.var_w0, var_margin0=hp.var_margin0))
-    loss_w = wasserstein_loss(out.float(), cov_out.float(), targets, cov_targets, lam)
+    loss_w = wasserstein_loss(vo._at_least_f32(out), vo._at_least_f32(cov_out), targets, cov_targets, lam)
     loss = loss_cyc + loss_w
     if hp.loss_scale != -1:
         loss = loss * hp.loss_scale

@@ -746,3 +746,317 @@ def test_synth_batch_on_device(L):
     assert torch.equal(img, img2) and torch.equal(mask, mask2)
     ok(L.uvit_op_synth_batch(P(img2), P(mask2), B, 3, S_, Pn, n_mask, 1234, 6, S()))
     assert not torch.equal(img, img2) and not torch.equal(mask, mask2)
+
+
+# ------------------------------------------------------------------------------------------------
+# Production shapes: the sizes of the benchmarked bs=128 step, where the large-size code paths run (slab loops, superchunks,
+# the unrolled streaming loops, batch-wide reductions).  References are float64 on the device; checks are per row, per
+# (sample, head) or per element.
+# ------------------------------------------------------------------------------------------------
+def rows_rel(got, ref):
+    """Per-row L2 error relative to that row's reference norm (2-D views)."""
+    got, ref = got.double().reshape(ref.shape[0], -1), ref.double().reshape(ref.shape[0], -1)
+    return (got - ref).norm(dim=1) / ref.norm(dim=1).clamp_min(1e-30)
+
+
+def arena_numel(L, embed, depth, heads):
+    """(numel, n_decay) of the parameter arena of a base model with this shape (uvit_arena_numel)."""
+    from uncertainty_vit_amd.native import Config
+    cfg = Config(224, 16, 3, embed, depth, heads, 4 * embed, 1, 0, 128, 1e-6, 0.0, 0.0, 0, 0)
+    nd = C.c_int64(0)
+    n = L.uvit_arena_numel(C.byref(cfg), C.byref(nd))
+    return int(n), int(nd.value)
+
+
+@pytest.mark.parametrize("model", ["vitb", "vitl", "odd"])
+def test_sumsq_adamw_ema_at_arena_size(L, model):
+    """The optimizer pass over a whole arena.  stream_grid caps the grid at 2048 x 256 lanes, so the 4-way unrolled main loop of
+    sumsq_kernel runs at these sizes; its 16-iteration fp32 flush runs once n/4 >= 64 strides (the ViT-L arena: 36 iterations,
+    two flushes -- the ViT-B arena, 10 iterations, never reaches it).  `odd`: n/4 not a multiple of 4 strides, the remainder
+    loop after the main loop."""
+    stride = 2048 * 256
+    if model == "odd":
+        n, n_decay = 4 * (16 * 4 * stride + 3 * stride + 12345), 4 * (40 * stride + 7)
+    else:
+        n, n_decay = arena_numel(L, 768, 12, 12) if model == "vitb" else arena_numel(L, 1024, 24, 16)
+    assert n % 4 == 0 and 0 < n_decay < n
+    g = torch.randn(n, generator=torch.Generator(device="cuda").manual_seed(61), device="cuda") * 1e-3
+    ss = torch.zeros(1, dtype=torch.float64, device="cuda")
+    ok(L.uvit_op_sumsq(P(g), n, P(ss), S()))
+    ref = float((g.double() ** 2).sum())
+    print(f"\nn = {n}: sumsq relative error {abs(ss.item() - ref) / ref:.2e}")
+    assert abs(ss.item() - ref) < 1e-6 * ref
+    # AdamW (first two steps, clipped) and the EMA, per element, against torch.optim.AdamW in float64
+    p = torch.randn(n, generator=torch.Generator(device="cuda").manual_seed(60), device="cuda") * 0.02
+    p0 = p.clone()
+    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    pb, gn = torch.zeros(n, dtype=torch.bfloat16, device="cuda"), torch.zeros(1, device="cuda")
+    refd, refn = p0[:n_decay].double().requires_grad_(True), p0[n_decay:].double().requires_grad_(True)
+    opt = torch.optim.AdamW([{"params": [refd], "weight_decay": 0.05}, {"params": [refn], "weight_decay": 0.0}],
+                            lr=2e-3, betas=(0.9, 0.999), eps=1e-8)
+    for step in (1, 2):
+        gg = g * (1.0 if step == 1 else -0.5)
+        refd.grad, refn.grad = gg[:n_decay].double(), gg[n_decay:].double()
+        norm = torch.nn.utils.clip_grad_norm_([refd, refn], 3e-2)       # the norm is ~ 1e-3 sqrt(n) > 3e-2: clipping is on
+        opt.step()
+        ss.zero_()
+        ok(L.uvit_op_sumsq(P(gg), n, P(ss), S()))
+        ok(L.uvit_op_adamw(P(p), P(gg), P(m), P(v), P(pb), n, n_decay, C.c_float(2e-3), C.c_float(0.05), C.c_float(0.9),
+                           C.c_float(0.999), C.c_float(1e-8), step, P(ss), C.c_float(3e-2), C.c_float(1.0), P(gn), S()))
+        assert abs(gn.item() - norm.item()) < 1e-5 * norm.item()
+    refp = torch.cat([refd, refn]).detach()
+    err = (p.double() - refp).abs()
+    worst = int(err.argmax())
+    print(f"AdamW: worst element {worst} off by {float(err[worst]):.2e}")
+    assert float(err.max()) <= 1e-6, (worst, float(err[worst]))        # two steps move a weight by <= 4e-3; fp32 rounding of 2e-2
+    assert torch.equal(pb, p.to(torch.bfloat16))
+    del m, v, pb, refd, refn, opt
+    e = p0.clone()
+    eb = torch.zeros(n, dtype=torch.bfloat16, device="cuda")
+    ok(L.uvit_op_ema(P(e), P(p), P(eb), n, C.c_float(0.9998), S()))
+    err = (e.double() - (0.9998 * p0.double() + (1 - 0.9998) * p.double())).abs()
+    assert float(err.max()) <= 2e-9 + 1e-7 * float(p0.abs().max()), (int(err.argmax()), float(err.max()))
+    assert torch.equal(eb, e.to(torch.bfloat16))
+
+
+def mask_rows_ref(mask, Pn):
+    nz = mask.view(-1).nonzero().view(-1)
+    return ((nz // Pn) * (Pn + 1) + 1 + nz % Pn).to(torch.int32)
+
+
+@pytest.mark.parametrize("B", [128, 168, 256])
+def test_mask_compact_superchunks(L, B):
+    """mask_compact_kernel walks the B*P flags in 32768-element superchunks and carries the running count (`base`) from one to the
+    next: B*P = 25088 (one superchunk), 32928 and 50176 (two).  Exact rowidx and count; the last element set; an all-zero first
+    superchunk (everything then comes from the carry); the unused tail of rowidx is pointed at row 0."""
+    Pn = 196
+    g = torch.Generator().manual_seed(B)
+    cases = {"random": (torch.rand(B, Pn, generator=g) < 0.6).long()}
+    m = torch.zeros(B, Pn, dtype=torch.int64)
+    m.view(-1)[-1] = 1
+    m.view(-1)[32767 % (B * Pn)] = 1
+    cases["last"] = m
+    m = (torch.rand(B, Pn, generator=g) < 0.3).long()
+    m.view(-1)[: min(32768, B * Pn - 5)] = 0
+    cases["zero_superchunk"] = m
+    exact = torch.zeros(B, Pn, dtype=torch.int64)
+    for b in range(B):
+        exact[b, torch.randperm(Pn, generator=g)[:120]] = 1
+    cases["bench"] = exact
+    for name, mk in cases.items():
+        mk = mk.cuda()
+        rowidx = torch.full((B * Pn,), -7, dtype=torch.int32, device="cuda")
+        count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        ok(L.uvit_op_mask_compact(P(mk), P(rowidx), P(count), B, Pn, S()))
+        ref = mask_rows_ref(mk, Pn)
+        assert count.item() == ref.numel(), (name, count.item(), ref.numel())
+        bad = (rowidx[: ref.numel()] != ref).nonzero()
+        assert bad.numel() == 0, (name, "first wrong entry", int(bad[0]))
+        assert torch.all(rowidx[ref.numel():] == 0), name
+
+
+@pytest.mark.parametrize("M,Cd,offset", [(25216, 768, 0.3), (25216 + 7, 768, 0.3), (12608, 1024, 0.3), (25216, 768, 40.0)])
+def test_layernorm_production_rows(L, M, Cd, offset):
+    """ln_fwd / ln_bwd at the token counts of the bs=128 step (M = 128 x 197, the ViT-L bs=64 step at C=1024) and 7 rows past it:
+    the backward gives each 8-wave workgroup a slab of about M / 256 rows and prefetches the next row.  Every row of y and dx
+    against float64; dw and db against float64 column sums.  offset 40: mean offset >> std (std 0.5)."""
+    x = rnd(M, Cd, seed=50) * (0.5 if offset > 1 else 2.0) + offset
+    w, b = rnd(Cd, seed=51) * 0.2 + 1, rnd(Cd, seed=52) * 0.1
+    y = torch.zeros(M, Cd, dtype=torch.bfloat16, device="cuda")
+    mean, rstd = torch.zeros(M, device="cuda"), torch.zeros(M, device="cuda")
+    ok(L.uvit_op_ln_fwd(P(x), P(w), P(b), P(y), P(mean), P(rstd), M, Cd, C.c_float(1e-6), S()))
+    xd = x.double()
+    mu = xd.mean(-1, keepdim=True)
+    var = ((xd - mu) ** 2).mean(-1, keepdim=True)
+    rs = torch.rsqrt(var + 1e-6)
+    xhat = (xd - mu) * rs
+    yref = xhat * w.double() + b.double()
+    r = rows_rel(y, yref)
+    print(f"\nM={M} C={Cd} offset {offset}: ln fwd worst row {int(r.argmax())} {float(r.max()):.2e}")
+    assert float(r.max()) < 5e-3                                           # bf16 output: 2^-9 per element
+    assert float(((mean.double() - mu[:, 0]).abs() * rs[:, 0]).max()) < 1e-4            # in units of the row std
+    assert float(((rstd.double() - rs[:, 0]).abs() / rs[:, 0]).max()) < 1e-4
+    dy = bf(rnd(M, Cd, seed=53)); dres = rnd(M, Cd, seed=54)
+    g = dy.double() * w.double()
+    dxref = dres.double() + rs * (g - g.mean(-1, keepdim=True) - xhat * (g * xhat).mean(-1, keepdim=True))
+    dx = torch.full((M, Cd), 5.0, device="cuda"); dw = torch.zeros(Cd, device="cuda"); db = torch.zeros(Cd, device="cuda")
+    ok(L.uvit_op_ln_bwd(P(dy), P(x), P(mean), P(rstd), P(w), P(dres), P(dx), P(dw), P(db), M, Cd, S()))
+    # dx - dres is the LayerNorm gradient: bound each row's error by that row's LayerNorm-gradient norm
+    r = (dx.double() - dxref).norm(dim=1) / (dxref - dres.double()).norm(dim=1)
+    print(f"ln bwd dx worst row {int(r.argmax())} {float(r.max()):.2e}")
+    assert float(r.max()) < 1e-3 * (1 if offset < 1 else 10), (int(r.argmax()), float(r.max()))
+    dwt, dbt = (dy.double() * xhat), dy.double()
+    for got, terms, name in ((dw, dwt, "dw"), (db, dbt, "db")):
+        err = (got.double() - terms.sum(0)).abs()
+        tol = 1e-5 * terms.abs().sum(0) + 1e-6                              # fp32 accumulation over M terms
+        assert torch.all(err <= tol), (name, int((err / tol).argmax()), float((err / tol).max()))
+
+
+def attn_ref64(qkv, bias, b0, b1, H, N, keep=None):
+    """attn_ref in float64 on samples [b0, b1): out, lse (natural log)."""
+    Bc = b1 - b0
+    q, k, v = qkv.view(-1, N, 3, H, 64)[b0:b1].double().permute(2, 0, 3, 1, 4)
+    s = (q * 0.125) @ k.transpose(-2, -1) + bias
+    a = s.softmax(-1)
+    lse = torch.logsumexp(s, -1)
+    if keep is not None:
+        a = a * keep[b0:b1].double()
+    return (a @ v).transpose(1, 2).reshape(Bc, N, H * 64), lse
+
+
+@pytest.mark.parametrize("B,H", [(128, 12), (64, 16)])
+def test_attention_fwd_bwd_production_batch(L, B, H):
+    """attn_fwd / attn_bwd at the benchmarked batch (ViT-B bs=128) and the ViT-L bs=64 one, with the relative-position bias and
+    p_drop 0.05: out, lse and dqkv relative L2 for EVERY (sample, head), and the bias gradient, which the backward sums over all
+    B samples, against a float64 reference computed 16 samples at a time."""
+    from oracle.vit_oracle import attn_keep_mask
+    N, Cd, p_drop, seed, layer = 197, H * 64, 0.05, 2468, 7
+    qkv = bf(rnd(B * N, 3 * Cd, seed=30))
+    bias = rnd(H, N, N, scale=0.5, seed=31)
+    biasP = padded_bias(bias)
+    keep = attn_keep_mask(seed, layer, B, H, N, p_drop)
+    out = torch.zeros(B * N, Cd, dtype=torch.bfloat16, device="cuda")
+    lse = torch.zeros(B, H, N, device="cuda")
+    ok(L.uvit_op_attn_fwd(P(qkv), P(biasP), P(out), P(lse), B, H, N, 208, C.c_float(0.125), C.c_float(p_drop), seed, layer, S()))
+    d_o = bf(rnd(B * N, Cd, scale=0.5, seed=32))
+    delta = torch.zeros(B, H, N, device="cuda")
+    dqkv = torch.full((B * N, 3 * Cd), 7.0, dtype=torch.bfloat16, device="cuda")
+    ws = torch.empty(L.uvit_op_attn_bwd_ws_bytes(B, H, N), dtype=torch.uint8, device="cuda")
+    slab = torch.zeros(H, 208, 208, device="cuda")
+    ok(L.uvit_op_attn_bwd(P(qkv), P(out), P(d_o), P(biasP), P(lse), P(delta), P(dqkv), P(slab), 0, P(ws), B, H, N, 208,
+                          C.c_float(0.125), C.c_float(p_drop), seed, layer, S()))
+    torch.cuda.synchronize()
+    bq = bias.double().requires_grad_(True)
+    e_out, e_lse, e_dq = [], [], []
+    for b0 in range(0, B, 16):
+        b1 = min(B, b0 + 16)
+        qf = qkv.view(B, N, 3 * Cd)[b0:b1].double().requires_grad_(True)
+        o, l_ = attn_ref64(qf.view(-1, 3 * Cd), bq, 0, b1 - b0, H, N, keep[b0:b1].cuda())
+        o.backward(d_o.view(B, N, Cd)[b0:b1].double())
+        e_out.append(rows_rel(out.view(B, N, H, 64)[b0:b1].permute(0, 2, 1, 3).reshape((b1 - b0) * H, -1),
+                              o.detach().view(-1, N, H, 64).permute(0, 2, 1, 3).reshape((b1 - b0) * H, -1)))
+        e_lse.append((lse[b0:b1].double() - l_.detach() * LOG2E).abs().amax(-1).view(-1))
+        gq = dqkv.view(B, N, 3, H, 64)[b0:b1].permute(0, 2, 3, 1, 4).reshape((b1 - b0) * 3 * H, -1)
+        rq = qf.grad.view(-1, N, 3, H, 64).permute(0, 2, 3, 1, 4).reshape((b1 - b0) * 3 * H, -1)
+        e_dq.append(rows_rel(gq, rq))
+        del qf, o, l_
+    e_out, e_lse, e_dq = torch.cat(e_out), torch.cat(e_lse), torch.cat(e_dq)
+    print(f"\nB={B} H={H}: worst (b, h) out {float(e_out.max()):.2e} at {divmod(int(e_out.argmax()), H)}, lse {float(e_lse.max()):.2e}, "
+          f"dqkv {float(e_dq.max()):.2e} at (b, part, h) {np.unravel_index(int(e_dq.argmax()), (B, 3, H))}")
+    assert float(e_out.max()) < 2e-2, divmod(int(e_out.argmax()), H)
+    assert float(e_lse.max()) < 3e-3 + 1e-3 * float(lse.abs().max())
+    assert float(e_dq.max()) < 2e-2, np.unravel_index(int(e_dq.argmax()), (B, 3, H))
+    dbias = slab[:, :N, :N].transpose(1, 2).double()
+    rel = rows_rel(dbias.reshape(H, -1), bq.grad.reshape(H, -1))
+    print(f"dbias (sum over {B} samples): worst head {int(rel.argmax())} relative L2 {float(rel.max()):.2e}")
+    assert float(rel.max()) < 1e-2
+    assert slab[:, N:, :].abs().sum() == 0 and slab[:, :, N:].abs().sum() == 0
+
+
+@pytest.mark.parametrize("post_ln", [1, 0])
+def test_target_builder_production(L, post_ln):
+    """target_accum / target_finalize for the bs=128 step: 6 layers, 120 of 196 patches masked, C = 768.  Every target row against
+    vo.build_targets in float64."""
+    from oracle import vit_oracle as vo
+    from oracle.closed_form import exact_masks
+    B, Pn, Cd, nl = 128, 196, 768, 6
+    mask = exact_masks(B, Pn, 120, 3).long().cuda()
+    rowidx = torch.zeros(B * Pn, dtype=torch.int32, device="cuda"); count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ok(L.uvit_op_mask_compact(P(mask), P(rowidx), P(count), B, Pn, S()))
+    layers = [rnd(B * (Pn + 1), Cd, seed=82 + i) * (i + 1) + 0.1 * i for i in range(nl)]
+    acc = torch.full((B * Pn, Cd), 3.0, device="cuda")
+    for i, x in enumerate(layers):
+        ok(L.uvit_op_target_accum(P(x), P(rowidx), P(count), P(acc), 1 if i == 0 else 0, B * Pn, Cd, C.c_float(1e-5), S()))
+    ok(L.uvit_op_target_finalize(P(acc), P(count), nl, post_ln, B * Pn, Cd, C.c_float(1e-5), S()))
+    hp = vo.StepHParams(target_layers=tuple(range(nl)), post_target_layer_norm=bool(post_ln))
+    ref = vo.build_targets([x.view(B, Pn + 1, Cd)[:, 1:].double() for x in layers], mask.view(B, 14, 14), hp)
+    assert count.item() == ref.shape[0] == B * 120
+    r = rows_rel(acc[: ref.shape[0]], ref)
+    print(f"\ntargets (post LN {post_ln}): worst row {int(r.argmax())} of {ref.shape[0]}, relative L2 {float(r.max()):.2e}")
+    assert float(r.max()) < 1e-5
+
+
+@pytest.mark.parametrize("beta,l2", [(2.0, 0), (0.12, 0), (1.0, 1)])
+def test_smooth_l1_production(L, beta, l2):
+    """smooth_l1 at the bs=128 step's shape: Mmax = 25088 rows allocated, 15360 masked rows valid, C = 768."""
+    Mmax, Cd, cnt = 25088, 768, 15360
+    out = rnd(Mmax, Cd, seed=70) * 3; tgt = rnd(Mmax, Cd, seed=71)
+    count = torch.tensor([cnt], dtype=torch.int32, device="cuda")
+    loss = torch.zeros(1, device="cuda"); dout = torch.ones(Mmax, Cd, dtype=torch.bfloat16, device="cuda")
+    ok(L.uvit_op_smooth_l1(P(out), P(tgt), P(count), C.c_float(beta), l2, C.c_float(1.0), P(loss), P(dout), Mmax, Cd, S()))
+    o = out[:cnt].double().requires_grad_(True)
+    ref = F.mse_loss(o, tgt[:cnt].double()) if l2 else F.smooth_l1_loss(o, tgt[:cnt].double(), beta=beta)
+    ref.backward()
+    print(f"\nbeta {beta} l2 {l2}: loss relative error {abs(loss.item() - ref.item()) / abs(ref.item()):.2e}")
+    assert abs(loss.item() - ref.item()) < 1e-5 * abs(ref.item()) + 1e-7
+    r = rows_rel(dout[:cnt], o.grad)
+    assert float(r.max()) < 5e-3, (int(r.argmax()), float(r.max()))        # bf16 gradient
+    assert dout[cnt:].abs().sum() == 0
+
+
+@pytest.mark.parametrize("Mmax,cnt,Cd", [(25088, 15360, 768), (300, 257, 128)])
+def test_variance_loss_operator(L, Mmax, cnt, Cd):
+    """uvit_op_variance_loss (engine_for_cyclical.py:130-139): loss, std_loss0 and the gradient it ADDS to dout, against float64
+    autograd of vo.variance_term.  Column scales straddle the margin, so some columns contribute and some do not (zero gradient);
+    rows >= count are padding and stay untouched."""
+    from oracle import vit_oracle as vo
+    w, margin = 2.0, 1.0
+    colscale = torch.linspace(0.2, 2.0, Cd, device="cuda")
+    out = rnd(Mmax, Cd, seed=90) * colscale + rnd(Cd, seed=91)
+    count = torch.tensor([cnt], dtype=torch.int32, device="cuda")
+    scratch = torch.full((2 * Cd + 16,), 9.0, device="cuda")
+    loss, std0 = torch.full((1,), 0.25, device="cuda"), torch.zeros(1, device="cuda")
+    dout = torch.zeros(Mmax, Cd, dtype=torch.bfloat16, device="cuda")
+    dout[cnt:] = 5.0
+    ok(L.uvit_op_variance_loss(P(out), P(count), C.c_float(w), C.c_float(margin), C.c_float(1.0), P(scratch), P(loss), P(std0),
+                               P(dout), Mmax, Cd, S()))
+    o = out[:cnt].double().requires_grad_(True)
+    ref = vo.variance_term(o, vo.StepHParams(var_w0=w, var_margin0=margin))
+    (w * ref).backward()
+    z0 = torch.sqrt(o.detach().var(dim=0) + 1e-6)
+    active = z0 < margin
+    assert 0 < int(active.sum()) < Cd                                   # columns on both sides of the margin
+    print(f"\nvariance term {ref.item():.6f}: kernel {std0.item():.6f}, loss relative error "
+          f"{abs(loss.item() - 0.25 - w * ref.item()) / (w * ref.item()):.2e}")
+    assert std0.item() == pytest.approx(ref.item(), rel=1e-4)
+    assert loss.item() - 0.25 == pytest.approx(w * ref.item(), rel=1e-4)
+    g = dout[:cnt].double()
+    assert torch.all(g[:, ~active] == 0)
+    r = rows_rel(g[:, active], o.grad[:, active])
+    assert float(r.max()) < 1e-2, (int(r.argmax()), float(r.max()))
+    assert torch.all(dout[cnt:] == 5.0)
+
+
+@pytest.mark.parametrize("chunks", [0, 1, 3, 8])
+def test_wgrad_group_production_layer(L, chunks):
+    """The grouped weight-gradient launch for one ViT-B layer of the bs=128 step: qkv (split q / v bias sums), proj, fc1 (bias),
+    fc2 (bias) at M = 25216 reduction rows; chunks 0 = the cost model's choice, the others forced."""
+    from uncertainty_vit_amd.native import WgradProblem
+    Cd, Hd, M = 768, 3072, 25216
+    specs = [(3 * Cd, Cd, "qkv"), (Cd, Cd, "full"), (Hd, Cd, "full"), (Cd, Hd, "full")]
+    probs = (WgradProblem * len(specs))()
+    keep = []
+    for i, (n, k, bias) in enumerate(specs):
+        y, x = bf(rnd(M, n, scale=0.1, seed=30 + i)), bf(rnd(M, k, seed=40 + i))
+        out = torch.full((n, k), 0.5, device="cuda")
+        b1 = torch.zeros(n if bias == "full" else Cd, device="cuda")
+        b2 = torch.zeros(Cd, device="cuda") if bias == "qkv" else None
+        keep.append((y, x, out, b1, b2))
+        q = probs[i]
+        q.Y, q.X, q.C = y.data_ptr(), x.data_ptr(), out.data_ptr()
+        q.bias, q.bias2 = b1.data_ptr(), (b2.data_ptr() if b2 is not None else None)
+        q.bias_end, q.bias2_begin = (n if bias == "full" else Cd), 2 * Cd
+        q.M, q.N, q.K, q.ldy, q.ldx, q.ldc = M, n, k, n, k, k
+    with tuned(wgrad_group_chunks=chunks) as tu:
+        ok(L.uvit_op_wgrad_group(probs, len(specs), C.byref(tu), S()))
+    for (y, x, out, b1, b2), (n, k, bias) in zip(keep, specs):
+        ref = y.double().t() @ x.double() + 0.5
+        close(out, ref, rtol=2e-3, atol=2e-3 * math.sqrt(M / 64), what=f"grouped wgrad {n}x{k}")
+        r = rows_rel(out.double() - 0.5, ref - 0.5)
+        assert float(r.max()) < 1e-3, (n, k, int(r.argmax()), float(r.max()))
+        colsum = y.double().sum(0)
+        if bias == "full":
+            close(b1, colsum, rtol=2e-3, atol=2e-2, what="bias sums")
+        else:
+            close(b1, colsum[:Cd], rtol=2e-3, atol=2e-2, what="q bias sums")
+            close(b2, colsum[2 * Cd:], rtol=2e-3, atol=2e-2, what="v bias sums")
