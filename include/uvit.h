@@ -261,6 +261,14 @@ int64_t uvit_op_attn_bwd_ws_bytes(int B, int H, int N);
 int uvit_op_attn_bwd(const void* qkv, const void* o_fwd, const void* d_o, const float* biasP, const float* lse,
                            float* delta, void* dqkv, float* dbias_slab, int accumulate_slab, void* ds_workspace, int B, int H,
                            int N, int NP, float scale, float p_drop, uint32_t seed, uint32_t layer, uvit_stream stream);
+/* The same two calls with an explicit head_dim: qkv (B,N,3,H,head_dim), out / d_o / o_fwd (B,N,H,head_dim).  head_dim 64 runs the
+ * kernels of uvit_op_attn_fwd / uvit_op_attn_bwd; 80 (ViT-H) runs their head_dim-80 variants; anything else returns
+ * UVIT_ERR_SHAPE.  The workspace size (uvit_op_attn_bwd_ws_bytes) does not depend on head_dim. */
+int uvit_op_attn_fwd_hd(const void* qkv, const float* biasP, void* out, float* lse, int B, int H, int N, int NP, int head_dim,
+                        float scale, float p_drop, uint32_t seed, uint32_t layer, uvit_stream stream);
+int uvit_op_attn_bwd_hd(const void* qkv, const void* o_fwd, const void* d_o, const float* biasP, const float* lse,
+                        float* delta, void* dqkv, float* dbias_slab, int accumulate_slab, void* ds_workspace, int B, int H,
+                        int N, int NP, int head_dim, float scale, float p_drop, uint32_t seed, uint32_t layer, uvit_stream stream);
 /* Two-stream Wasserstein attention core (modeling_finetune_dist.py:129-162 + uncertainty_evaluations.py:276-294).
  * qkv_m: mean-stream (B,N,3,H,64) bf16; qkv_c: covariance stream, already ELU(.)+1.  The backward returns the
  * gradient of the PRE-ELU covariance QKV (ELU' folded in).  biasP / lse units as for uvit_op_attn_fwd. */

@@ -1,4 +1,9 @@
-"""Micro-benchmark of the attention kernels through the C ABI (run on the GPU box)."""
+"""Micro-benchmark of the attention kernels through the C ABI (run on the GPU box).
+
+    python tools/bench_attn.py                          # ViT-B shape: base model (head_dim 64), then the two-stream kernels
+    python tools/bench_attn.py --head-dim 80 --heads 16  # ViT-H/16: the head_dim-80 kernels alone
+"""
+import argparse
 import ctypes as C
 import os
 import sys
@@ -27,27 +32,36 @@ def timeit(fn, iters=20):
 
 
 if __name__ == "__main__":
-    B, H, N, NP = 128, 12, 197, 208
-    Cd = H * 64
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--head-dim", type=int, default=64, choices=[64, 80])
+    ap.add_argument("--heads", type=int, default=12)
+    ap.add_argument("--batch", type=int, default=128)
+    a = ap.parse_args()
+    B, H, N, NP, HD = a.batch, a.heads, 197, 208, a.head_dim
+    Cd = H * HD
+    scale = HD ** -0.5
     qkv = torch.randn(B * N, 3 * Cd, device="cuda").to(torch.bfloat16)
     biasP = torch.zeros(H, NP, NP, device="cuda"); biasP[:, :, N:] = -1e30
     out = torch.zeros(B * N, Cd, device="cuda", dtype=torch.bfloat16)
     d_o = torch.randn(B * N, Cd, device="cuda").to(torch.bfloat16)
     lse = torch.zeros(B, H, N, device="cuda"); delta = torch.zeros_like(lse)
     dqkv = torch.zeros_like(qkv)
-    flops_fwd = 4.0 * B * H * N * N * 64
+    flops_fwd = 4.0 * B * H * N * N * HD
+    print(f"B={B} H={H} N={N} head_dim={HD}")
     for p in (0.0, 0.05):
-        f = lambda: L.uvit_op_attn_fwd(P(qkv), P(biasP), P(out), P(lse), B, H, N, NP, 0.125, p, 1, 0, S())
+        f = lambda: L.uvit_op_attn_fwd_hd(P(qkv), P(biasP), P(out), P(lse), B, H, N, NP, HD, scale, p, 1, 0, S())
         us = timeit(f)
         print(f"fwd  p={p}: {us:7.1f} us  {flops_fwd / us / 1e6:6.1f} TF/s")
         ws = torch.empty(L.uvit_op_attn_bwd_ws_bytes(B, H, N), dtype=torch.uint8, device="cuda")
         slab1 = torch.zeros(H, NP, NP, device="cuda")
         for with_dbias in (True, False):
-            g = lambda: L.uvit_op_attn_bwd(P(qkv), P(out), P(d_o), P(biasP), P(lse), P(delta), P(dqkv), P(slab1 if with_dbias else None), 1,
-                                                 P(ws), B, H, N, NP, 0.125, p, 1, 0, S())
+            g = lambda: L.uvit_op_attn_bwd_hd(P(qkv), P(out), P(d_o), P(biasP), P(lse), P(delta), P(dqkv), P(slab1 if with_dbias else None), 1,
+                                              P(ws), B, H, N, NP, HD, scale, p, 1, 0, S())
             us = timeit(g)
             print(f"bwd  p={p} fused{' + dbias reduce' if with_dbias else '               '}: {us:7.1f} us  {2.5 * flops_fwd / us / 1e6:6.1f} TF/s (5 products)")
 
+    if HD != 64:
+        sys.exit(0)
     # ---- two-stream (Wasserstein) attention: forward, fused backward (+ bias-gradient reduction)
     qkv_m = torch.randn(B * N, 3 * Cd, device="cuda").to(torch.bfloat16)
     qkv_c = (torch.nn.functional.elu(torch.randn(B * N, 3 * Cd, device="cuda")) + 1).to(torch.bfloat16)

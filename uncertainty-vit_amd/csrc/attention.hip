@@ -1,7 +1,7 @@
 // (units) biasP is the relative-position bias times log2(e) with -1e30 in padded key columns; LSE is kept in
 // log2 units -- both are private to these kernels (uvit_relpos_gather_launch builds biasP).
 // Fused multi-head attention with shared relative-position bias and attention dropout for
-// ViT token counts (N <= 208, head_dim 64), gfx950.  Scores never touch HBM.
+// ViT token counts (N <= 208, head_dim 64 or 80), gfx950.  Scores never touch HBM.
 //
 // Reference semantics: modeling_finetune.py:145-188 (Attention.forward) -- softmax(q*scale @ k^T
 // + rel_pos_bias) -> dropout -> @ v.
@@ -16,6 +16,11 @@
 //   fwd     : S^T = K.Q^T  -> softmax over keys -> O^T = V^T.P^T            (+ LSE saved)
 //   bwd     : ONE fused kernel (round 3): S^T, dP^T = V.dO^T -> P, dS -> dQ^T = K^T.dS^T from the accumulators; P, dS cross LDS once
 //             for dV^T = dO^T.P, dK^T = Q^T.dS; dS also leaves as bf16 and attn_dbias_reduce_kernel sums it over the batch
+//
+// head_dim 80 (ViT-H/16): attn_fwd_hd80_kernel and attn_bwd_fused_hd80_kernel, the same algorithms as the head_dim-64 kernels
+// (which they leave untouched).  Dims 0..63 stay in the 128-B swizzled image; dims 64..79 live in a TAIL image of 32-B rows
+// (tail_off).  A contraction over d (S, dP) adds a third v_mfma_f32_16x16x32_bf16 per tile whose k runs over the 16 tail dims and
+// 16 zeros (tail_row); P.V, dV, dK and dQ get a fifth 16-wide d-tile.
 #include <mutex>
 #include "common.h"
 #include "uvit_internal.h"
@@ -57,6 +62,23 @@ __device__ __forceinline__ void dma_rows8(char* img, int rb, const bf16* src, si
 }
 #define IMG_PIECES (ROWS_PAD / 8)          // 28 DMA pieces per image
 
+// head_dim 80: dims 64..79 of a row in a tail image of 32-B rows, four 8-B slots (4 dims each); the two 16-B halves of a row swap
+// when bit 3 of the row is set.  Row reads (8 B, slot g, 16 consecutive rows) and transposed reads (8 consecutive rows x 4 slots
+// per 32-lane half) then each cover the 64 banks once; every address is 8-B aligned, as ds_read_b64_tr_b16 requires.
+#define TAIL_BYTES (ROWS_PAD * 32)         // 7,168 B
+#define TAIL_PIECES (ROWS_PAD / 32)        // 7 DMA pieces per tail image
+__device__ __forceinline__ int tail_off(int row, int slot) { return row * 32 + ((slot ^ ((row >> 2) & 2)) << 3); }
+
+// One 1-KiB LDS-DMA piece of a tail image: rows 32 rb .. 32 rb + 31, dims 64..79.  Lane l writes LDS byte rb * 1024 + 16 l, the
+// 16-B half (l & 1) of row 32 rb + (l >> 1); it reads source half (l & 1) ^ bit 3 of the row (the swizzle on the SOURCE side, as in
+// dma_rows8, whose padded-row rule applies too).
+__device__ __forceinline__ void dma_tail32(char* tail, int rb, const bf16* src, size_t stride, int n_valid, int lane) {
+    const int row = 32 * rb + (lane >> 1);
+    const int half = (lane & 1) ^ ((row >> 3) & 1);
+    const int r = row < n_valid ? row : n_valid - 1;
+    __builtin_amdgcn_global_load_lds(GLB_PTR(void, src + (size_t)r * stride + 64 + half * 8), LDS_PTR(void, tail + rb * 1024), 16, 0, 0);
+}
+
 // After an explicit `s_waitcnt vmcnt(0)`: tell the compiler's wait-count tracking that a prefetched register HAS landed (it inserts
 // its own, by then free, wait in front of this use).  Without it the first real use -- on the far side of a loop back-edge and
 // behind newly issued stores, which the in-order vmcnt cannot skip -- waits for those as well.
@@ -73,6 +95,23 @@ __device__ __forceinline__ bf16x8 col_frag(const char* img, int r_lo, int r_hi, 
     const int ra = r_lo + 4 * g + q, rb = r_hi + 4 * g + q;
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, img + img_off(ra, chunk) + within));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, img + img_off(rb, chunk) + within));
+    typedef __attribute__((ext_vector_type(8))) short s16x8;
+    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, v);
+}
+
+// tail operand of a v_mfma_f32_16x16x32_bf16 whose k runs over the 16 tail dims and 16 zeros: lane (g, i) holds dims
+// 64 + 8 g .. 64 + 8 g + 7 of row `row` for g < 2 and zeros for g >= 2 (a per-lane select: every lane reads a valid 16-B half)
+__device__ __forceinline__ bf16x8 tail_row(const char* tail, int row, int g) {
+    const bf16x8 v = *(const bf16x8*)(tail + row * 32 + (((g & 1) ^ ((row >> 3) & 1)) << 4));
+    const bf16x8 z = {};
+    return g < 2 ? v : z;
+}
+// as col_frag, for the 16 tail dims: element j of lane (g, i) = tail[row (j<4 ? r_lo : r_hi) + 4g + (j&3)][dim 64 + i]
+__device__ __forceinline__ bf16x8 col_frag_tail(const char* tail, int r_lo, int r_hi, int lane) {
+    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, tail + tail_off(r_lo + 4 * g + q, p)));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, tail + tail_off(r_hi + 4 * g + q, p)));
     typedef __attribute__((ext_vector_type(8))) short s16x8;
     const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
@@ -265,6 +304,144 @@ void attn_fwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ bia
     }
 }
 
+// head_dim 80: attn_fwd_kernel with the K / V tail images [224 rows][32 B] behind the two images (71,680 B: two workgroups per CU
+// still fit), a third, K = 16, MFMA per score tile and a fifth output d-tile
+template <int NW, bool HAS_BIAS>
+__global__ __launch_bounds__(NW * 64, 4)
+void attn_fwd_hd80_kernel(const bf16* __restrict__ qkv, const float* __restrict__ biasP, bf16* __restrict__ out,
+                          float* __restrict__ lse, int H, int N, int NP, float scale, uint32_t drop_thr,
+                          float inv_keep, uint32_t drop_key, int ncu, const int* __restrict__ bmap) {
+    constexpr int HDK = 80;
+        constexpr int NDT = HDK / 16;          // output d-tiles
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* kimg = smem;
+    char* vimg = smem + IMG_BYTES;
+    char* ktail = smem + 2 * IMG_BYTES;
+    char* vtail = ktail + TAIL_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, li = lane & 15;
+    const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+    const int C = H * HDK;
+    const size_t ld = 3 * (size_t)C;
+    const bf16* base = qkv + (size_t)b * N * ld + h * HDK;
+    const uint32_t bh_rng = (uint32_t)__builtin_amdgcn_readfirstlane(bmap ? bmap[b] * H + h : bh);
+    // the second workgroup of every CU starts late, as in attn_fwd_kernel
+    if (blockIdx.x >= (unsigned)ncu && blockIdx.x < 2u * (unsigned)ncu) __builtin_amdgcn_s_sleep(127);
+    // K / V images and their tails by LDS-DMA: 56 pieces of 8 rows and 14 tail pieces of 32 rows over the NW waves
+    for (int p = wave; p < 2 * IMG_PIECES; p += NW) {
+        const int img = p / IMG_PIECES, rb = p - img * IMG_PIECES;
+        dma_rows8(smem + img * IMG_BYTES, rb, base + (size_t)(1 + img) * C, ld, N, lane);
+    }
+    {
+        for (int p = wave; p < 2 * TAIL_PIECES; p += NW) {
+            const int img = p / TAIL_PIECES, rb = p - img * TAIL_PIECES;
+            dma_tail32(ktail + img * TAIL_BYTES, rb, base + (size_t)(1 + img) * C, ld, N, lane);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const int nt = (N + 15) >> 4, nt2 = (nt + 1) >> 1;
+
+    for (int qt = wave; qt < nt; qt += NW) {
+        const int q = qt * 16 + li;
+        // this tile's Q fragments (no prefetch of the next tile's: at 80 dims its 10 registers do not fit the budget)
+        const int qr = q < N ? q : N - 1;
+        const bf16x8 qf[2] = {*(const bf16x8*)(base + (size_t)qr * ld + g * 8), *(const bf16x8*)(base + (size_t)qr * ld + 32 + g * 8)};
+        const bf16x8 qt0 = *(const bf16x8*)(base + (size_t)qr * ld + 64 + 8 * (g & 1)), qz = {};
+        const bf16x8 qtf = g < 2 ? qt0 : qz;
+        // scores in log2 units: s' = (q.k) * scale*log2(e) + biasP   (biasP is pre-multiplied by log2(e) and holds
+        // -1e30 in padded key columns, so padded keys vanish in the softmax without per-element selects).
+        // All bias rows of the tile are requested up front, into the registers that will hold the scores.
+        float s[NT_MAX][4];
+#pragma unroll
+        for (int t = 0; t < NT_MAX; ++t) {
+            if constexpr (HAS_BIAS) {
+                if (t < nt) {
+                    const float4 bv = *(const float4*)(biasP + ((size_t)h * NP + q) * NP + t * 16 + 4 * g);
+                    s[t][0] = bv.x; s[t][1] = bv.y; s[t][2] = bv.z; s[t][3] = bv.w;
+                }
+            }
+        }
+        float mx = NEG_BIG;
+        const float c = scale * LOG2E;
+#pragma unroll
+        for (int t = 0; t < NT_MAX; ++t) {
+            if (t < nt) {
+                f32x4 a = {0.f, 0.f, 0.f, 0.f};
+                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(row_frag(kimg, t * 16 + li, g), qf[0], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(row_frag(kimg, t * 16 + li, 4 + g), qf[1], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tail_row(ktail, t * 16 + li, g), qtf, a, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float bb;
+                    if constexpr (HAS_BIAS) bb = s[t][r]; else bb = (t * 16 + 4 * g + r) < N ? 0.f : NEG_BIG;
+                    const float v = a[r] * c + bb;
+                    s[t][r] = v;
+                    mx = fmaxf(mx, v);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s[t][r] = 0.f;
+            }
+        }
+        mx = group_max4(mx);
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT_MAX; ++t) {
+            if (t < nt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float p = __builtin_amdgcn_exp2f(s[t][r] - mx);
+                    s[t][r] = p;
+                    sum += p;
+                }
+            }
+        }
+        sum = group_sum4(sum);
+        if (g == 0 && q < N) lse[(size_t)bh * N + q] = mx + __builtin_amdgcn_logf(sum);      // log2 units
+        f32x4 o[NDT];
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // bh_rng (drop-path sample lists): sample slot b of a COMPACT batch is sample bmap[b] of the step's batch -- the dropout draws are
+        // indexed by the sample, so a compacted launch draws what the dense one does
+        const uint32_t rowpair = (bh_rng * N + q) * (uint32_t)(NP >> 1);
+#pragma unroll
+        for (int ks = 0; ks < (NT_MAX + 1) / 2; ++ks) {
+            if (ks < nt2) {
+                const int t0 = 2 * ks, t1 = 2 * ks + 1;
+                float pa[4], pb[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { pa[r] = s[t0][r]; pb[r] = t1 < NT_MAX ? s[t1 < NT_MAX ? t1 : 0][r] : 0.f; }
+                if (drop_thr) {        // dropout applied while packing P: short live ranges for the hash values
+                    bool k4[4];
+                    keep4(drop_key, rowpair, t0 * 16 + 4 * g, drop_thr, k4);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pa[r] = k4[r] ? pa[r] : 0.f;
+                    keep4(drop_key, rowpair, t1 * 16 + 4 * g, drop_thr, k4);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pb[r] = k4[r] ? pb[r] : 0.f;
+                }
+                const bf16x8 pf = pack8(pa, pb);
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) {
+                    const bf16x8 vf = col_frag(vimg, t0 * 16, t1 * 16, dt * 16, lane);
+                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);
+                }
+                o[4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(col_frag_tail(vtail, t0 * 16, t1 * 16, lane), pf, o[4], 0, 0, 0);
+            }
+        }
+        if (q < N) {
+            const float f = inv_keep / sum;
+            bf16* dst = out + ((size_t)b * N + q) * C + h * HDK + 4 * g;
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                bf16x4 v = {f2bf(o[dt][0] * f), f2bf(o[dt][1] * f), f2bf(o[dt][2] * f), f2bf(o[dt][3] * f)};
+                *(bf16x4*)(dst + dt * 16) = v;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // backward, FUSED (round 3): dQ, dK, dV and dS from ONE recomputation of P.
 //
@@ -321,6 +498,10 @@ extern "C" int uvit_debug_attn_bwd_fused(const void* qkv, const void* o, const v
 #define FB_SB (FB_ROWS * 64)                  // 13,312 B
 #define FB_LDS (4 * FB_IMG + 4 * FB_SB)       // 159,744 B
 #define FB_BWAVES 8                           // waves that run the B phase (one (product, d-tile) each, both key tiles of the step)
+// head_dim 80: 4 images + 4 tail images [224 rows][32 B] (the DMA pieces are 32 rows) = 133,120 + 2,048 B, so the step buffers are
+// SINGLE-buffered (2 x 13 KiB; double buffering would need 186 KiB): a second barrier per step separates the B phase's reads of
+// step i from A_{i+1}'s writes.  10 B-phase jobs (2 products x 5 d-tiles), 3 streaming waves.
+#define FB80_LDS (4 * FB_IMG + 4 * TAIL_BYTES + 2 * FB_SB)   // 161,792 B
 
 __device__ __forceinline__ int sb_off(int q, int slot) {
     const int f = (((q >> 2) & 1) << 2) | (((q >> 3) & 1) << 1) | ((q >> 1) & 1);
@@ -609,6 +790,323 @@ void attn_bwd_fused_kernel(const bf16* __restrict__ qkv, const bf16* __restrict_
     ASTAMP(13);
 }
 
+template <bool HAS_BIAS, int NT_C>
+__global__ __launch_bounds__(FB_WAVES * 64)
+void attn_bwd_fused_hd80_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o_fwd, const bf16* __restrict__ d_o,
+                                const float* __restrict__ biasP, const float* __restrict__ lse, float* __restrict__ delta,
+                                bf16* __restrict__ dqkv, bf16* __restrict__ ds_out, int H, int N, int NP, float scale,
+                                uint32_t drop_thr, float inv_keep, uint32_t drop_key, const int* __restrict__ bmap) {
+    constexpr int HDK = 80;
+        constexpr int BW = 10;                                  // B-phase waves: 2 products x 5 d-tiles
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* const kimg = smem;
+    char* const vimg = smem + FB_IMG;
+    char* const qimg = smem + 2 * FB_IMG;
+    char* const doimg = smem + 3 * FB_IMG;
+    char* const ktail = smem + 4 * FB_IMG;                 // HDK = 80: K, V, Q, dO tails
+    char* const vtail = ktail + TAIL_BYTES;
+    char* const qtail = ktail + 2 * TAIL_BYTES;
+    char* const dotail = ktail + 3 * TAIL_BYTES;
+    char* const pbuf = smem + 4 * FB_IMG + 4 * TAIL_BYTES;   // single-buffered step buffers: P, then dS
+    char* const dbuf = pbuf + FB_SB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, li = lane & 15;
+    const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+    const int C = H * HDK;
+    const size_t ld = 3 * (size_t)C;
+    const int nt = NT_C ? NT_C : (N + 15) >> 4;
+    const int nsteps = (nt + 1) >> 1;
+    const bf16* base = qkv + (size_t)b * N * ld + h * HDK;
+    const bf16* dobase = d_o + (size_t)b * N * C + h * HDK;
+    const bool active = NT_C ? true : wave < nt;
+    const int q = wave * 16 + li, qr = q < N ? q : N - 1;
+
+    // ---- images by LDS-DMA: row blocks of 8; K and V first (rb-interleaved), then Q and dO; blocks beyond the last tile are never read
+    for (int p = wave; p < 4 * (FB_ROWS / 8); p += FB_WAVES) {
+        int img, rb;
+        if (p < 2 * (FB_ROWS / 8)) { img = p & 1; rb = p >> 1; } else { img = 2 + (p >= 3 * (FB_ROWS / 8)); rb = p - img * (FB_ROWS / 8); }
+        if (rb * 8 >= nt * 16) continue;
+        if (img == 3) dma_rows8(doimg, rb, dobase, (size_t)C, N, lane);
+        else dma_rows8(smem + img * FB_IMG, rb, base + (img == 2 ? 0 : (size_t)(1 + img) * C), ld, N, lane);
+    }
+    {
+        for (int p = wave; p < 4 * TAIL_PIECES; p += FB_WAVES) {
+            const int img = p / TAIL_PIECES, rb = p - img * TAIL_PIECES;
+            if (rb * 32 >= nt * 16) continue;
+            if (img == 3) dma_tail32(dotail, rb, dobase, (size_t)C, N, lane);
+            else dma_tail32(ktail + img * TAIL_BYTES, rb, base + (img == 2 ? 0 : (size_t)(1 + img) * C), ld, N, lane);
+        }
+    }
+    // ---- this wave's queries: delta = rowsum(dO o O), LSE  (their Q / dO fragments -- the B operands of S^T and dP^T -- are re-read
+    //      from the images every step: 16 registers the 128-VGPR budget does not have)
+    float dl = 0.f, lse_q = 1e30f;                    // padded query lanes: p = exp2(.. - 1e30) = 0, so they add nothing to dK / dV
+    if (active) {
+        const size_t orow = ((size_t)b * N + qr) * C + h * HDK;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const bf16x8 dof = *(const bf16x8*)(d_o + orow + kk * 32 + g * 8);
+            const bf16x8 of = *(const bf16x8*)(o_fwd + orow + kk * 32 + g * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) dl += bf2f(dof[j]) * bf2f(of[j]);
+        }
+        {
+            const bf16x4 dof = *(const bf16x4*)(d_o + orow + 64 + g * 4);
+            const bf16x4 of = *(const bf16x4*)(o_fwd + orow + 64 + g * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dl += bf2f(dof[j]) * bf2f(of[j]);
+        }
+        dl = group_sum4(dl);
+        if (q < N) {
+            lse_q = lse[(size_t)bh * N + q];
+            if (g == 0) delta[(size_t)bh * N + q] = dl;
+        }
+    }
+    const uint32_t bh_rng = (uint32_t)__builtin_amdgcn_readfirstlane(bmap ? bmap[b] * H + h : bh);     // (compact batch: see the forward)
+    const uint32_t rowpair = (bh_rng * N + q) * (uint32_t)(NP >> 1);
+    const float cs = scale * LOG2E;
+    const float* brow = HAS_BIAS ? biasP + ((size_t)h * NP + (q < NP ? q : NP - 1)) * NP + 4 * g : nullptr;
+    // the bias tiles of a step are requested one step ahead
+    float4 bnext[2];
+    auto bias_fetch = [&](int i) {
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const int t = 2 * i + tt;
+            if constexpr (HAS_BIAS) {
+                bnext[tt] = (t < nt && active) ? *(const float4*)(brow + t * 16) : make_float4(NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG);
+            } else {
+                const int k0 = t * 16 + 4 * g;
+                bnext[tt] = make_float4(k0 < N ? 0.f : NEG_BIG, k0 + 1 < N ? 0.f : NEG_BIG, k0 + 2 < N ? 0.f : NEG_BIG, k0 + 3 < N ? 0.f : NEG_BIG);
+            }
+        }
+    };
+    bias_fetch(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    constexpr int NDT = HDK / 16;
+    f32x4 dq[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // B-phase job of this wave: product pj (0: dV from P and dO, 1: dK from dS and Q), d-tile dtj
+    const int pj = wave / 5, dtj = wave - 5 * pj;
+
+    // ================= A_i: this wave's 16 queries against the 2 key tiles of step i, in two parts: A_compute (S^T, dP^T -> P, dS in
+    // registers) and A_finish (P, dS into the step buffers, dQ^T), with the step's first barrier between them
+    float pdv[2][4], dsv[2][4];
+    auto A_compute = [&](int i) {
+        const int t0 = 2 * i;
+        const bool has1 = t0 + 1 < nt;
+        const float4 bcur[2] = {bnext[0], bnext[1]};
+        if (i + 1 < nsteps) bias_fetch(i + 1);
+        // NO wave-uniform branch may sit between an MFMA and the first VALU read of its result: hipcc's hazard recogniser pads the
+        // MFMA -> VALU wait states along the layout (fall-through) path only, and a taken branch that skips a block lands on the
+        // consumer too early (seen here: accumulator elements 1 and 2 stale after a skipped `if`).  So the dropout draw -- the one
+        // conditional block of the step -- comes BEFORE the MFMAs.
+        bool k4[2][4] = {{true, true, true, true}, {true, true, true, true}};
+#ifndef ATTN_HAZARD_DEMO
+        if (drop_thr) {
+            keep4(drop_key, rowpair, t0 * 16 + 4 * g, drop_thr, k4[0]);
+            keep4(drop_key, rowpair, t0 * 16 + 16 + 4 * g, drop_thr, k4[1]);
+        }
+#endif
+        // Staged so that at most 16 operand registers are live: K rows -> S^T, V rows -> dP^T, softmax backward, K^T columns -> dQ^T.
+        // (With every read of the step hoisted to the top the kernel spills ~55 registers at the 128-VGPR budget of 13 waves.)
+        const int row0 = t0 * 16 + li, row1 = (has1 ? t0 + 1 : t0) * 16 + li;   // no second tile: re-read the first (its p is 0)
+        f32x4 sacc[2], dp[2];
+        {
+            const bf16x8 k00 = row_frag(kimg, row0, g), k01 = row_frag(kimg, row0, 4 + g);
+            const bf16x8 k10 = row_frag(kimg, row1, g), k11 = row_frag(kimg, row1, 4 + g);
+            const bf16x8 qf0 = row_frag(qimg, q, g), qf1 = row_frag(qimg, q, 4 + g);      // B operand: this lane's query row
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            sacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k00, qf0, z, 0, 0, 0);
+            sacc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k10, qf0, z, 0, 0, 0);
+            sacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k01, qf1, sacc[0], 0, 0, 0);
+            sacc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k11, qf1, sacc[1], 0, 0, 0);
+            {
+                const bf16x8 qt = tail_row(qtail, q, g);
+                sacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tail_row(ktail, row0, g), qt, sacc[0], 0, 0, 0);
+                sacc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tail_row(ktail, row1, g), qt, sacc[1], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            const bf16x8 v00 = row_frag(vimg, row0, g), v01 = row_frag(vimg, row0, 4 + g);
+            const bf16x8 v10 = row_frag(vimg, row1, g), v11 = row_frag(vimg, row1, 4 + g);
+            const bf16x8 do0 = row_frag(doimg, q, g), do1 = row_frag(doimg, q, 4 + g);
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            dp[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v00, do0, z, 0, 0, 0);
+            dp[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v10, do0, z, 0, 0, 0);
+            dp[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v01, do1, dp[0], 0, 0, 0);
+            dp[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v11, do1, dp[1], 0, 0, 0);
+            {
+                const bf16x8 dot = tail_row(dotail, q, g);
+                dp[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tail_row(vtail, row0, g), dot, dp[0], 0, 0, 0);
+                dp[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tail_row(vtail, row1, g), dot, dp[1], 0, 0, 0);
+            }
+        }
+#ifdef ATTN_HAZARD_DEMO      // the round-3 bug, kept as the build-time guard's test case (tools/check_mfma_hazard.py): a skipped `if` right after the MFMAs
+        if (drop_thr) {
+            keep4(drop_key, rowpair, t0 * 16 + 4 * g, drop_thr, k4[0]);
+            keep4(drop_key, rowpair, t0 * 16 + 16 + 4 * g, drop_thr, k4[1]);
+        }
+#endif
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const float bb[4] = {bcur[tt].x, bcur[tt].y, bcur[tt].z, bcur[tt].w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                // no second tile: its bias is -1e30, so p = 0 and the tile adds nothing
+                const float p = __builtin_amdgcn_exp2f(sacc[tt][r] * cs + bb[r] - lse_q);
+                const float pd = k4[tt][r] ? p * inv_keep : 0.f;
+                pdv[tt][r] = pd;
+                dsv[tt][r] = pd * dp[tt][r] - p * dl;
+            }
+        }
+    };
+    auto A_finish = [&](int i) {
+        char* pb = pbuf;
+        char* db = dbuf;
+        const int t0 = 2 * i;
+        const bool has1 = t0 + 1 < nt;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            if (tt == 0 || has1) {
+                const bf16x4 pv = {f2bf(pdv[tt][0]), f2bf(pdv[tt][1]), f2bf(pdv[tt][2]), f2bf(pdv[tt][3])};
+                const bf16x4 dv = {f2bf(dsv[tt][0]), f2bf(dsv[tt][1]), f2bf(dsv[tt][2]), f2bf(dsv[tt][3])};
+                *(bf16x4*)(pb + sb_off(q, 4 * tt + g)) = pv;
+                *(bf16x4*)(db + sb_off(q, 4 * tt + g)) = dv;
+            }
+        }
+        const bf16x8 dsf = pack8(dsv[0], dsv[1]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const bf16x8 kt = col_frag(kimg, t0 * 16, has1 ? t0 * 16 + 16 : t0 * 16, dt * 16, lane);
+            dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt, dsf, dq[dt], 0, 0, 0);
+        }
+        dq[4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(col_frag_tail(ktail, t0 * 16, has1 ? t0 * 16 + 16 : t0 * 16, lane),
+                                                                             dsf, dq[4], 0, 0, 0);
+    };
+
+    // ================= B_i (waves 0..BW-1): d{V,K}^T of the step's 32 keys, contracted over every query
+    auto B_step = [&](int i) {
+        const char* sb = pj ? dbuf : pbuf;
+        const char* img = pj ? qimg : doimg;
+        const char* timg = pj ? qtail : dotail;
+        const bool has1 = 2 * i + 1 < nt;
+        f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+        // both key tiles always (a step without a second tile multiplies stale but finite slots; the result is dropped): no
+        // branch between the MFMAs and the conversion of their results (see A_compute)
+        auto kstep = [&](int ks, auto is_tail) {
+            const bool hk = 2 * ks + 1 < nt;
+            const int r_lo = 32 * ks, r_hi = hk ? r_lo + 16 : r_lo;
+            bf16x8 a;
+            if constexpr (decltype(is_tail)::value) a = col_frag_tail(timg, r_lo, r_hi, lane);
+            else a = col_frag(img, r_lo, r_hi, dtj * 16, lane);
+            const bf16x8 b0 = sb_col_frag(sb, r_lo, r_hi, 0, hk, lane);
+            const bf16x8 b1 = sb_col_frag(sb, r_lo, r_hi, 1, hk, lane);
+            acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b0, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b1, acc[1], 0, 0, 0);
+        };
+        auto kloop = [&](auto is_tail) {
+            if constexpr (NT_C != 0) {
+#pragma unroll
+                for (int ks = 0; ks < (NT_C + 1) / 2; ++ks) kstep(ks, is_tail);
+            } else {
+                for (int ks = 0; ks < nsteps; ++ks) kstep(ks, is_tail);
+            }
+        };
+        if (dtj == 4) kloop(std::true_type{});      // wave-uniform: the d-tile of the tail image
+        else kloop(std::false_type{});
+        HAZARD_PAD();     // the loop exit is a branch: pad the MFMA -> VALU wait states by hand
+        // acc[tt][r] = d{V,K}[key 32 i + 16 tt + li][d = 16 dtj + 4 g + r]  ->  the dead rows of the V / K image (or tail image)
+        char* dst = pj ? kimg : vimg;
+        char* tdst = pj ? ktail : vtail;
+        const float sc = pj ? scale : 1.0f;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            if (tt == 0 || has1) {
+                const int row = 32 * i + 16 * tt + li;
+                const bf16x4 v = {f2bf(acc[tt][0] * sc), f2bf(acc[tt][1] * sc), f2bf(acc[tt][2] * sc), f2bf(acc[tt][3] * sc)};
+                if (dtj == 4) *(bf16x4*)(tdst + tail_off(row, g)) = v;
+                else *(bf16x4*)(dst + img_off(row, 2 * dtj + (g >> 1)) + ((g & 1) << 3)) = v;
+            }
+        }
+    };
+    // rows 32 i .. 32 i + 31 of the K / V images hold dK / dV of step i once B_i is done: 8 pieces of 8 rows, as full 128-B rows
+    // (HDK = 80: pieces 8, 9 are the 32 rows of the K / V tail image, 32 B per row)
+    auto store_rows = [&](int i, int sw) {
+        for (int c = sw; c < 10; c += FB_WAVES - BW) {
+            if (c >= 8) {
+                const int img = c - 8, row = 32 * i + (lane >> 1), hl = lane & 1;
+                if (row < N) {
+                    const uint4 v = *(const uint4*)(ktail + img * TAIL_BYTES + row * 32 + hl * 16);
+                    *(uint4*)(dqkv + ((size_t)b * N + row) * ld + (size_t)(1 + img) * C + h * HDK + 64 + 8 * (hl ^ ((row >> 3) & 1))) = v;
+                }
+                continue;
+            }
+            const int img = c >> 2, row = 32 * i + 8 * (c & 3) + (lane >> 3), ch = lane & 7;
+            if (row < N) {
+                const uint4 v = *(const uint4*)(smem + img * FB_IMG + img_off(row, ch));
+                *(uint4*)(dqkv + ((size_t)b * N + row) * ld + (size_t)(1 + img) * C + h * HDK + ch * 8) = v;
+            }
+        }
+    };
+    // the dS step buffer as it stands (attn_dbias_reduce_kernel undoes the slot swizzle): 1-KiB pieces of 16 rows
+    auto stream_ds = [&](int i, int sw) {
+        if (!ds_out) return;
+        const char* db = dbuf;
+        char* dst = (char*)(ds_out + ((size_t)bh * nsteps + i) * (FB_SB / 2));
+        for (int j = sw; j < nt; j += FB_WAVES - BW) {
+            const uint4 v = *(const uint4*)(db + j * 1024 + lane * 16);
+            *(uint4*)(dst + j * 1024 + lane * 16) = v;
+        }
+    };
+
+    // iteration i: B_{i-1} (or the streaming of step i-1 / i-2) and A_compute(i), which does not touch the step buffers; barrier;
+    // A_finish(i) overwrites them; barrier
+#pragma unroll 1
+    for (int i = 0; i <= nsteps; ++i) {
+        if (wave < BW) {
+            if (i > 0) B_step(i - 1);
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            const int sw = wave - BW;
+            if (i > 1) store_rows(i - 2, sw);
+            if (i > 0) stream_ds(i - 1, sw);
+        }
+        if (i < nsteps && active) A_compute(i);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (i < nsteps && active) A_finish(i);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    }
+    if (wave >= BW) store_rows(nsteps - 1, wave - BW);
+    if (active) {
+        // dq[dt][r] = dQ[q = li][d = 16 dt + 4 g + r]: through this wave's own 16 rows of the Q image, then 16 B per lane
+        // (the tail d-tile straight from the registers, 8 B per lane)
+        {
+            const bf16x4 v = {f2bf(dq[4][0] * scale), f2bf(dq[4][1] * scale), f2bf(dq[4][2] * scale), f2bf(dq[4][3] * scale)};
+            if (q < N) *(bf16x4*)(dqkv + ((size_t)b * N + q) * ld + h * HDK + 64 + 4 * g) = v;
+        }
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const bf16x4 v = {f2bf(dq[dt][0] * scale), f2bf(dq[dt][1] * scale), f2bf(dq[dt][2] * scale), f2bf(dq[dt][3] * scale)};
+            *(bf16x4*)(qimg + img_off(q, 2 * dt + (g >> 1)) + ((g & 1) << 3)) = v;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int row = wave * 16 + (lane >> 3) + 8 * k, ch = lane & 7;
+            const uint4 v = *(const uint4*)(qimg + img_off(row, ch));
+            if (row < N) *(uint4*)(dqkv + ((size_t)b * N + row) * ld + h * HDK + ch * 8) = v;
+        }
+    }
+}
+
 // Bias gradient from the dS the fused kernel streamed out: slab[h][key][q] += sum_b dS_b[h][q][key]  (slab zeroed by the launcher
 // unless it accumulates).  ds = [B * H][nsteps][208 rows x 64 B] bf16 step-buffer images (slot swizzle of sb_off).
 // One 256-thread workgroup per (head, step, 64 queries, batch part): thread (q, 16-B chunk) streams its chunk of every sample of the
@@ -655,6 +1153,7 @@ void attn_dbias_reduce_kernel(const bf16* __restrict__ ds, float* __restrict__ s
 // host launchers
 // ------------------------------------------------------------------------------------------
 #define FWD_WAVES 7
+#define FWD80_LDS (2 * IMG_BYTES + 2 * TAIL_BYTES)     // 71,680 B: two workgroups per CU still fit
 static std::once_flag g_attn_once;
 static int g_attn_ncu = 256;
 static void attn_init_impl() {
@@ -667,20 +1166,34 @@ static void attn_init_impl() {
     (void)hipFuncSetAttribute((const void*)attn_bwd_fused_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     (void)hipFuncSetAttribute((const void*)attn_bwd_fused_kernel<true, NT_MAX>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
     (void)hipFuncSetAttribute((const void*)attn_bwd_fused_kernel<false, NT_MAX>, hipFuncAttributeMaxDynamicSharedMemorySize, FB_LDS);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_hd80_kernel<FWD_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FWD80_LDS);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_hd80_kernel<FWD_WAVES, false>, hipFuncAttributeMaxDynamicSharedMemorySize, FWD80_LDS);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_fused_hd80_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, FB80_LDS);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_fused_hd80_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, FB80_LDS);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_fused_hd80_kernel<true, NT_MAX>, hipFuncAttributeMaxDynamicSharedMemorySize, FB80_LDS);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_fused_hd80_kernel<false, NT_MAX>, hipFuncAttributeMaxDynamicSharedMemorySize, FB80_LDS);
 }
 static void attn_init_once() { std::call_once(g_attn_once, attn_init_impl); }
 
 static int attn_check(int B, int H, int N, int head_dim) {
-    if (head_dim != HD || B <= 0 || H <= 0 || N <= 0 || N > NT_MAX * 16) return UVIT_ERR_SHAPE;
+    if ((head_dim != 64 && head_dim != 80) || B <= 0 || H <= 0 || N <= 0 || N > NT_MAX * 16) return UVIT_ERR_SHAPE;
     return UVIT_OK;
 }
 
 int uvit_attn_fwd_launch(const void* qkv, const float* biasP, void* out, float* lse, int B, int H, int N, int NP,
-                         float scale, float p_drop, uint32_t seed, uint32_t layer, hipStream_t s, const int* bmap) {
-    int rc = attn_check(B, H, N, HD); if (rc) return rc;
+                         float scale, float p_drop, uint32_t seed, uint32_t layer, hipStream_t s, const int* bmap, int head_dim) {
+    int rc = attn_check(B, H, N, head_dim); if (rc) return rc;
     attn_init_once();
     const uint32_t thr = p_drop > 0.f ? uvit_drop_threshold16(p_drop) : 0u;
     const float inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
+    if (head_dim == 80) {
+#define F80_ARGS dim3(B * H), dim3(FWD_WAVES * 64), FWD80_LDS, s, (const bf16*)qkv, biasP, (bf16*)out, lse, H, N, NP, scale, thr, inv_keep, \
+        uvit_layer_key(seed, layer), g_attn_ncu, bmap
+        if (biasP) hipLaunchKernelGGL((attn_fwd_hd80_kernel<FWD_WAVES, true>), F80_ARGS);
+        else hipLaunchKernelGGL((attn_fwd_hd80_kernel<FWD_WAVES, false>), F80_ARGS);
+#undef F80_ARGS
+        return uvit_check_launch();
+    }
     if (biasP) hipLaunchKernelGGL((attn_fwd_kernel<FWD_WAVES, true>), dim3(B * H), dim3(FWD_WAVES * 64), 2 * IMG_BYTES, s, (const bf16*)qkv,
                                   biasP, (bf16*)out, lse, H, N, NP, scale, thr, inv_keep, uvit_layer_key(seed, layer), g_attn_ncu, bmap);
     else hipLaunchKernelGGL((attn_fwd_kernel<FWD_WAVES, false>), dim3(B * H), dim3(FWD_WAVES * 64), 2 * IMG_BYTES, s, (const bf16*)qkv,
@@ -696,8 +1209,8 @@ size_t uvit_attn_bwd_fused_ws_bytes(int B, int H, int N) {
 // ds_ws: bf16 workspace of uvit_attn_bwd_fused_ws_bytes(B, H, N) bytes, written when want_ds != 0 (the bias gradient needs it)
 int uvit_attn_bwd_fused_launch(const void* qkv, const void* o_fwd, const void* d_o, const float* biasP, const float* lse,
                                float* delta, void* dqkv, void* ds_ws, int want_ds, int B, int H, int N, int NP, float scale,
-                               float p_drop, uint32_t seed, uint32_t layer, hipStream_t s, const int* bmap) {
-    int rc = attn_check(B, H, N, HD); if (rc) return rc;
+                               float p_drop, uint32_t seed, uint32_t layer, hipStream_t s, const int* bmap, int head_dim) {
+    int rc = attn_check(B, H, N, head_dim); if (rc) return rc;
     if (NP < NT_MAX * 16 || (want_ds && !ds_ws)) return UVIT_ERR_ARG;
     attn_init_once();
     const uint32_t thr = p_drop > 0.f ? uvit_drop_threshold16(p_drop) : 0u;
@@ -706,7 +1219,16 @@ int uvit_attn_bwd_fused_launch(const void* qkv, const void* o_fwd, const void* d
     bf16* dsw = want_ds ? (bf16*)ds_ws : nullptr;
 #define FB_ARGS dim3(B * H), dim3(FB_WAVES * 64), FB_LDS, s, (const bf16*)qkv, (const bf16*)o_fwd, (const bf16*)d_o, biasP, lse, delta, \
         (bf16*)dqkv, dsw, H, N, NP, scale, thr, inv_keep, key, bmap
-    if ((N + 15) / 16 == NT_MAX) {
+    if (head_dim == 80) {
+#define FB80_ARGS dim3(B * H), dim3(FB_WAVES * 64), FB80_LDS, s, (const bf16*)qkv, (const bf16*)o_fwd, (const bf16*)d_o, biasP, lse, delta, \
+        (bf16*)dqkv, dsw, H, N, NP, scale, thr, inv_keep, key, bmap
+        if ((N + 15) / 16 == NT_MAX) {
+            if (biasP) hipLaunchKernelGGL((attn_bwd_fused_hd80_kernel<true, NT_MAX>), FB80_ARGS); else hipLaunchKernelGGL((attn_bwd_fused_hd80_kernel<false, NT_MAX>), FB80_ARGS);
+        } else {
+            if (biasP) hipLaunchKernelGGL((attn_bwd_fused_hd80_kernel<true, 0>), FB80_ARGS); else hipLaunchKernelGGL((attn_bwd_fused_hd80_kernel<false, 0>), FB80_ARGS);
+        }
+#undef FB80_ARGS
+    } else if ((N + 15) / 16 == NT_MAX) {
         if (biasP) hipLaunchKernelGGL((attn_bwd_fused_kernel<true, NT_MAX>), FB_ARGS); else hipLaunchKernelGGL((attn_bwd_fused_kernel<false, NT_MAX>), FB_ARGS);
     } else {
         if (biasP) hipLaunchKernelGGL((attn_bwd_fused_kernel<true, 0>), FB_ARGS); else hipLaunchKernelGGL((attn_bwd_fused_kernel<false, 0>), FB_ARGS);

@@ -39,7 +39,9 @@ static size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 
 static int cfg_ok(const uvit_config* c) {
     if (!c) return UVIT_ERR_ARG;
-    if (c->depth < 1 || c->depth > UVIT_MAX_DEPTH || c->num_heads < 1 || c->embed_dim != c->num_heads * 64) return UVIT_ERR_SHAPE;
+    if (c->depth < 1 || c->depth > UVIT_MAX_DEPTH || c->num_heads < 1) return UVIT_ERR_SHAPE;
+    // head_dim 64 (ViT-B/L) or, base model only, 80 (ViT-H): attention2.hip (two-stream) is specialised for 64
+    if (c->embed_dim != c->num_heads * 64 && (c->two_stream || c->embed_dim != c->num_heads * 80)) return UVIT_ERR_SHAPE;
     if (c->embed_dim % 64 || c->mlp_hidden % 64 || c->patch_size % 8 || c->img_size % c->patch_size) return UVIT_ERR_SHAPE;
     if ((c->in_chans * c->patch_size * c->patch_size) % 64) return UVIT_ERR_SHAPE;
     const int g = c->img_size / c->patch_size;
@@ -135,7 +137,9 @@ struct uvit_engine {
     uvit_config cfg;
     uvit_buffers buf;
     Layout lo;
-    int B, P, N, NP, C, Hd, H, Kpe, M, Mpad, BP, BPpad, chunk, nchunk;
+    int B, P, N, NP, C, Hd, H, Kpe, M, Mpad, BP, BPpad, chunk, nchunk;     // (Hd: the MLP hidden size)
+    int head_dim;          // C / H: 64 or 80
+    float attn_scale;      // head_dim ** -0.5 (0.125f for 64)
     int S;                 // streams: 1 or 2
     GemmTune tune;         // launch tuning of this engine's GEMMs (uvit_engine_set_tuning)
     int cur_B;             // batch of the last forward
@@ -265,6 +269,8 @@ static void fill_dims(uvit_engine* e) {
     const int g = c.img_size / c.patch_size;
     e->B = c.batch; e->P = g * g; e->N = e->P + 1; e->NP = 208; e->C = c.embed_dim; e->Hd = c.mlp_hidden;
     e->H = c.num_heads; e->Kpe = c.in_chans * c.patch_size * c.patch_size;
+    e->head_dim = c.embed_dim / c.num_heads;
+    e->attn_scale = e->head_dim == 64 ? 0.125f : (float)(1.0 / std::sqrt((double)e->head_dim));
     e->S = c.two_stream ? 2 : 1;
     e->M = e->B * e->N; e->Mpad = (int)roundup(e->M, 128); e->BP = e->B * e->P; e->BPpad = (int)roundup(e->BP, 128);
     if (c.bias_chunk > 0) {
@@ -644,7 +650,8 @@ static int forward_layer(uvit_engine* e, const Weights& w, int l, const float* x
         CHECK(GEMM_NT(st ? EPI_QKV_ELU : EPI_QKV, a.ln1 + at.off[st] * C, w.b + o.qkvw, at.n[st], 3 * C, C, C, C, &q, s));
     }
     if (S == 1) {
-        CHECK(uvit_attn_fwd_launch(a.qkv, biasP, a.attn, a.lse, at.K, e->H, e->N, e->NP, 0.125f, pdrop, seed, (uint32_t)l, s, at.d[0].bmap));
+        CHECK(uvit_attn_fwd_launch(a.qkv, biasP, a.attn, a.lse, at.K, e->H, e->N, e->NP, e->attn_scale, pdrop, seed, (uint32_t)l, s, at.d[0].bmap,
+                                   e->head_dim));
     } else {
         CHECK(uvit_attn2_fwd_launch(a.qkv, a.qkv + Mp * 3 * C, biasP, a.attn, a.attn + Mp * C, a.lse, Bc, e->H, e->N, e->NP, 0.125f,
                                     pdrop, seed, (uint32_t)l, s));
@@ -1038,7 +1045,7 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
             if (at.mode == ROWS_LIST && ml.mode == ROWS_MASKED && at.red > at.rows)
                 CHECK(uvit_zero_launch(dqkv + (size_t)at.rows * 3 * C, (size_t)(at.red - at.rows) * 3 * C * sizeof(bf16), s));
             CHECK(uvit_attn_bwd_fused_launch(a.qkv, a.attn, e->dAttn, biasP, a.lse, e->delta, dqkv, dsw, dsw != nullptr, at.K, e->H,
-                                             e->N, e->NP, 0.125f, pdrop, e->last_seed, (uint32_t)l, s, at.d[0].bmap));
+                                             e->N, e->NP, e->attn_scale, pdrop, e->last_seed, (uint32_t)l, s, at.d[0].bmap, e->head_dim));
         } else {
             CHECK(uvit_attn2_bwd_launch(a.qkv, a.qkv + Mp * 3 * C, a.attn, a.attn + Mp * C, e->dAttn, e->dAttn + Mp * C, biasP, a.lse,
                                         e->delta, dqkv, dqkv + Mp * 3 * C, dsw, dsw != nullptr, e->B, e->H, e->N, e->NP, 0.125f, pdrop,
@@ -1237,6 +1244,22 @@ extern "C" int uvit_op_attn_bwd(const void* qkv, const void* o_fwd, const void* 
                                       float scale, float p_drop, uint32_t seed, uint32_t layer, uvit_stream st) {
     if (!qkv || !o_fwd || !d_o || !lse || !delta || !dqkv || (slab && !ds_ws)) return UVIT_ERR_ARG;
     CHECK(uvit_attn_bwd_fused_launch(qkv, o_fwd, d_o, biasP, lse, delta, dqkv, ds_ws, slab != nullptr, B, H, N, NP, scale, p_drop, seed, layer, S(st)));
+    if (slab) CHECK(uvit_attn_dbias_reduce_launch(ds_ws, slab, acc, B, H, N, NP, S(st)));
+    return UVIT_OK;
+}
+extern "C" int uvit_op_attn_fwd_hd(const void* qkv, const float* biasP, void* out, float* lse, int B, int H, int N, int NP, int head_dim,
+                                   float scale, float p_drop, uint32_t seed, uint32_t layer, uvit_stream st) {
+    if (!qkv || !out || !lse) return UVIT_ERR_ARG;
+    if (head_dim != 64 && head_dim != 80) return UVIT_ERR_SHAPE;
+    return uvit_attn_fwd_launch(qkv, biasP, out, lse, B, H, N, NP, scale, p_drop, seed, layer, S(st), nullptr, head_dim);
+}
+extern "C" int uvit_op_attn_bwd_hd(const void* qkv, const void* o_fwd, const void* d_o, const float* biasP, const float* lse,
+                                   float* delta, void* dqkv, float* slab, int acc, void* ds_ws, int B, int H, int N, int NP, int head_dim,
+                                   float scale, float p_drop, uint32_t seed, uint32_t layer, uvit_stream st) {
+    if (!qkv || !o_fwd || !d_o || !lse || !delta || !dqkv || (slab && !ds_ws)) return UVIT_ERR_ARG;
+    if (head_dim != 64 && head_dim != 80) return UVIT_ERR_SHAPE;
+    CHECK(uvit_attn_bwd_fused_launch(qkv, o_fwd, d_o, biasP, lse, delta, dqkv, ds_ws, slab != nullptr, B, H, N, NP, scale, p_drop, seed, layer,
+                                     S(st), nullptr, head_dim));
     if (slab) CHECK(uvit_attn_dbias_reduce_launch(ds_ws, slab, acc, B, H, N, NP, S(st)));
     return UVIT_OK;
 }

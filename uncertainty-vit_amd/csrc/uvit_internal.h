@@ -74,14 +74,16 @@ int uvit_gemm_tn_group_launch(const TnProb* probs, int n, hipStream_t s, const G
 // attention.hip
 // bmap != nullptr: the launch runs a COMPACT batch (drop-path sample list); sample slot b draws the dropout of sample bmap[b]
 int uvit_attn_fwd_launch(const void* qkv, const float* biasP, void* out, float* lse, int B, int H, int N, int NP,
-                         float scale, float p_drop, uint32_t seed, uint32_t layer, hipStream_t s, const int* bmap = nullptr);
+                         float scale, float p_drop, uint32_t seed, uint32_t layer, hipStream_t s, const int* bmap = nullptr,
+                         int head_dim = 64);     // head_dim: 64 or 80 (qkv (B, N, 3, H, head_dim))
 // fused backward (one recomputation of P; dS leaves as bf16 for the bias gradient): ds_ws holds uvit_attn_bwd_fused_ws_bytes()
 // bytes and is written when want_ds != 0; uvit_attn_dbias_reduce_launch sums it over the batch into ONE [H][NP][NP] slab laid out
 // [h][key][q] (accumulate = 0: the slab is zero-filled first).  Two launches so that the reduction can run on another stream.
 size_t uvit_attn_bwd_fused_ws_bytes(int B, int H, int N);
 int uvit_attn_bwd_fused_launch(const void* qkv, const void* o_fwd, const void* d_o, const float* biasP, const float* lse,
                                float* delta, void* dqkv, void* ds_ws, int want_ds, int B, int H, int N, int NP, float scale,
-                               float p_drop, uint32_t seed, uint32_t layer, hipStream_t s, const int* bmap = nullptr);
+                               float p_drop, uint32_t seed, uint32_t layer, hipStream_t s, const int* bmap = nullptr,
+                               int head_dim = 64);
 int uvit_attn_dbias_reduce_launch(const void* ds_ws, float* dbias_slab, int accumulate, int B, int H, int N, int NP, hipStream_t s);
 
 // attention2.hip (two-stream Wasserstein attention)

@@ -22,7 +22,8 @@ import torch.nn as nn
 from . import native
 from .native import Buffers, Config, LayoutEntry, check, cur_stream, lib, ptr
 
-__all__ = ["beit_base_patch16_224", "dist_beit_base_patch16_224", "beit_large_patch16_224", "dist_beit_large_patch16_224", "create_model", "register_model",
+__all__ = ["beit_base_patch16_224", "dist_beit_base_patch16_224", "beit_large_patch16_224", "dist_beit_large_patch16_224",
+           "beit_huge_patch16_224", "create_model", "register_model",
            "VisionTransformerForCyclicalTraining", "DistVisionTransformerForCyclicalTraining"]
 
 
@@ -170,8 +171,11 @@ class VisionTransformerForCyclicalTraining(nn.Module):
         if init_values is None or not init_values > 0:
             # modeling_finetune.py:284 `if init_values > 0` -- None raises TypeError there too
             raise TypeError("init_values must be > 0 (LayerScale is part of the configured path)")
-        if embed_dim != num_heads * 64:
-            raise NotImplementedError("attention kernels are specialised for head_dim 64 (ViT-B/L/H)")
+        head_dims = (64,) if self._two_stream else (64, 80)
+        if embed_dim not in [num_heads * d for d in head_dims]:
+            raise NotImplementedError(
+                f"attention kernels support head_dim {' or '.join(map(str, head_dims))} for this model "
+                f"(ViT-B/L: 64, ViT-H: 80); got embed_dim {embed_dim} / num_heads {num_heads}")
         self.num_features = self.embed_dim = embed_dim
         self.depth, self.num_heads, self.mlp_hidden = depth, num_heads, int(embed_dim * mlp_ratio)
         self.img_size, self.in_chans = img_size, in_chans
@@ -485,3 +489,10 @@ def beit_large_patch16_224(pretrained=False, **kwargs):
     """modeling_cyclical.py:326-343 (the reference entry point is broken under create_model, SURVEY F9;
     this one accepts the same kwargs as the base entry point)."""
     return _build(pretrained, kwargs, embed_dim=1024, depth=24, num_heads=16)
+
+
+@register_model
+def beit_huge_patch16_224(pretrained=False, **kwargs):
+    """modeling_cyclical.py:346-363: embed 1280, depth 32, 16 heads (head_dim 80).  Like beit_large_patch16_224 it accepts the
+    base entry point's kwargs (the reference entry point is broken under create_model)."""
+    return _build(pretrained, kwargs, embed_dim=1280, depth=32, num_heads=16)
