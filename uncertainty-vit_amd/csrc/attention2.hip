@@ -17,58 +17,14 @@
 //   bwd : ONE fused kernel (round 4): query-side images Am, Ac, dMean, dCov whole, key-side rows in a 2-slot ring, 16-key steps
 #include <mutex>
 #include <type_traits>
-#include "common.h"
+#include "attn_common.h"
 #include "uvit_internal.h"
 
-// hand-placed MFMA -> VALU wait states where a branch follows an MFMA chain (tools/check_mfma_hazard.py is the build-time guard;
-// -DATTN_NO_HAZARD_PAD builds the deliberately broken variant the guard must flag)
-#ifdef ATTN_NO_HAZARD_PAD
-#define HAZARD_PAD()
-#else
-#define HAZARD_PAD() asm volatile("s_nop 15\n\ts_nop 7" ::: "memory")
-#endif
 #define HD 64
-#define NT_MAX 13
-#define LOG2E 1.4426950408889634f
-#define NEG_BIG (-1e30f)
 
-__device__ __forceinline__ int img_off2(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 __device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
 enum { TR_NONE = 0, TR_SIG = 1, TR_SQRT_SIG = 2 };
-
-__device__ __forceinline__ bf16x8 rowf(const char* img, int row, int chunk) { return *(const bf16x8*)(img + img_off2(row, chunk)); }
-
-__device__ __forceinline__ bf16x8 colf(const char* img, int r_lo, int r_hi, int col0, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int chunk = (col0 >> 3) + (p >> 1), within = (p & 1) << 3;
-    const int ra = r_lo + 4 * g + q, rb = r_hi + 4 * g + q;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, img + img_off2(ra, chunk) + within));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, img + img_off2(rb, chunk) + within));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ bf16x8 pk8(const float* a, const float* b) {
-    bf16x8 v = {f2bf(a[0]), f2bf(a[1]), f2bf(a[2]), f2bf(a[3]), f2bf(b[0]), f2bf(b[1]), f2bf(b[2]), f2bf(b[3])};
-    return v;
-}
-__device__ __forceinline__ uint32_t pair_hash2(uint32_t key32, uint32_t pidx) {
-    uint32_t x = (pidx ^ key32) * 0x9E3779B1u;
-    x ^= x >> 15; x *= 0x85EBCA77u; x ^= x >> 13;
-    return x;
-}
-__device__ __forceinline__ void keep4b(uint32_t key32, uint32_t rowpair, int kbase, uint32_t thr16, bool (&k)[4]) {
-    const uint32_t h0 = pair_hash2(key32, rowpair + (kbase >> 1)), h1 = pair_hash2(key32, rowpair + (kbase >> 1) + 1);
-    k[0] = (h0 & 0xFFFFu) >= thr16; k[1] = (h0 >> 16) >= thr16; k[2] = (h1 & 0xFFFFu) >= thr16; k[3] = (h1 >> 16) >= thr16;
-}
-__device__ __forceinline__ bool keep1b(uint32_t key32, uint32_t rowpair, int key, uint32_t thr16) {
-    const uint32_t h = pair_hash2(key32, rowpair + (key >> 1));
-    return ((key & 1) ? (h >> 16) : (h & 0xFFFFu)) >= thr16;
-}
-__device__ __forceinline__ float gsum4(float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; }
-__device__ __forceinline__ float gmax4(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); v = fmaxf(v, __shfl_xor(v, 32, 64)); return v; }
 
 // the wave's 16 tokens as MFMA B-operand fragments: lane (g, li) holds token li, features 8g..8g+7 (+32)
 struct TokFrags { bf16x8 m[2], c[2]; float side; };     // side = sum sig^2 + sum sig over this lane's 16+16 features
@@ -90,12 +46,6 @@ __device__ __forceinline__ TokFrags load_tok(const bf16* mean_row, const bf16* c
     return t;
 }
 
-__device__ __forceinline__ void dma_rows8_2(char* img, int rb, const bf16* src, size_t stride, int row0, int n_valid, int lane) {
-    const int row = row0 + 8 * rb + (lane >> 3);
-    const int chunk = (lane & 7) ^ (lane >> 3);
-    const int r = row < n_valid ? row : n_valid - 1;
-    __builtin_amdgcn_global_load_lds(GLB_PTR(void, src + (size_t)r * stride + chunk * 8), LDS_PTR(void, img + rb * 1024), 16, 0, 0);
-}
 // one 16-B chunk of a token row through the transform: returns the transformed chunk and this chunk's part of the row term
 template <int TR>
 __device__ __forceinline__ bf16x8 tr_chunk(const bf16x8 v, float pre_scale, float& part) {
@@ -148,7 +98,7 @@ void attn2_fwd_kernel(const bf16* __restrict__ qkv_m, const bf16* __restrict__ q
     for (int p = wave; p < 2 * (FW2_ROWS / 8); p += FW2_WAVES) {
         const int img = p & 1, rb = p >> 1;
         if (rb * 8 >= nt * 16) continue;
-        dma_rows8_2(img ? cvimg : vimg, rb, (img ? base_c : base_m) + 2 * C, ld, 0, N, lane);
+        dma_rows8(img ? cvimg : vimg, rb, (img ? base_c : base_m) + 2 * C, ld, 0, N, lane);
     }
     // staging tasks: task = wave + 13 j covers (tensor, 8-row block): 2 x 26 row blocks of 8 rows x 8 chunks
     bf16x8 kraw[4];
@@ -162,7 +112,7 @@ void attn2_fwd_kernel(const bf16* __restrict__ qkv_m, const bf16* __restrict__ q
     float ri = 0.f;
     if (active) {
         A = load_tok(base_m + (size_t)qr * ld, base_c + (size_t)qr * ld, g, scale);
-        ri = gsum4(A.side);
+        ri = group_sum4(A.side);
     }
     for (int i = tid; i < FW2_ROWS; i += FW2_WAVES * 64) cj[i] = 0.f;
     __syncthreads();
@@ -177,7 +127,7 @@ void attn2_fwd_kernel(const bf16* __restrict__ qkv_m, const bf16* __restrict__ q
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = f2bf(0.f);
         }
-        *(bf16x8*)((tens ? bc : bm) + img_off2(row, ch)) = o;
+        *(bf16x8*)((tens ? bc : bm) + img_off(row, ch)) = o;
         part += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, part), 0x101, 0xf, 0xf, true));   // row_shl:1
         part += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, part), 0x102, 0xf, 0xf, true));   // row_shl:2
         part += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, part), 0x104, 0xf, 0xf, true));   // row_shl:4
@@ -204,8 +154,8 @@ void attn2_fwd_kernel(const bf16* __restrict__ qkv_m, const bf16* __restrict__ q
             f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowf(bm, t * 16 + li, kk * 4 + g), A.m[kk], a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rowf(bc, t * 16 + li, kk * 4 + g), A.c[kk], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(row_frag(bm, t * 16 + li, kk * 4 + g), A.m[kk], a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(row_frag(bc, t * 16 + li, kk * 4 + g), A.c[kk], a, 0, 0, 0);
             }
             const float4 cv4 = *(const float4*)(cj + t * 16 + 4 * g);
             const float cc[4] = {cv4.x, cv4.y, cv4.z, cv4.w};
@@ -222,7 +172,7 @@ void attn2_fwd_kernel(const bf16* __restrict__ qkv_m, const bf16* __restrict__ q
             for (int r = 0; r < 4; ++r) s[t][r] = 0.f;
         }
     }
-    mx = gmax4(mx);
+    mx = group_max4(mx);
     float sum = 0.f;
 #pragma unroll
     for (int t = 0; t < NT_MAX; ++t)
@@ -230,7 +180,7 @@ void attn2_fwd_kernel(const bf16* __restrict__ qkv_m, const bf16* __restrict__ q
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const float p = __builtin_amdgcn_exp2f(s[t][r] - mx); s[t][r] = p; sum += p; }
         }
-    sum = gsum4(sum);
+    sum = group_sum4(sum);
     if (g == 0 && q < N) lse[(size_t)bh * N + q] = mx + __builtin_amdgcn_logf(sum);
     const float f = inv_keep / sum;        // PD = p * f (kept) ; PD^2 = p^2 * f^2
     f32x4 om[4], oc[4];
@@ -246,21 +196,21 @@ void attn2_fwd_kernel(const bf16* __restrict__ qkv_m, const bf16* __restrict__ q
             for (int r = 0; r < 4; ++r) { pa[r] = s[t0][r] * f; pb[r] = t1 < NT_MAX ? s[t1 < NT_MAX ? t1 : 0][r] * f : 0.f; }
             if (drop_thr) {
                 bool k4[4];
-                keep4b(drop_key, rowpair, t0 * 16 + 4 * g, drop_thr, k4);
+                keep4(drop_key, rowpair, t0 * 16 + 4 * g, drop_thr, k4);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pa[r] = k4[r] ? pa[r] : 0.f;
-                keep4b(drop_key, rowpair, t1 * 16 + 4 * g, drop_thr, k4);
+                keep4(drop_key, rowpair, t1 * 16 + 4 * g, drop_thr, k4);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pb[r] = k4[r] ? pb[r] : 0.f;
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) { qa[r] = pa[r] * pa[r]; qb[r] = pb[r] * pb[r]; }
-            const bf16x8 pf = pk8(pa, pb), pf2 = pk8(qa, qb);
+            const bf16x8 pf = pack8(pa, pb), pf2 = pack8(qa, qb);
             const int r1 = t1 < nt ? t1 * 16 : t0 * 16;          // no second tile: its p is 0 (bias -1e30 / zeroed s), re-read the first
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                om[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(colf(vimg, t0 * 16, r1, dt * 16, lane), pf, om[dt], 0, 0, 0);
-                oc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(colf(cvimg, t0 * 16, r1, dt * 16, lane), pf2, oc[dt], 0, 0, 0);
+                om[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(col_frag(vimg, t0 * 16, r1, dt * 16, lane), pf, om[dt], 0, 0, 0);
+                oc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(col_frag(cvimg, t0 * 16, r1, dt * 16, lane), pf2, oc[dt], 0, 0, 0);
             }
         }
     }
@@ -308,7 +258,7 @@ __device__ __forceinline__ float back_cov(float dA, float dside, float y) {   //
 // Why steps of 16 keys: the B phase needs all four query-side operands whole (dM, dC, A_m, A_c: 104 KiB), and P, P^2, gW staged
 // for every query of a step; with 32-key steps (the base kernel's) that is 104 + 78 KiB + the key rows.  At 16 keys: 104 KiB +
 // 2 x 3 x 6.5 KiB of step buffers + 2 x 8 KiB of key rows = 159 KiB.
-// LDS images use the forward's swizzle (img_off2); step buffer rows are 32 B = four 8-B slots (4 keys each), slot s of row q
+// LDS images use the forward's swizzle (img_off); step buffer rows are 32 B = four 8-B slots (4 keys each), slot s of row q
 // at s ^ ((q >> 2) & 3): the 8-B writes of a 16-lane group (16 consecutive rows, one slot) touch every bank once, and a
 // transposed read's 32-lane half covers 8 whole rows = 256 contiguous bytes.
 // ------------------------------------------------------------------------------------------
@@ -351,7 +301,7 @@ __device__ __forceinline__ bf16x8 sb16_col_frag(const char* sb, int r_lo, int r_
 // A operand of the K = 16 MFMA: lane (g, i) = img[row 4g + e][col0 + i], e = 0..3 (rows = the step's keys)
 __device__ __forceinline__ s16x4 col_frag16(const char* img, int col0, int lane) {
     const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, img + img_off2(4 * g + q, (col0 >> 3) + (p >> 1)) + ((p & 1) << 3)));
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, img + img_off(4 * g + q, (col0 >> 3) + (p >> 1)) + ((p & 1) << 3)));
 }
 template <bool HAS_BIAS, int NT_C>
 __global__ __launch_bounds__(F2_WAVES * 64)
@@ -401,7 +351,7 @@ void attn2_bwd_fused_kernel(const bf16* __restrict__ qkv_m, const bf16* __restri
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = f2bf(0.f);
         }
-        *(bf16x8*)(slot + l_t * 2048 + img_off2(l_row, l_ch)) = o;
+        *(bf16x8*)(slot + l_t * 2048 + img_off(l_row, l_ch)) = o;
         // sum over the row's 8 chunk lanes by DPP row shifts (lane 8 k of a row ends with lanes 8 k .. 8 k + 7), then the other tensor
         part += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, part), 0x101, 0xf, 0xf, true));   // row_shl:1
         part += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, part), 0x102, 0xf, 0xf, true));   // row_shl:2
@@ -413,7 +363,7 @@ void attn2_bwd_fused_kernel(const bf16* __restrict__ qkv_m, const bf16* __restri
         char* slot = ring + (step & 1) * F2_SLOT;
 #pragma unroll
         for (int pc = 0; pc < 4; ++pc)
-            dma_rows8_2(slot + 4096 + (pc >> 1) * 2048, pc & 1, ((pc >> 1) ? base_c : base_m) + 2 * C, ld, step * 16, N, lane);
+            dma_rows8(slot + 4096 + (pc >> 1) * 2048, pc & 1, ((pc >> 1) ? base_c : base_m) + 2 * C, ld, step * 16, N, lane);
     };
 
     // ---- preamble: every global request first (dM, dC images by LDS-DMA; this wave's raw q / cov_q rows, its dM / dC / mean / cov
@@ -421,7 +371,7 @@ void attn2_bwd_fused_kernel(const bf16* __restrict__ qkv_m, const bf16* __restri
     for (int p = wave; p < 2 * (F2_ROWS / 8); p += F2_WAVES) {
         const int img = p & 1, rb = p >> 1;
         if (rb * 8 >= nt * 16) continue;
-        dma_rows8_2(img ? dcimg : dmimg, rb, img ? dcbase : dmbase, (size_t)C, 0, N, lane);
+        dma_rows8(img ? dcimg : dmimg, rb, img ? dcbase : dmbase, (size_t)C, 0, N, lane);
     }
     float ri = 0.f, dl = 0.f, lse_q = 1e30f;        // padded query lanes: p = exp2(.. - 1e30) = 0
     bf16x8 kraw0 = {};
@@ -450,8 +400,8 @@ void attn2_bwd_fused_kernel(const bf16* __restrict__ qkv_m, const bf16* __restri
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { om_[j] = f2bf(0.f); oc_[j] = f2bf(0.f); }
             }
-            *(bf16x8*)(qa + img_off2(row, ch)) = om_;
-            *(bf16x8*)(qc + img_off2(row, ch)) = oc_;
+            *(bf16x8*)(qa + img_off(row, ch)) = om_;
+            *(bf16x8*)(qc + img_off(row, ch)) = oc_;
             float s_ = pm_ + pc_;
             s_ += __shfl_xor(s_, 1, 64); s_ += __shfl_xor(s_, 2, 64); s_ += __shfl_xor(s_, 4, 64);
             side[k] = s_;                                              // row term of row 8 k + (lane >> 3)
@@ -463,7 +413,7 @@ void attn2_bwd_fused_kernel(const bf16* __restrict__ qkv_m, const bf16* __restri
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
             for (int j = 0; j < 8; ++j) dl += bf2f(dmf[kk][j]) * bf2f(omf[kk][j]) + 2.0f * bf2f(dcf[kk][j]) * bf2f(ocf[kk][j]);
-        dl = gsum4(dl);                                               // delta_i = dM.mean + 2 dC.cov
+        dl = group_sum4(dl);                                               // delta_i = dM.mean + 2 dC.cov
         if (q < N && g == 0) delta[(size_t)bh * N + q] = dl;
     }
     if (wave < 4) k_write(0, kraw0, lane);
@@ -502,35 +452,35 @@ void attn2_bwd_fused_kernel(const bf16* __restrict__ qkv_m, const bf16* __restri
         // the dropout draw comes BEFORE the MFMAs: no wave-uniform branch between an MFMA and the first VALU read of its result
         // (hipcc pads the MFMA -> VALU wait states along the fall-through path only; attention.hip)
         bool k4[4] = {true, true, true, true};
-        if (drop_thr) keep4b(drop_key, ((uint32_t)bh * N + q) * (uint32_t)(NP >> 1), i * 16 + 4 * g, drop_thr, k4);
+        if (drop_thr) keep4(drop_key, ((uint32_t)bh * N + q) * (uint32_t)(NP >> 1), i * 16 + 4 * g, drop_thr, k4);
         const float4 cv4 = *(const float4*)(cjr + (i & 1) * 16 + 4 * g);
         F2SUB(24);
         f32x4 sacc, pm, pc;
         {
-            const bf16x8 k0 = rowf(bm, li, g), k1 = rowf(bm, li, 4 + g);
-            const bf16x8 a0 = rowf(qa, q, g), a1 = rowf(qa, q, 4 + g);
+            const bf16x8 k0 = row_frag(bm, li, g), k1 = row_frag(bm, li, 4 + g);
+            const bf16x8 a0 = row_frag(qa, q, g), a1 = row_frag(qa, q, 4 + g);
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
             sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, a0, z, 0, 0, 0);
             sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, a1, sacc, 0, 0, 0);
         }
         {
-            const bf16x8 k0 = rowf(bc, li, g), k1 = rowf(bc, li, 4 + g);
-            const bf16x8 a0 = rowf(qc, q, g), a1 = rowf(qc, q, 4 + g);
+            const bf16x8 k0 = row_frag(bc, li, g), k1 = row_frag(bc, li, 4 + g);
+            const bf16x8 a0 = row_frag(qc, q, g), a1 = row_frag(qc, q, 4 + g);
             sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, a0, sacc, 0, 0, 0);
             sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, a1, sacc, 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
         F2SUB(25);
         {
-            const bf16x8 v0 = rowf(vimg, li, g), v1 = rowf(vimg, li, 4 + g);
-            const bf16x8 d0 = rowf(dmimg, q, g), d1 = rowf(dmimg, q, 4 + g);
+            const bf16x8 v0 = row_frag(vimg, li, g), v1 = row_frag(vimg, li, 4 + g);
+            const bf16x8 d0 = row_frag(dmimg, q, g), d1 = row_frag(dmimg, q, 4 + g);
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
             pm = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, d0, z, 0, 0, 0);
             pm = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, d1, pm, 0, 0, 0);
         }
         {
-            const bf16x8 v0 = rowf(cvimg, li, g), v1 = rowf(cvimg, li, 4 + g);
-            const bf16x8 d0 = rowf(dcimg, q, g), d1 = rowf(dcimg, q, 4 + g);
+            const bf16x8 v0 = row_frag(cvimg, li, g), v1 = row_frag(cvimg, li, 4 + g);
+            const bf16x8 d0 = row_frag(dcimg, q, g), d1 = row_frag(dcimg, q, 4 + g);
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
             pc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, d0, z, 0, 0, 0);
             pc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, d1, pc, 0, 0, 0);
@@ -597,11 +547,11 @@ void attn2_bwd_fused_kernel(const bf16* __restrict__ qkv_m, const bf16* __restri
         auto kstep = [&](int ks) __attribute__((always_inline)) {
             const bool hk = 2 * ks + 1 < nt;
             const int r_lo = 32 * ks, r_hi = hk ? r_lo + 16 : r_lo;
-            const bf16x8 a0 = colf(img0, r_lo, r_hi, dtj * 16, lane);
+            const bf16x8 a0 = col_frag(img0, r_lo, r_hi, dtj * 16, lane);
             const bf16x8 b0 = sb16_col_frag(sb0, r_lo, r_hi, hk, lane);
             acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc0, 0, 0, 0);
             if constexpr (role == 2) {
-                const bf16x8 a1 = colf(dcimg, r_lo, r_hi, dtj * 16, lane);
+                const bf16x8 a1 = col_frag(dcimg, r_lo, r_hi, dtj * 16, lane);
                 const bf16x8 b1 = sb16_col_frag(pbuf + F2_SB, r_lo, r_hi, hk, lane);
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc1, 0, 0, 0);
             } else {
@@ -694,7 +644,7 @@ void attn2_bwd_fused_kernel(const bf16* __restrict__ qkv_m, const bf16* __restri
     if (wave < F2_WAVES - 1) B_any(nt - 1, lane, xnext);
     F2STAMP(18);
     if (active) {
-        dside = gsum4(dside);                                  // d r_i = sum_j dL/dW_ij
+        dside = group_sum4(dside);                                  // d r_i = sum_j dL/dW_ij
         if (q < N) {
             bf16* om = dqkv_m + ((size_t)b * N + q) * ld + h * HD + 4 * g;
             bf16* oc = dqkv_c + ((size_t)b * N + q) * ld + h * HD + 4 * g;
