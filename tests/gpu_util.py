@@ -85,6 +85,118 @@ def assert_grads_close(native_grads, ref_grads, names=None, max_tol=5e-2, l2_tol
     assert not bad, f"{what}gradient mismatch (max-norm ratio, relative L2): {bad}"
 
 
+def nt_auto_plan(M, N, K, mode, cu=256, persist=True):
+    """The auto dispatch (nt_variant 3) of uvit_gemm_nt_launch for an M x N x K launch, restated from the comments of that
+    function: (kernel, tail_rows) with kernel one of "128" (the 128x128 kernel: N % 256 != 0, M < 1024, K < 128 or K % 64 != 0),
+    "320" (320-row tiles, taken when they save more than 10 % of rounds x rows), "256p" (256-row tiles, persistent: more tiles
+    than `cu & ~7` workgroups; never for the MULAUX / DGELU epilogues) and "256"; tail_rows > 0 when 256-row tiles overflow whole
+    rounds of the CUs by at most a quarter of them: the overflowing row tiles go to a second, 128x128 launch (not PATCH)."""
+    if (N % 256) or M < 1024 or K < 128 or (K % 64):
+        return "128", 0
+    tn = N // 256
+    ceil = lambda a, b: (a + b - 1) // b                                      # noqa: E731
+    c4, c5 = ceil(ceil(M, 256) * tn, cu) * 256, ceil(ceil(M, 320) * tn, cu) * 320
+    if c5 * 10 < c4 * 9:
+        return "320", 0
+    tail = 0
+    if mode != 5:
+        tiles = ceil(M, 256) * tn
+        rounds = tiles // cu
+        over = tiles - rounds * cu
+        if rounds >= 1 and 0 < over and over * 4 <= cu:
+            rows_a = (rounds * cu // tn) * 256
+            if 0 < rows_a < M:
+                tail, M = M - rows_a, rows_a
+    grid = ceil(M, 256) * tn
+    return ("256p" if persist and grid > (cu & ~7) and mode not in (6, 9) else "256"), tail
+
+
+def nt_boundary_rows(N, K, mode, m_max, cu=256, persist=True):
+    """Every M in [1, m_max] just below, at and just above a row count where nt_auto_plan changes its kernel or starts / stops
+    splitting rows off, plus one 256-row tile to either side of each change between the persistent and the one-tile-per-workgroup form."""
+    out = set()
+    prev = nt_auto_plan(1, N, K, mode, cu, persist)
+    for M in range(2, m_max + 1):
+        cur = nt_auto_plan(M, N, K, mode, cu, persist)
+        if (cur[0], cur[1] > 0) != (prev[0], prev[1] > 0):
+            out.update((M - 2, M - 1, M, M + 1))
+            if {cur[0], prev[0]} == {"256", "256p"}:
+                out.update((M - 1 - 256, M - 1 + 256))
+        prev = cur
+    return sorted(m for m in out if 1 <= m <= m_max)
+
+
+# ---- schedules of tests/test_gpu_history.py (their properties are asserted without a GPU by tests/test_host_history.py) ----
+HISTORY_SEED = 4321
+# Per schedule: the model, the batch size, and the steps in order.  A step is ("step", iteration, options) or ("eval", batch size);
+# options: lists=False switches the drop-path sample lists off for that step, masked=N gives the step host-side ragged masks with N
+# masked patches in all (the host's count becomes n_rows_hint: the masked-row last block), oracle=True also compares the step on
+# a fresh engine with the float64 oracle.
+HISTORY = {
+    # kept samples per (branch; layer 0..3) at B = 3: it 8 [[3,3,2,3],[3,3,2,2]], it 1 [[3,2,0,0],[3,3,3,2]], it 9 [[3,3,1,3],[3,3,0,0]],
+    # it 15 [[3,2,2,2],[3,2,3,3]], it 16 [[3,2,3,1],[3,3,2,1]], it 21 [[3,3,2,1],[3,2,3,3]], it 5 [[3,2,2,1],[3,3,3,2]], it 12 [[3,3,1,2],[3,3,3,2]]
+    "tiny": dict(cfg=dict(img_size=48, embed_dim=128, depth=4, num_heads=2, drop_path_rate=0.5, attn_drop_rate=0.1), B=3, n_mask=4,
+                 target_layers=[2, 3], two_stream=False,
+                 steps=[("step", 8, {}), ("step", 1, dict(oracle=True)), ("step", 9, dict(oracle=True)), ("step", 15, {}), ("step", 16, {}),
+                        ("step", 21, dict(lists=False)), ("step", 5, {}), ("step", 12, {})]),
+    # ViT-B/16, B = 32: R = roundup(masked, 64) = 2432, 2304 (a shrink across a multiple of 64), [eval forward at B = 5], 2432, 0 (device-side
+    # masks: the dense last block), 1024, 1536
+    "vitb32": dict(cfg=dict(drop_path_rate=0.5, attn_drop_rate=0.05), B=32, n_mask=75, target_layers=list(range(6, 12)), two_stream=False,
+                   steps=[("step", 0, dict(masked=2400)), ("step", 1, dict(masked=2290)), ("eval", 5), ("step", 2, dict(masked=2400)),
+                          ("step", 3, {}), ("step", 4, dict(masked=1000)), ("step", 5, dict(masked=1500))]),
+    # kept samples of the MLP branch per layer (mean stream; covariance stream) at B = 4: it 10 [4,4,2,3; 4,3,3,3], it 5 [4,3,3,3; 4,2,2,2],
+    # it 6 [4,4,3,2; 4,2,3,3] (layer 3: the mean stream's list shrinks 3 -> 2 while the covariance stream's grows 2 -> 3), it 8 [4,2,2,2; 4,3,4,0],
+    # it 12 [4,3,4,3; 4,3,1,1], it 27 [4,4,4,2; 4,4,3,2]
+    "tiny2": dict(cfg=dict(img_size=48, embed_dim=128, depth=4, num_heads=2, drop_path_rate=0.5, attn_drop_rate=0.05), B=4, n_mask=4,
+                  target_layers=[2, 3], two_stream=True,
+                  steps=[("step", 10, {}), ("step", 5, {}), ("step", 6, {}), ("step", 8, {}), ("step", 12, {}), ("step", 27, {})]),
+    # the head_dim-80 fixture shape (tests/golden/model_hd80.npz); kept samples of layer 1 (attention, MLP) at B = 4: it 6 (4, 3), it 0 (3, 2), it 3 (1, 3)
+    "hd80": dict(cfg=dict(img_size=48, embed_dim=320, depth=2, num_heads=4, drop_path_rate=0.5, attn_drop_rate=0.1), B=4, n_mask=4,
+                 target_layers=[1], two_stream=False, steps=[("step", 6, {}), ("step", 0, {}), ("step", 3, {})]),
+}
+
+
+def history_cfg(name):
+    return vo.VitConfig(init_values=0.1, **HISTORY[name]["cfg"])
+
+
+def history_kept_counts(name, it):
+    """(depth, draws) kept samples per (layer, draw) of a schedule's step, from the oracle's replay of the drop-path draws (pinned to
+    uvit_drop_path_kept_counts by tests/test_host_cpu.py); draws = (attention, MLP), two-stream: (mean attn, mean MLP, cov attn, cov MLP)."""
+    h, cfg = HISTORY[name], history_cfg(name)
+    cols = vd.drop_path_scales(HISTORY_SEED, it, cfg, h["B"]) if h["two_stream"] else list(vo.drop_path_scales(HISTORY_SEED, it, cfg, h["B"]))
+    return [[h["B"] if c[l] is None else int((c[l] != 0).sum()) for c in cols] for l in range(cfg.depth)]
+
+
+def ragged_masks(B, n_patches, total, seed):
+    """(B, g, g) int64 masks with `total` ones in all and another count per sample (the mean +- up to 8, in pairs that cancel)."""
+    base, rem = divmod(total, B)
+    counts = [base + (1 if i < rem else 0) for i in range(B)]
+    for i in range(0, B - 1, 2):
+        d = min(1 + (i // 2 + seed) % 8, counts[i + 1], n_patches - counts[i])
+        counts[i] += d
+        counts[i + 1] -= d
+    assert sum(counts) == total and all(0 <= c <= n_patches for c in counts)
+    g = torch.Generator().manual_seed(seed)
+    m = torch.zeros(B, n_patches, dtype=torch.int64)
+    for b in range(B):
+        m[b, torch.randperm(n_patches, generator=g)[:counts[b]]] = 1
+    side = int(round(n_patches ** 0.5))
+    return m.reshape(B, side, side)
+
+
+def history_batch(name, index):
+    """(images, mask, host_side) of step `index` of a schedule: CPU tensors; host_side = the mask stays on the host (n_rows_hint)."""
+    from oracle.closed_form import closed_form_images, exact_masks
+    h, cfg = HISTORY[name], history_cfg(name)
+    kind, arg, opt = (h["steps"][index] + ({},))[:3]
+    B = h["B"] if kind == "step" else arg
+    x = closed_form_images(f"history/{name}/{index}", B, cfg.img_size)
+    if kind == "step" and "masked" in opt:
+        return x, ragged_masks(B, cfg.num_patches, opt["masked"], 100 + index), True
+    return x, exact_masks(B, cfg.num_patches, h["n_mask"], 100 + index), False
+
+
 def full_size_step_properties(cfg_drop, cfg_nodrop, B, img, n_patches, n_mask, target_layers, two_stream=False, lam=1e-5,
                               lr=2e-3, wd=0.05, decay=0.9998, tag="full"):
     """Size-independent properties of ONE full-size step (the oracle cannot run these sizes in seconds):

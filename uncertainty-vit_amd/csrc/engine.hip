@@ -977,6 +977,10 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
     const BranchRows at = branch_rows(e, l, 0, PASS_STUDENT, e->B), ml = branch_rows(e, l, 1, PASS_STUDENT, e->B);
     const BranchRows nx = l > 0 ? branch_rows(e, l - 1, 1, PASS_STUDENT, e->B) : BranchRows{};
     const int Mmlp = ml.mode == ROWS_ALL ? ml.rows : ml.red;
+    // two-stream model, dense MLP branch: the rows between the mean stream's tokens and the covariance stream's first row (M .. Mpad) are pad
+    // rows of the stacked dY1, which the dgrads and wgrads walk.  A stacked-list branch (ROWS_LIST2: the layer above of this parity, or an
+    // earlier step) puts the covariance stream's compact rows there, so they are zeroed here rather than assumed to have stayed zero
+    if (S == 2 && ml.mode == ROWS_ALL && Mp > (size_t)M) CHECK(uvit_zero_launch(dY1 + (size_t)M * C, (Mp - M) * C * sizeof(bf16), s));
     // weight gradients of the block, launched once the dgrad chain has produced every dY (wgrad)
     TnProb wg[UVIT_TN_GROUP_MAX];
     int nwg = 0;
