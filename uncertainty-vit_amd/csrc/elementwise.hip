@@ -4,6 +4,7 @@
 // weight transposes and the drop-path multipliers.
 #include "common.h"
 #include "uvit_internal.h"
+#include "rowwise.h"
 
 // ------------------------------------------------------------------------------------------
 // images (B,Cin,S,S) f32 -> cols (B*P, Cin*p*p) bf16, k = c*p*p + i*p + j   (conv == GEMM,
@@ -106,7 +107,6 @@ __global__ void relpos_scatter_kernel(const float* __restrict__ slab, int nslab,
 // ------------------------------------------------------------------------------------------
 // column-partial machinery: 4 waves x 64 lanes, each lane owns float4 column groups
 // ------------------------------------------------------------------------------------------
-#define CP_MAXV 8
 #define CP_ROWS 32
 
 template <int NV, int WAVES = 4>
@@ -149,12 +149,7 @@ void ls_bwd_kernel(const float* __restrict__ dx, const bf16* __restrict__ y, con
     const int row_end = min((int)(blockIdx.x + 1) * CP_ROWS, M);
     const int n_valid = rowidx ? min(*count, M) : M;
     for (int row = blockIdx.x * CP_ROWS + wave; row < row_end; row += 4) {
-        if (row >= n_valid) {
-#pragma unroll
-            for (int k = 0; k < NV; ++k)
-                if (lane + 64 * k < nv) ((bf16x4*)(dy + (size_t)row * C))[lane + 64 * k] = bf16x4{f2bf(0.f), f2bf(0.f), f2bf(0.f), f2bf(0.f)};
-            continue;
-        }
+        if (row >= n_valid) { store_zero_row<NV>(dy + (size_t)row * C, nv, lane); continue; }
         const int xr = rowidx ? rowidx[row] : row;
         const float dp = rowscale ? rowscale[xr / tokens] : 1.0f;
 #pragma unroll
@@ -164,11 +159,7 @@ void ls_bwd_kernel(const float* __restrict__ dx, const bf16* __restrict__ y, con
                 const float4 d = ((const float4*)(dx + (size_t)xr * C))[i];
                 const float4 g = ((const float4*)gamma)[i];
                 const bf16x4 yy = ((const bf16x4*)(y + (size_t)xr * C))[i];
-                const float e0 = d.x * dp, e1 = d.y * dp, e2 = d.z * dp, e3 = d.w * dp;
-                ag[k].x += e0 * bf2f(yy[0]); ag[k].y += e1 * bf2f(yy[1]); ag[k].z += e2 * bf2f(yy[2]); ag[k].w += e3 * bf2f(yy[3]);
-                bf16x4 o = {f2bf(e0 * g.x), f2bf(e1 * g.y), f2bf(e2 * g.z), f2bf(e3 * g.w)};
-                ((bf16x4*)(dy + (size_t)row * C))[i] = o;
-                ab[k].x += bf2f(o[0]); ab[k].y += bf2f(o[1]); ab[k].z += bf2f(o[2]); ab[k].w += bf2f(o[3]);
+                ls_apply(d, dp, yy, g, (bf16x4*)(dy + (size_t)row * C) + i, ag[k], ab[k]);
             }
         }
     }
@@ -226,7 +217,7 @@ void smooth_l1_kernel(const float* __restrict__ out, const float* __restrict__ t
     const float inv = loss_scale / ((float)n_valid * (float)C);
     float part = 0.f;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
-        bf16x4 g = {f2bf(0.f), f2bf(0.f), f2bf(0.f), f2bf(0.f)};
+        bf16x4 g = bf16x4_zero();
         if (i < valid) {
             const float4 o = ((const float4*)out)[i], t = ((const float4*)target)[i];
             const float d[4] = {o.x - t.x, o.y - t.y, o.z - t.z, o.w - t.w};
@@ -404,19 +395,6 @@ void droppath_lists_kernel(const float* __restrict__ scales, int* __restrict__ p
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-#define CP_DISPATCH(KERNEL, C, ...) do { const int _nv = ((C) + 255) / 256; \
-    if (_nv <= 1) hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); else if (_nv == 2) hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); \
-    else if (_nv == 3) hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); else if (_nv == 4) hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); \
-    else if (_nv == 5) hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); else hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); } while (0)
-
-#define LN_DISPATCH2_TKB(W) do { const int _nv = (C + 255) / 256; const dim3 g_((M + rpb - 1) / rpb), b_((W) * 64); \
-    if (_nv <= 1) hipLaunchKernelGGL((token_bwd_kernel<1, W>), g_, b_, 0, s, dx, mask, (bf16*)dpatch, dcls, dmask_token, B, P, C, rpb); \
-    else if (_nv == 2) hipLaunchKernelGGL((token_bwd_kernel<2, W>), g_, b_, 0, s, dx, mask, (bf16*)dpatch, dcls, dmask_token, B, P, C, rpb); \
-    else if (_nv == 3) hipLaunchKernelGGL((token_bwd_kernel<3, W>), g_, b_, 0, s, dx, mask, (bf16*)dpatch, dcls, dmask_token, B, P, C, rpb); \
-    else if (_nv == 4) hipLaunchKernelGGL((token_bwd_kernel<4, W>), g_, b_, 0, s, dx, mask, (bf16*)dpatch, dcls, dmask_token, B, P, C, rpb); \
-    else if (_nv == 5) hipLaunchKernelGGL((token_bwd_kernel<5, W>), g_, b_, 0, s, dx, mask, (bf16*)dpatch, dcls, dmask_token, B, P, C, rpb); \
-    else hipLaunchKernelGGL((token_bwd_kernel<8, W>), g_, b_, 0, s, dx, mask, (bf16*)dpatch, dcls, dmask_token, B, P, C, rpb); } while (0)
-
 static inline int grid_for(size_t n, int block, int cap = 256 * 8) {
     size_t g = (n + block - 1) / block;
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
@@ -448,12 +426,13 @@ int uvit_relpos_scatter_launch(const float* slab, int nslab, const int* index, f
     hipLaunchKernelGGL(relpos_scatter_kernel, dim3(H, 24), dim3(256), ntable * sizeof(float), s, slab, nslab, index, dtable, H, N, NP, ntable);
     return uvit_check_launch();
 }
-int uvit_ls_bwd_launch(const float* dx, const void* y, const float* gamma, const float* rowscale, void* dy,
-                       float* dgamma, float* dbias, int M, int C, int tokens, int nrep, size_t rep_stride, hipStream_t s,
+int uvit_ls_bwd_launch(const float* dx, const LsNext& ls, int M, int C, int nrep, size_t rep_stride, hipStream_t s,
                        const int* rowidx, const int* count) {
-    if (C % 4 || C > CP_MAXV * 256 || (rowidx && !count)) return UVIT_ERR_SHAPE;
-    CP_DISPATCH(ls_bwd_kernel, C, dim3((M + CP_ROWS - 1) / CP_ROWS), dim3(256), 0, s, dx, (const bf16*)y, gamma, rowscale,
-                       (bf16*)dy, dgamma, dbias, M, C, tokens, nrep > 0 ? nrep : 1, rep_stride, rowidx, count);
+    if (C % 4 || C > ROW_MAXV * 256 || (rowidx && !count)) return UVIT_ERR_SHAPE;
+    dispatch_nv(C, [&](auto nv) {
+        hipLaunchKernelGGL(ls_bwd_kernel<decltype(nv)::value>, dim3((M + CP_ROWS - 1) / CP_ROWS), dim3(256), 0, s, dx, ls.y, ls.gamma, ls.rowscale,
+                           ls.dy, ls.dgamma, ls.dbias, M, C, ls.tokens, nrep > 0 ? nrep : 1, rep_stride, rowidx, count);
+    });
     return uvit_check_launch();
 }
 __global__ void rows_guard_kernel(const int* __restrict__ count, int limit, float* __restrict__ loss) {
@@ -478,7 +457,7 @@ int uvit_smooth_l1_launch(const float* out, const float* target, const int* coun
 }
 int uvit_token_bwd_launch(const float* dx, const int64_t* mask, void* dpatch, float* dcls, float* dmask_token, int B,
                           int P, int C, hipStream_t s) {
-    if (C % 4 || C > CP_MAXV * 256) return UVIT_ERR_SHAPE;
+    if (C % 4 || C > ROW_MAXV * 256) return UVIT_ERR_SHAPE;
     // every workgroup ends with 2 x C same-address atomics (d cls_token, d mask_token have ONE accumulator each): with
     // 32-row workgroups (788 of them at bs = 128) those contended atomics were most of the kernel's 169 us.  One
     // workgroup per CU-slot instead: <= 512 workgroups.
@@ -489,7 +468,10 @@ int uvit_token_bwd_launch(const float* dx, const int64_t* mask, void* dpatch, fl
     int rpb = (M + 127) / 128;
     rpb = ((rpb + 15) / 16) * 16;
     if (rpb < 32) rpb = 32;
-    LN_DISPATCH2_TKB(16);
+    dispatch_nv(C, [&](auto nv) {
+        hipLaunchKernelGGL((token_bwd_kernel<decltype(nv)::value, 16>), dim3((M + rpb - 1) / rpb), dim3(16 * 64), 0, s, dx, mask, (bf16*)dpatch,
+                           dcls, dmask_token, B, P, C, rpb);
+    });
     return uvit_check_launch();
 }
 int uvit_transpose_batch_launch(const void* descs_dev, int ndesc, int total_tiles, hipStream_t s) {

@@ -642,8 +642,10 @@ static int forward_layer(uvit_engine* e, const Weights& w, int l, const float* x
     const BranchRows at = branch_rows(e, l, 0, pass, Bc), ml = branch_rows(e, l, 1, pass, Bc);
     // counters of the persistent GEMMs' dynamic tile assignment: one block per stream (the teacher and student forwards run side by side)
     unsigned* const tcnt = e->tile_cnt + ((e->dual && s == e->aux) ? 16 : 0);
-    if (at.mode == ROWS_LIST) CHECK(uvit_ln_fwd_keep_launch(x_in, at.d[0].pos, w.f + o.n1w, w.f + o.n1b, a.ln1, a.mean1, a.rstd1, x_mid, M, C, e->N, e->cfg.ln_eps, s));
-    else CHECK(uvit_ln_fwd_launch(x_in, w.f + o.n1w, w.f + o.n1b, a.ln1, a.mean1, a.rstd1, at.rows, C, e->cfg.ln_eps, s));
+    LnFwd n1; n1.x = x_in; n1.w = w.f + o.n1w; n1.b = w.f + o.n1b; n1.y = a.ln1; n1.mean = a.mean1; n1.rstd = a.rstd1; n1.M = at.rows; n1.C = C;
+    n1.eps = e->cfg.ln_eps;
+    if (at.mode == ROWS_LIST) { n1.pos = at.d[0].pos; n1.xcopy = x_mid; n1.tokens = e->N; n1.M = M; }      // the dropped rows copied to x_mid
+    CHECK(uvit_ln_fwd_launch(n1, s));
     for (int st = 0; st < S; ++st) {     // same qkv.weight for both streams (modeling_finetune_dist.py:121,127)
         GemmEpi q; q.out = a.qkv + at.off[st] * 3 * C; q.bias = w.f + off_qb(o, st); q.bias2 = w.f + off_vb(o, st); q.ldo = 3 * C;
         q.tile_counter = tcnt;
@@ -672,18 +674,18 @@ static int forward_layer(uvit_engine* e, const Weights& w, int l, const float* x
         CHECK(GEMM_NT(EPI_RESID, a.attn + at.off[st] * C, w.b + off_projw(o, st), at.n[st], C, C, C, C, &p, s));
         prof_end(pp);
     }
-    switch (ml.mode) {
-    case ROWS_LIST: case ROWS_LIST2:     // each stream's kept rows to its compact rows; the dropped rows copied to x_out
-        for (int st = 0; st < S; ++st)
-            CHECK(uvit_ln_fwd_keep_launch(x_mid + st * Mp * C, ml.d[st].pos, w.f + o.n2w, w.f + o.n2b, a.ln2 + ml.off[st] * C, a.mean2 + ml.off[st],
-                                          a.rstd2 + ml.off[st], x_out + st * Mp * C, M, C, e->N, e->cfg.ln_eps, s));
-        break;
-    case ROWS_MASKED:
-        CHECK(uvit_ln_fwd_gather_launch(x_mid, e->rowidx, e->count, w.f + o.n2w, w.f + o.n2b, a.ln2, a.mean2, a.rstd2, ml.rows, C, e->cfg.ln_eps, s));
-        break;
-    case ROWS_ALL:
-        CHECK(uvit_ln_fwd_launch(x_mid, w.f + o.n2w, w.f + o.n2b, a.ln2, a.mean2, a.rstd2, ml.rows, C, e->cfg.ln_eps, s));
-        break;
+    LnFwd n2; n2.x = x_mid; n2.w = w.f + o.n2w; n2.b = w.f + o.n2b; n2.y = a.ln2; n2.mean = a.mean2; n2.rstd = a.rstd2; n2.M = ml.rows; n2.C = C;
+    n2.eps = e->cfg.ln_eps;
+    if (ml.mode == ROWS_LIST || ml.mode == ROWS_LIST2) {     // each stream's kept rows to its compact rows; the dropped rows copied to x_out
+        n2.tokens = e->N; n2.M = M;
+        for (int st = 0; st < S; ++st) {
+            n2.x = x_mid + st * Mp * C; n2.pos = ml.d[st].pos; n2.xcopy = x_out + st * Mp * C;
+            n2.y = a.ln2 + ml.off[st] * C; n2.mean = a.mean2 + ml.off[st]; n2.rstd = a.rstd2 + ml.off[st];
+            CHECK(uvit_ln_fwd_launch(n2, s));
+        }
+    } else {                                                 // every row of the stacked streams, or the masked rows gathered (row map null / set)
+        n2.rowidx = ml.rowmap[0]; n2.count = ml.rowcnt[0];
+        CHECK(uvit_ln_fwd_launch(n2, s));
     }
     GemmEpi f1; f1.out = a.a; f1.out2 = save ? a.h : nullptr; f1.bias = w.f + o.fc1b; f1.ldo = Hd; f1.tile_counter = tcnt;
     const bool prof = prof_begin(save ? UVIT_PROF_FC1_S : UVIT_PROF_FC1_T, ml.rows);
@@ -808,10 +810,11 @@ static int head_forward(uvit_engine* e, const Weights& w, int Bc, int st, bool a
     const int BP = rows > 0 ? rows : Bc * e->P;        // rows > 0: a host-side bound on the masked rows (training step with n_rows_hint)
     const float* x = e->X[e->cfg.depth] + (size_t)st * e->Mpad * e->C;
     const size_t lmw = st ? e->lo.clmw : e->lo.lmw, lmb = st ? e->lo.clmb : e->lo.lmb;
+    LnFwd fn; fn.x = x; fn.w = w.f + e->lo.normw; fn.b = w.f + e->lo.normb; fn.C = e->C; fn.eps = e->cfg.ln_eps;
     if (all_tokens) {
         // normalise all tokens, then run the head on the patch rows of each sample
-        CHECK(uvit_ln_fwd_launch(x, w.f + e->lo.normw, w.f + e->lo.normb, e->acts[0].ln1, e->acts[0].mean1, e->acts[0].rstd1,
-                                 Bc * e->N, e->C, e->cfg.ln_eps, s));
+        fn.y = e->acts[0].ln1; fn.mean = e->acts[0].mean1; fn.rstd = e->acts[0].rstd1; fn.M = Bc * e->N;
+        CHECK(uvit_ln_fwd_launch(fn, s));
         for (int b = 0; b < Bc; ++b) {
             GemmEpi h; h.out = out + (size_t)b * e->P * e->C; h.bias = w.f + lmb; h.ldo = e->C;
             CHECK(GEMM_NT(EPI_F32, e->acts[0].ln1 + ((size_t)b * e->N + 1) * e->C, w.b + lmw, e->P, e->C, e->C,
@@ -819,8 +822,8 @@ static int head_forward(uvit_engine* e, const Weights& w, int Bc, int st, bool a
         }
         return UVIT_OK;
     }
-    CHECK(uvit_ln_fwd_gather_launch(x, e->rowidx, e->count, w.f + e->lo.normw, w.f + e->lo.normb, e->normed[st], e->meanF[st],
-                                    e->rstdF[st], BP, e->C, e->cfg.ln_eps, s));
+    fn.rowidx = e->rowidx; fn.count = e->count; fn.y = e->normed[st]; fn.mean = e->meanF[st]; fn.rstd = e->rstdF[st]; fn.M = BP;
+    CHECK(uvit_ln_fwd_launch(fn, s));
     GemmEpi h; h.out = out; h.bias = w.f + lmb; h.ldo = e->C;
     CHECK(GEMM_NT(EPI_F32, e->normed[st], w.b + lmw, BP, e->C, e->C, e->C, e->C, &h, s));
     return UVIT_OK;
@@ -943,9 +946,10 @@ extern "C" int uvit_step_begin(uvit_engine* e, const float* images, const int64_
         GemmEpi d; d.out = e->dnormed[st]; d.ldo = C;
         CHECK(GEMM_NT(EPI_BF16, e->dout[st], wt + lmw, Rh, C, C, C, C, &d, s));
         // final LayerNorm backward scattered into the (zeroed) residual-stream gradient
-        CHECK(uvit_ln_bwd_scatter_launch(e->dnormed[st], e->X[e->cfg.depth] + (size_t)st * e->Mpad * C, e->rowidx, e->count,
-                                         e->meanF[st], e->rstdF[st], e->buf.params + lo.normw, e->dXa + (size_t)st * e->Mpad * C,
-                                         RP(lo.normw), RP(lo.normb), Rh, C, NREP, e->n_nd, s));
+        LnBwd fn; fn.dy = e->dnormed[st]; fn.x = e->X[e->cfg.depth] + (size_t)st * e->Mpad * C; fn.rowidx = e->rowidx; fn.count = e->count;
+        fn.mean = e->meanF[st]; fn.rstd = e->rstdF[st]; fn.w = e->buf.params + lo.normw; fn.dx = e->dXa + (size_t)st * e->Mpad * C;
+        fn.dw = RP(lo.normw); fn.db = RP(lo.normb); fn.M = Rh; fn.C = C; fn.nrep = NREP; fn.rep_stride = e->n_nd;
+        CHECK(uvit_ln_bwd_launch(fn, s));
     }
     return UVIT_OK;
 }
@@ -1002,35 +1006,36 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
     // (the LayerScale backward of a branch rides in the LayerNorm backward that produces its input -- below the top layer, the MLP branch's
     //  rides in the LayerNorm 1 backward of the layer above; in the two-stream model that kernel is launched once per stream, because
     //  drop-path scales and the proj bias differ per stream)
+    // the MLP branch of layer `layer` as the rider of a row-wise backward over stream st: its dY1 is compact by the branch's rows `br`
+    auto mlp_rider = [&](int layer, int st, const BranchRows& br, bf16* dY) {
+        const LayerOff& L = e->lo.L[layer];
+        LsNext n; n.y = e->acts[layer].mlpout + st * Mp * C; n.gamma = pf + L.g2; n.rowscale = dp_ptr(e, dp_on, layer, st, 1, e->B);
+        n.dy = dY + br.off[st] * C; n.dgamma = RP(L.g2); n.dbias = RP(L.fc2b); n.tokens = e->N;
+        return n;
+    };
     if (l == e->cfg.depth - 1)
         for (int st = 0; st < S; ++st)      // a compact branch's last stream runs to the reduction length: the kernel zero-fills the pad rows
-            CHECK(uvit_ls_bwd_launch(e->dXa + st * Mp * C, a.mlpout + st * Mp * C, pf + o.g2, dp_ptr(e, dp_on, l, st, 1, e->B), dY1 + ml.off[st] * C,
-                                     RP(o.g2), RP(o.fc2b), (ml.mode == ROWS_ALL || st + 1 < S) ? ml.n[st] : ml.red - (int)ml.off[st], C, e->N,
-                                     NREP, e->n_nd, s, ml.rowmap[st], ml.rowcnt[st]));
+            CHECK(uvit_ls_bwd_launch(e->dXa + st * Mp * C, mlp_rider(l, st, ml, dY1), (ml.mode == ROWS_ALL || st + 1 < S) ? ml.n[st] : ml.red - (int)ml.off[st],
+                                     C, NREP, e->n_nd, s, ml.rowmap[st], ml.rowcnt[st]));
     GemmEpi d1; d1.out = dH; d1.aux = a.h; d1.ldo = Hd;
     CHECK(GEMM_NT(EPI_MULAUX, dY1, wt + o.fc2w, Mmlp, Hd, C, C, C, &d1, s));      // dH = (dY.W2) * gelu'(h)
     GemmEpi d2; d2.out = e->dLN; d2.ldo = C;
     CHECK(GEMM_NT(EPI_BF16, dH, wt + o.fc1w, Mmlp, C, Hd, Hd, Hd, &d2, s));
     // --- attention branch: x_mid = x_in + dp * gamma1 * proj(attn(ln1(x_in)))   (proj differs per stream)
-    // LayerNorm 2 backward + the attention branch's LayerScale backward
-    if (ml.mode != ROWS_MASKED && (ml.mode != ROWS_ALL || at.mode == ROWS_LIST)) {
-        // dense walk with each branch's sample list (also zero-fills the pad rows of dqkv: the attention backward writes K samples)
-        for (int st = 0; st < S; ++st) {
-            const size_t eo = st * Mp * C;
-            CHECK(uvit_ln_bwd_keep_launch(e->dLN + ml.off[st] * C, e->XM[l] + eo, ml.d[st].pos, a.mean2 + ml.off[st], a.rstd2 + ml.off[st], pf + o.n2w,
-                                          e->dXa + eo, e->dXb + eo, RP(o.n2w), RP(o.n2b), a.projout + eo, pf + o.g1, dp_ptr(e, dp_on, l, st, 0, e->B),
-                                          dY2 + eo, RP(o.g1), RP(off_projb(o, st)), at.d[st].pos, at.d[st].cnt, e->N, M, C, NREP, e->n_nd, s, 0,
-                                          at.mode == ROWS_LIST ? dqkv : nullptr, 3 * C));
-        }
-    } else {
-        // dense, or the row-list kernel of the masked-row last block: dY1 / mean / rstd compact, the (zeroed) dense dXb / dY2 written at the
-        // listed rows, dY2 compact by the attention list when there is one
-        for (int st = 0; st < S; ++st) {
-            const size_t ro = st * Mp, eo = ro * C;
-            CHECK(uvit_ln_bwd_ls_launch(e->dLN + eo, e->XM[l] + eo, a.mean2 + ro, a.rstd2 + ro, pf + o.n2w, e->dXa + eo, e->dXb + eo,
-                                        RP(o.n2w), RP(o.n2b), a.projout + eo, pf + o.g1, dp_ptr(e, dp_on, l, st, 0, e->B), dY2 + eo,
-                                        RP(o.g1), RP(off_projb(o, st)), e->N, ml.n[st], C, NREP, e->n_nd, s, ml.rowmap[st], ml.rowcnt[st], at.d[st].pos));
-        }
+    // LayerNorm 2 backward + the attention branch's LayerScale backward.  Samples walk: dense, with each branch's sample list (it also
+    // zero-fills the pad rows of dY2 and of dqkv: the attention backward writes K samples).  Rows walk: dense, or the row list of the masked-row
+    // last block -- dLN / mean / rstd compact, the (zeroed) dense dXb / dY2 written at the listed rows, dY2 compact by the attention list if any
+    const bool ln2_samples = ml.mode != ROWS_MASKED && (ml.mode != ROWS_ALL || at.mode == ROWS_LIST);
+    for (int st = 0; st < S; ++st) {
+        const size_t eo = st * Mp * C;
+        LnBwd b; b.dy = e->dLN + ml.off[st] * C; b.x = e->XM[l] + eo; b.mean = a.mean2 + ml.off[st]; b.rstd = a.rstd2 + ml.off[st]; b.w = pf + o.n2w;
+        b.dres = e->dXa + eo; b.dx = e->dXb + eo; b.dw = RP(o.n2w); b.db = RP(o.n2b); b.C = C; b.nrep = NREP; b.rep_stride = e->n_nd;
+        LsNext& n = b.next;
+        n.y = a.projout + eo; n.gamma = pf + o.g1; n.rowscale = dp_ptr(e, dp_on, l, st, 0, e->B); n.dy = dY2 + at.off[st] * C;
+        n.dgamma = RP(o.g1); n.dbias = RP(off_projb(o, st)); n.tokens = e->N; n.pos = at.d[st].pos;
+        if (ln2_samples) { b.M = M; b.pos = ml.d[st].pos; n.cnt = at.d[st].cnt; if (at.mode == ROWS_LIST) { n.pad2 = dqkv; n.pad2_cols = 3 * C; } }
+        else { b.M = ml.n[st]; b.rowidx = ml.rowmap[st]; b.count = ml.rowcnt[st]; }
+        CHECK(uvit_ln_bwd_launch(b, s));
     }
     for (int st = 0; st < S; ++st) {
         GemmEpi d3; d3.out = e->dAttn + at.off[st] * C; d3.ldo = C;
@@ -1070,29 +1075,21 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
     // LayerNorm 1 backward + the LayerScale backward of layer l-1's MLP branch into its dY1, of parity (l-1) & 1, last read by the wgrad of
     // layer l+1
     if (l > 0 && e->dual && l + 1 < e->cfg.depth) HIPCHECK(hipStreamWaitEvent(s, e->ev_wdone[l + 1], 0));
-    const LayerOff& on = e->lo.L[l > 0 ? l - 1 : 0];
-    bf16* dYn = l > 0 ? e->dY1[(l - 1) & 1] : nullptr;
-    if (at.mode == ROWS_LIST || nx.mode != ROWS_ALL) {
-        // dense walk with the attention list and the list of layer l-1's MLP (two-stream: its stacked compact dY1, the second launch zero-fills the pad rows)
-        for (int st = 0; st < S; ++st) {
-            const size_t ro = st * Mp, eo = ro * C;
-            const bool last = st + 1 == S;
-            CHECK(uvit_ln_bwd_keep_launch(e->dLN + eo, e->X[l] + eo, at.d[st].pos, a.mean1 + ro, a.rstd1 + ro, pf + o.n1w, e->dXb + eo, e->dXa + eo,
-                                          RP(o.n1w), RP(o.n1b), l > 0 ? e->acts[l - 1].mlpout + eo : nullptr, l > 0 ? pf + on.g2 : nullptr,
-                                          l > 0 ? dp_ptr(e, dp_on, l - 1, st, 1, e->B) : nullptr, l > 0 ? dYn + nx.off[st] * C : nullptr,
-                                          l > 0 ? RP(on.g2) : nullptr, l > 0 ? RP(on.fc2b) : nullptr, nx.d[st].pos, last ? nx.d[st].cnt : nullptr,
-                                          e->N, M, C, NREP, e->n_nd, s, last ? (int)nx.off[st] : 0));
+    // Samples walk: dense, with the attention list and the list of layer l-1's MLP (two-stream: its stacked compact dY1, the last stream's launch
+    // zero-fills the pad rows).  Layer 0 has no rider and no per-stream operand: one launch over the stacked streams
+    const bool ln1_samples = at.mode == ROWS_LIST || nx.mode != ROWS_ALL;
+    for (int st = 0; st < (l > 0 ? S : 1); ++st) {
+        const size_t ro = st * Mp, eo = ro * C;
+        LnBwd b; b.dy = e->dLN + eo; b.x = e->X[l] + eo; b.mean = a.mean1 + ro; b.rstd = a.rstd1 + ro; b.w = pf + o.n1w; b.dres = e->dXb + eo;
+        b.dx = e->dXa + eo; b.dw = RP(o.n1w); b.db = RP(o.n1b); b.M = l > 0 ? M : (int)e->rows_all(); b.C = C; b.nrep = NREP;
+        b.rep_stride = e->n_nd;
+        if (ln1_samples) { b.pos = at.d[st].pos; b.next.tokens = e->N; }
+        if (l > 0) {
+            b.next = mlp_rider(l - 1, st, nx, e->dY1[(l - 1) & 1]);
+            b.next.pos = nx.d[st].pos;
+            if (st + 1 == S && nx.d[st].cnt) { b.next.cnt = nx.d[st].cnt; b.next.pad_base = (int)nx.off[st]; }
         }
-    } else if (l > 0) {
-        for (int st = 0; st < S; ++st) {
-            const size_t ro = st * Mp, eo = ro * C;
-            CHECK(uvit_ln_bwd_ls_launch(e->dLN + eo, e->X[l] + eo, a.mean1 + ro, a.rstd1 + ro, pf + o.n1w, e->dXb + eo, e->dXa + eo,
-                                        RP(o.n1w), RP(o.n1b), e->acts[l - 1].mlpout + eo, pf + on.g2, dp_ptr(e, dp_on, l - 1, st, 1, e->B),
-                                        dYn + eo, RP(on.g2), RP(on.fc2b), e->N, M, C, NREP, e->n_nd, s));
-        }
-    } else {
-        CHECK(uvit_ln_bwd_launch(e->dLN, e->X[l], a.mean1, a.rstd1, pf + o.n1w, e->dXb, e->dXa, RP(o.n1w), RP(o.n1b), (int)e->rows_all(), C,
-                                 NREP, e->n_nd, s));
+        CHECK(uvit_ln_bwd_launch(b, s));
     }
     return UVIT_OK;
 }
@@ -1293,10 +1290,14 @@ extern "C" int uvit_op_relpos_scatter(const float* slab, int nslab, const int32_
     return uvit_relpos_scatter_launch(slab, nslab, idx, dt, H, N, NP, S(st));
 }
 extern "C" int uvit_op_ln_fwd(const float* x, const float* w, const float* b, void* y, float* mean, float* rstd, int M, int C,
-                              float eps, uvit_stream st) { return uvit_ln_fwd_launch(x, w, b, y, mean, rstd, M, C, eps, S(st)); }
+                              float eps, uvit_stream st) {
+    LnFwd p; p.x = x; p.w = w; p.b = b; p.y = (bf16*)y; p.mean = mean; p.rstd = rstd; p.M = M; p.C = C; p.eps = eps;
+    return uvit_ln_fwd_launch(p, S(st));
+}
 extern "C" int uvit_op_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* w,
                               const float* dres, float* dx, float* dw, float* db, int M, int C, uvit_stream st) {
-    return uvit_ln_bwd_launch(dy, x, mean, rstd, w, dres, dx, dw, db, M, C, 1, 0, S(st));
+    LnBwd p; p.dy = (const bf16*)dy; p.x = x; p.mean = mean; p.rstd = rstd; p.w = w; p.dres = dres; p.dx = dx; p.dw = dw; p.db = db; p.M = M; p.C = C;
+    return uvit_ln_bwd_launch(p, S(st));
 }
 extern "C" int uvit_op_ema(float* ema, const float* p, void* eb, int64_t n, float d, uvit_stream st) {
     return uvit_ema_launch(ema, p, eb, (size_t)n, d, S(st));

@@ -6,83 +6,48 @@
 // masked-row gather (engine_for_cyclical.py:92-122).
 #include "common.h"
 #include "uvit_internal.h"
+#include "rowwise.h"
 
-#define LN_MAXV 8          // float4 per lane: C <= 2048
 #define LN_WAVES 4
 
-// NV = float4 per lane actually needed (ceil(C / 256)): a template parameter so register use and
-// hence occupancy follow the real row length (NV = 3 for C = 768) instead of the maximum.
-template <int NV> struct RowVec { float4 v[NV]; };
+// How a kernel's row index becomes addresses (LnFwd / LnBwd in uvit_internal.h): WALK_ROWS = dense or through a row list, WALK_SAMPLES =
+// dense walk of the residual stream with COMPACT branch buffers, by the per-sample maps of the drop-path sample lists (round 4).
+enum LnWalk { WALK_ROWS, WALK_SAMPLES };
 
-template <int NV>
-__device__ __forceinline__ void load_row(RowVec<NV>& r, const float* x, int C, int lane) {
-    const int nv = C >> 2;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        r.v[k] = i < nv ? ((const float4*)x)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-
-template <int NV>
-__device__ __forceinline__ void row_stats(const RowVec<NV>& r, int C, int lane, float eps, float& mean, float& rstd) {
-    const int nv = C >> 2;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s += r.v[k].x + r.v[k].y + r.v[k].z + r.v[k].w;
-    mean = wave_sum(s) / C;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        if (lane + 64 * k < nv) {
-            const float a = r.v[k].x - mean, b = r.v[k].y - mean, c = r.v[k].z - mean, d = r.v[k].w - mean;
-            q += a * a + b * b + c * c + d * d;
-        }
-    }
-    rstd = rsqrtf(wave_sum(q) / C + eps);
-}
-
-// y = (x - mean) * rstd * w + b  ->  bf16
-template <int NV>
+template <int NV, LnWalk WALK>
 __global__ __launch_bounds__(LN_WAVES * 64)
 void ln_fwd_kernel(const float* __restrict__ x, const int* __restrict__ rowidx, const int* __restrict__ count,
-                   const float* __restrict__ w, const float* __restrict__ b, bf16* __restrict__ y,
-                   float* __restrict__ mean_o, float* __restrict__ rstd_o, int M, int C, float eps) {
+                   const int* __restrict__ pos, const float* __restrict__ w, const float* __restrict__ b, bf16* __restrict__ y,
+                   float* __restrict__ mean_o, float* __restrict__ rstd_o, float* __restrict__ xcopy, int M, int C, float eps, int tokens) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * LN_WAVES + (threadIdx.x >> 6);
     if (row >= M) return;
     const int nv = C >> 2;
-    const int n_valid = count ? *count : M;
-    if (row >= n_valid) {     // padded compact rows stay zero
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const int i = lane + 64 * k;
-            if (i < nv) ((bf16x4*)(y + (size_t)row * C))[i] = bf16x4{f2bf(0.f), f2bf(0.f), f2bf(0.f), f2bf(0.f)};
-        }
-        return;
+    int src = row;
+    size_t dst = row;
+    if constexpr (WALK == WALK_ROWS) {
+        if (row >= (count ? *count : M)) { store_zero_row<NV>(y + (size_t)row * C, nv, lane); return; }    // padded compact rows stay zero
+        if (rowidx) src = rowidx[row];
     }
-    const int src = rowidx ? rowidx[row] : row;
     RowVec<NV> r;
     load_row(r, x + (size_t)src * C, C, lane);
+    if constexpr (WALK == WALK_SAMPLES) {
+        const int smp = row / tokens, slot = pos[smp];
+        if (slot < 0) {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) if (lane + 64 * k < nv) ((float4*)(xcopy + (size_t)row * C))[lane + 64 * k] = r.v[k];
+            return;
+        }
+        dst = (size_t)slot * tokens + (row - smp * tokens);
+    }
     float mean, rstd;
     row_stats(r, C, lane, eps, mean, rstd);
-    if (lane == 0 && mean_o) { mean_o[row] = mean; rstd_o[row] = rstd; }
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        if (i < nv) {
-            const float4 ww = ((const float4*)w)[i], bb = ((const float4*)b)[i];
-            bf16x4 o = {f2bf((r.v[k].x - mean) * rstd * ww.x + bb.x), f2bf((r.v[k].y - mean) * rstd * ww.y + bb.y),
-                        f2bf((r.v[k].z - mean) * rstd * ww.z + bb.z), f2bf((r.v[k].w - mean) * rstd * ww.w + bb.w)};
-            ((bf16x4*)(y + (size_t)row * C))[i] = o;
-        }
-    }
+    if (lane == 0 && (WALK == WALK_SAMPLES || mean_o)) { mean_o[dst] = mean; rstd_o[dst] = rstd; }
+    normalize_store(r, mean, rstd, w, b, y + dst * C, nv, lane);
 }
 
-// dx = dres + rstd * (dy*w - mean(dy*w) - xhat * mean(dy*w*xhat));  dw += dy*xhat;  db += dy
-// LS = true fuses the LayerScale + DropPath backward of the branch that consumes dx next (modeling_finetune.py:295-298):
-// with e = dx * dp[row / tokens]:  dy_next = bf16(e * gamma),  dgamma += e * y_next,  dbias += dy_next  -- the fp32
-// residual gradient is then not read a second time by a separate pass.
+// Backward (LnBwd): LS = a branch's LayerScale + DropPath backward rides along on dx (LsNext), so the fp32 residual gradient is not read
+// a second time by a separate pass.
 //
 // Shape of the launch (round 2): ONE 8-wave workgroup per CU walks a contiguous slab of rows.
 //   * every operand row of a wave's NEXT row (x, dy, dres, y_next: 9 KB) is requested before the current row's two wave
@@ -92,10 +57,6 @@ void ln_fwd_kernel(const float* __restrict__ x, const int* __restrict__ rowidx, 
 //     per workgroup: ~250 x 4 x C atomics per launch instead of ~900 x 4 x C (the old 4-wave blocks), 8 adders per
 //     replica address instead of 28 -- same-address float atomics run at a fraction of the streaming rate
 //     (MI355X_MICROARCH.md, Global float atomics), and they were a large part of this kernel's 108 us.
-struct LsNext {
-    const bf16* y; const float* gamma; const float* rowscale; bf16* dy; float* dgamma; float* dbias; int tokens;
-    const int* pos = nullptr;      // row-list kernel only: dy is COMPACT by this sample map (drop-path sample list of the branch), -1 = dropped
-};
 #define LNB_WAVES 8
 
 template <int NV, bool LS>
@@ -103,36 +64,62 @@ struct LnbRow {                      // operands of one row, as loaded
     float4 x[NV], dres[NV];
     bf16x4 dy[NV], y[LS ? NV : 1];
     float mean, rstd, dp;
-    int xr, yr;                      // residual-stream row; row of dy_next (-1: its branch dropped the sample)
+    int xr;                          // residual-stream row
+    int ar;                          // row of dy / mean / rstd (-1: the LayerNorm's own branch dropped the sample, dres passes through)
+    int yr;                          // row of dy_next (-1: its branch dropped the sample)
 };
 
-template <int NV, bool LS>
-__device__ __forceinline__ void lnb_load(LnbRow<NV, LS>& r, int row, const bf16* dy, const float* x, const int* rowidx,
+template <int NV, LnWalk WALK, bool LS>
+__device__ __forceinline__ void lnb_load(LnbRow<NV, LS>& r, int row, const bf16* dy, const float* x, const int* map,
                                          const float* mean_i, const float* rstd_i, const float* dres, const LsNext& ls,
                                          int C, int nv, int lane) {
-    const int xr = rowidx ? rowidx[row] : row;
-    r.xr = xr;
-    r.mean = mean_i[row]; r.rstd = rstd_i[row];
-    r.dp = 1.0f; r.yr = xr;
-    if constexpr (LS) {
-        if (ls.rowscale) r.dp = ls.rowscale[xr / ls.tokens];
-        if (ls.pos) { const int smp = xr / ls.tokens, sl = ls.pos[smp]; r.yr = sl < 0 ? -1 : sl * ls.tokens + (xr - smp * ls.tokens); }
+    const int tokens = ls.tokens;
+    r.dp = 1.0f;
+    if constexpr (WALK == WALK_ROWS) {
+        const int xr = map ? map[row] : row;
+        r.xr = xr; r.ar = row; r.yr = xr;
+        r.mean = mean_i[row]; r.rstd = rstd_i[row];
+        if constexpr (LS) {
+            if (ls.rowscale) r.dp = ls.rowscale[xr / tokens];
+            if (ls.pos) { const int smp = xr / tokens, sl = ls.pos[smp]; r.yr = sl < 0 ? -1 : sl * tokens + (xr - smp * tokens); }
+        }
+    } else {
+        const int smp = row / tokens, t = row - smp * tokens;
+        const int sa = map ? map[smp] : smp, sb = LS ? (ls.pos ? ls.pos[smp] : smp) : -1;
+        r.xr = row;
+        r.ar = sa < 0 ? -1 : sa * tokens + t;
+        r.yr = sb < 0 ? -1 : sb * tokens + t;
+        r.mean = 0.f; r.rstd = 0.f;
+        if (r.ar >= 0) { r.mean = mean_i[r.ar]; r.rstd = rstd_i[r.ar]; }
+        if (r.yr >= 0 && ls.rowscale) r.dp = ls.rowscale[smp];
     }
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         const int i = lane + 64 * k;
         if (i < nv) {
-            r.x[k] = ((const float4*)(x + (size_t)xr * C))[i];
-            r.dy[k] = ((const bf16x4*)(dy + (size_t)row * C))[i];
-            r.dres[k] = dres ? ((const float4*)(dres + (size_t)xr * C))[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (LS) r.y[k] = ((const bf16x4*)(ls.y + (size_t)xr * C))[i];
+            if (WALK == WALK_ROWS || r.ar >= 0) {
+                r.x[k] = ((const float4*)(x + (size_t)r.xr * C))[i];
+                r.dy[k] = ((const bf16x4*)(dy + (size_t)r.ar * C))[i];
+            }
+            r.dres[k] = WALK == WALK_SAMPLES || dres ? ((const float4*)(dres + (size_t)r.xr * C))[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (LS) if (WALK == WALK_ROWS || r.yr >= 0) r.y[k] = ((const bf16x4*)(ls.y + (size_t)r.xr * C))[i];
         }
     }
 }
 
-template <int NV, bool LS>
+// samples walk: the pad rows of dy_next (and of pad2) <- 0, see LsNext
+template <int NV>
+__device__ __forceinline__ void lnb_pad_fill(const LsNext& ls, int C, int nv, int lane, int wave) {
+    const int n = *ls.cnt, npad = ((ls.pad_base + n + 63) & ~63) - ls.pad_base;
+    for (int r = n + wave; r < npad; r += LNB_WAVES) {
+        store_zero_row<NV>(ls.dy + (size_t)r * C, nv, lane);
+        if (ls.pad2) for (int c = lane * 4; c < ls.pad2_cols; c += 256) *(bf16x4*)(ls.pad2 + (size_t)r * ls.pad2_cols + c) = bf16x4_zero();
+    }
+}
+
+template <int NV, LnWalk WALK, bool LS>
 __global__ __launch_bounds__(LNB_WAVES * 64)
-void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, const int* __restrict__ rowidx,
+void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, const int* __restrict__ map /* rowidx | pos */,
                    const int* __restrict__ count, const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
                    const float* __restrict__ w, const float* __restrict__ dres, float* __restrict__ dx,
                    float* __restrict__ dw, float* __restrict__ db, int M, int C, int nrep, size_t rep_stride, LsNext ls,
@@ -140,7 +127,9 @@ void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, con
     __shared__ float red[LNB_WAVES][64 * 4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nv = C >> 2;
-    const int n_valid = count ? min(*count, M) : M;
+    int n_valid = M;
+    if constexpr (WALK == WALK_ROWS) { if (count) n_valid = min(*count, M); }
+    if constexpr (WALK == WALK_SAMPLES && LS) { if (ls.cnt && blockIdx.x == gridDim.x - 1) lnb_pad_fill<NV>(ls, C, nv, lane, wave); }
     float4 ww[NV], gm[LS ? NV : 1];
     RowVec<NV> aw, ab;
     RowVec<LS ? NV : 1> ag, ay;
@@ -157,45 +146,42 @@ void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, con
     const int row_end = min((int)(blockIdx.x + 1) * rows_per_block, n_valid);
     int row = blockIdx.x * rows_per_block + wave;
     LnbRow<NV, LS> cur, nxt;
-    if (row < row_end) lnb_load<NV, LS>(cur, row, dy, x, rowidx, mean_i, rstd_i, dres, ls, C, nv, lane);
+    if (row < row_end) lnb_load<NV, WALK, LS>(cur, row, dy, x, map, mean_i, rstd_i, dres, ls, C, nv, lane);
     for (; row < row_end; row += LNB_WAVES) {
         const bool more = row + LNB_WAVES < row_end;
-        if (more) lnb_load<NV, LS>(nxt, row + LNB_WAVES, dy, x, rowidx, mean_i, rstd_i, dres, ls, C, nv, lane);
+        if (more) lnb_load<NV, WALK, LS>(nxt, row + LNB_WAVES, dy, x, map, mean_i, rstd_i, dres, ls, C, nv, lane);
+        const bool own = WALK == WALK_ROWS || cur.ar >= 0;      // false: the row passes dres through
         const float mean = cur.mean, rstd = cur.rstd;
         float4 g[NV], h[NV];
         float s1 = 0.f, s2 = 0.f;
+        if (own) {
 #pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            if (lane + 64 * k < nv) {
-                const float d0 = bf2f(cur.dy[k][0]), d1 = bf2f(cur.dy[k][1]), d2 = bf2f(cur.dy[k][2]), d3 = bf2f(cur.dy[k][3]);
-                h[k] = make_float4((cur.x[k].x - mean) * rstd, (cur.x[k].y - mean) * rstd, (cur.x[k].z - mean) * rstd,
-                                   (cur.x[k].w - mean) * rstd);
-                aw.v[k].x += d0 * h[k].x; aw.v[k].y += d1 * h[k].y; aw.v[k].z += d2 * h[k].z; aw.v[k].w += d3 * h[k].w;
-                ab.v[k].x += d0; ab.v[k].y += d1; ab.v[k].z += d2; ab.v[k].w += d3;
-                g[k] = make_float4(d0 * ww[k].x, d1 * ww[k].y, d2 * ww[k].z, d3 * ww[k].w);
-                s1 += g[k].x + g[k].y + g[k].z + g[k].w;
-                s2 += g[k].x * h[k].x + g[k].y * h[k].y + g[k].z * h[k].z + g[k].w * h[k].w;
-            } else {
-                g[k] = make_float4(0.f, 0.f, 0.f, 0.f); h[k] = g[k];
+            for (int k = 0; k < NV; ++k) {
+                if (lane + 64 * k < nv) {
+                    const float d0 = bf2f(cur.dy[k][0]), d1 = bf2f(cur.dy[k][1]), d2 = bf2f(cur.dy[k][2]), d3 = bf2f(cur.dy[k][3]);
+                    h[k] = normalize4(cur.x[k], mean, rstd);
+                    aw.v[k].x += d0 * h[k].x; aw.v[k].y += d1 * h[k].y; aw.v[k].z += d2 * h[k].z; aw.v[k].w += d3 * h[k].w;
+                    ab.v[k].x += d0; ab.v[k].y += d1; ab.v[k].z += d2; ab.v[k].w += d3;
+                    g[k] = make_float4(d0 * ww[k].x, d1 * ww[k].y, d2 * ww[k].z, d3 * ww[k].w);
+                    s1 += g[k].x + g[k].y + g[k].z + g[k].w;
+                    s2 += g[k].x * h[k].x + g[k].y * h[k].y + g[k].z * h[k].z + g[k].w * h[k].w;
+                } else {
+                    g[k] = make_float4(0.f, 0.f, 0.f, 0.f); h[k] = g[k];
+                }
             }
+            s1 = wave_sum(s1) / C;
+            s2 = wave_sum(s2) / C;
         }
-        s1 = wave_sum(s1) / C;
-        s2 = wave_sum(s2) / C;
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
             const int i = lane + 64 * k;
             if (i < nv) {
-                const float4 o = make_float4(cur.dres[k].x + rstd * (g[k].x - s1 - h[k].x * s2), cur.dres[k].y + rstd * (g[k].y - s1 - h[k].y * s2),
-                                             cur.dres[k].z + rstd * (g[k].z - s1 - h[k].z * s2), cur.dres[k].w + rstd * (g[k].w - s1 - h[k].w * s2));
+                float4 o = cur.dres[k];
+                if (own) o = make_float4(o.x + rstd * (g[k].x - s1 - h[k].x * s2), o.y + rstd * (g[k].y - s1 - h[k].y * s2),
+                                         o.z + rstd * (g[k].z - s1 - h[k].z * s2), o.w + rstd * (g[k].w - s1 - h[k].w * s2));
                 ((float4*)(dx + (size_t)cur.xr * C))[i] = o;
-                if constexpr (LS) if (cur.yr >= 0) {
-                    const float e0 = o.x * cur.dp, e1 = o.y * cur.dp, e2 = o.z * cur.dp, e3 = o.w * cur.dp;
-                    ag.v[k].x += e0 * bf2f(cur.y[k][0]); ag.v[k].y += e1 * bf2f(cur.y[k][1]);
-                    ag.v[k].z += e2 * bf2f(cur.y[k][2]); ag.v[k].w += e3 * bf2f(cur.y[k][3]);
-                    const bf16x4 ob = {f2bf(e0 * gm[k].x), f2bf(e1 * gm[k].y), f2bf(e2 * gm[k].z), f2bf(e3 * gm[k].w)};
-                    ((bf16x4*)(ls.dy + (size_t)cur.yr * C))[i] = ob;
-                    ay.v[k].x += bf2f(ob[0]); ay.v[k].y += bf2f(ob[1]); ay.v[k].z += bf2f(ob[2]); ay.v[k].w += bf2f(ob[3]);
-                }
+                if constexpr (LS) if (cur.yr >= 0)
+                    ls_apply(o, cur.dp, cur.y[k], gm[k], (bf16x4*)(ls.dy + (size_t)cur.yr * C) + i, ag.v[k], ay.v[k]);
             }
         }
         if (more) cur = nxt;
@@ -227,187 +213,6 @@ void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, con
     }
 }
 
-// ---- drop-path sample lists (round 4): the same two kernels over a DENSE walk of the residual stream with COMPACT branch buffers ----
-// pos[b] = compact slot of sample b, -1 when the branch dropped it.  Forward: a kept row is normalised into compact row slot * tokens + t;
-// a dropped row is copied to the branch's output stream (x + 0 * branch = x), which the residual epilogue of the branch's last GEMM then
-// does not touch.
-template <int NV>
-__global__ __launch_bounds__(LN_WAVES * 64)
-void ln_fwd_keep_kernel(const float* __restrict__ x, const int* __restrict__ pos, const float* __restrict__ w,
-                        const float* __restrict__ b, bf16* __restrict__ y, float* __restrict__ mean_o, float* __restrict__ rstd_o,
-                        float* __restrict__ xcopy, int M, int C, float eps, int tokens) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * LN_WAVES + (threadIdx.x >> 6);
-    if (row >= M) return;
-    const int nv = C >> 2;
-    const int smp = row / tokens, slot = pos[smp];
-    RowVec<NV> r;
-    load_row(r, x + (size_t)row * C, C, lane);
-    if (slot < 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) if (lane + 64 * k < nv) ((float4*)(xcopy + (size_t)row * C))[lane + 64 * k] = r.v[k];
-        return;
-    }
-    const size_t crow = (size_t)slot * tokens + (row - smp * tokens);
-    float mean, rstd;
-    row_stats(r, C, lane, eps, mean, rstd);
-    if (lane == 0) { mean_o[crow] = mean; rstd_o[crow] = rstd; }
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        if (i < nv) {
-            const float4 ww = ((const float4*)w)[i], bb = ((const float4*)b)[i];
-            bf16x4 o = {f2bf((r.v[k].x - mean) * rstd * ww.x + bb.x), f2bf((r.v[k].y - mean) * rstd * ww.y + bb.y),
-                        f2bf((r.v[k].z - mean) * rstd * ww.z + bb.z), f2bf((r.v[k].w - mean) * rstd * ww.w + bb.w)};
-            ((bf16x4*)(y + crow * C))[i] = o;
-        }
-    }
-}
-
-// Backward: rows are walked densely.  posA maps the sample to the compact slot of the LayerNorm's own branch (dy, mean, rstd compact;
-// nullptr = every sample kept, dense): a dropped sample's row passes dres through (dx = dres) and adds nothing to dw / db.  posB maps it
-// to the slot of the branch whose LayerScale backward rides along (dy_next compact, y_next dense-indexed; nullptr = dense; ls.dy ==
-// nullptr: no such branch): a dropped sample writes nothing and adds nothing to dgamma / dbias.  The pad rows of dy_next (cntB .. next
-// multiple of 64 of pad_base + cntB: the wgrad's reduction length; pad_base = rows in front of dy_next in a stacked buffer) are zero-filled
-// by the last workgroup when cntB is given.
-template <int NV>
-struct LnkRow {
-    float4 x[NV], dres[NV];
-    bf16x4 dy[NV], y[NV];
-    float mean, rstd, dp;
-    int ca, cb;                     // compact rows of the two branches, -1 = dropped
-};
-
-template <int NV>
-__device__ __forceinline__ void lnk_load(LnkRow<NV>& r, int row, const bf16* dy, const float* x, const int* posA, const int* posB,
-                                         const float* mean_i, const float* rstd_i, const float* dres, const LsNext& ls,
-                                         int C, int nv, int lane) {
-    const int smp = row / ls.tokens, t = row - smp * ls.tokens;
-    const int sa = posA ? posA[smp] : smp, sb = ls.dy ? (posB ? posB[smp] : smp) : -1;
-    r.ca = sa < 0 ? -1 : sa * ls.tokens + t;
-    r.cb = sb < 0 ? -1 : sb * ls.tokens + t;
-    r.mean = 0.f; r.rstd = 0.f; r.dp = 1.0f;
-    if (r.ca >= 0) { r.mean = mean_i[r.ca]; r.rstd = rstd_i[r.ca]; }
-    if (r.cb >= 0 && ls.rowscale) r.dp = ls.rowscale[smp];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        if (i < nv) {
-            r.dres[k] = ((const float4*)(dres + (size_t)row * C))[i];
-            if (r.ca >= 0) {
-                r.x[k] = ((const float4*)(x + (size_t)row * C))[i];
-                r.dy[k] = ((const bf16x4*)(dy + (size_t)r.ca * C))[i];
-            }
-            if (r.cb >= 0) r.y[k] = ((const bf16x4*)(ls.y + (size_t)row * C))[i];
-        }
-    }
-}
-
-template <int NV>
-__global__ __launch_bounds__(LNB_WAVES * 64)
-void ln_bwd_keep_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, const int* __restrict__ posA,
-                        const int* __restrict__ posB, const int* __restrict__ cntB, const float* __restrict__ mean_i,
-                        const float* __restrict__ rstd_i, const float* __restrict__ w, const float* __restrict__ dres,
-                        float* __restrict__ dx, float* __restrict__ dw, float* __restrict__ db, int M, int C, int nrep,
-                        size_t rep_stride, LsNext ls, int rows_per_block, int pad_base, bf16* __restrict__ pad2, int pad2_cols) {
-    __shared__ float red[LNB_WAVES][64 * 4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nv = C >> 2;
-    if (ls.dy && cntB && blockIdx.x == gridDim.x - 1) {
-        const int n = *cntB, npad = ((pad_base + n + 63) & ~63) - pad_base;
-        for (int r = n + wave; r < npad; r += LNB_WAVES) {
-#pragma unroll
-            for (int k = 0; k < NV; ++k)
-                if (lane + 64 * k < nv) ((bf16x4*)(ls.dy + (size_t)r * C))[lane + 64 * k] = bf16x4{f2bf(0.f), f2bf(0.f), f2bf(0.f), f2bf(0.f)};
-            // a second buffer with the same row list (the attention branch's dqkv, written by the attention backward for the kept samples only)
-            if (pad2) for (int c = lane * 4; c < pad2_cols; c += 256) *(bf16x4*)(pad2 + (size_t)r * pad2_cols + c) = bf16x4{f2bf(0.f), f2bf(0.f), f2bf(0.f), f2bf(0.f)};
-        }
-    }
-    float4 ww[NV], gm[NV];
-    RowVec<NV> aw, ab, ag, ay;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        aw.v[k] = make_float4(0.f, 0.f, 0.f, 0.f); ab.v[k] = aw.v[k]; ag.v[k] = aw.v[k]; ay.v[k] = aw.v[k]; gm[k] = aw.v[k];
-        ww[k] = lane + 64 * k < nv ? ((const float4*)w)[lane + 64 * k] : aw.v[k];
-        if (ls.dy && lane + 64 * k < nv) gm[k] = ((const float4*)ls.gamma)[lane + 64 * k];
-    }
-    const int row_end = min((int)(blockIdx.x + 1) * rows_per_block, M);
-    int row = blockIdx.x * rows_per_block + wave;
-    LnkRow<NV> cur, nxt;
-    if (row < row_end) lnk_load<NV>(cur, row, dy, x, posA, posB, mean_i, rstd_i, dres, ls, C, nv, lane);
-    for (; row < row_end; row += LNB_WAVES) {
-        const bool more = row + LNB_WAVES < row_end;
-        if (more) lnk_load<NV>(nxt, row + LNB_WAVES, dy, x, posA, posB, mean_i, rstd_i, dres, ls, C, nv, lane);
-        float4 o[NV];
-#pragma unroll
-        for (int k = 0; k < NV; ++k) o[k] = cur.dres[k];
-        if (cur.ca >= 0) {
-            const float mean = cur.mean, rstd = cur.rstd;
-            float4 g[NV], h[NV];
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) {
-                if (lane + 64 * k < nv) {
-                    const float d0 = bf2f(cur.dy[k][0]), d1 = bf2f(cur.dy[k][1]), d2 = bf2f(cur.dy[k][2]), d3 = bf2f(cur.dy[k][3]);
-                    h[k] = make_float4((cur.x[k].x - mean) * rstd, (cur.x[k].y - mean) * rstd, (cur.x[k].z - mean) * rstd,
-                                       (cur.x[k].w - mean) * rstd);
-                    aw.v[k].x += d0 * h[k].x; aw.v[k].y += d1 * h[k].y; aw.v[k].z += d2 * h[k].z; aw.v[k].w += d3 * h[k].w;
-                    ab.v[k].x += d0; ab.v[k].y += d1; ab.v[k].z += d2; ab.v[k].w += d3;
-                    g[k] = make_float4(d0 * ww[k].x, d1 * ww[k].y, d2 * ww[k].z, d3 * ww[k].w);
-                    s1 += g[k].x + g[k].y + g[k].z + g[k].w;
-                    s2 += g[k].x * h[k].x + g[k].y * h[k].y + g[k].z * h[k].z + g[k].w * h[k].w;
-                } else {
-                    g[k] = make_float4(0.f, 0.f, 0.f, 0.f); h[k] = g[k];
-                }
-            }
-            s1 = wave_sum(s1) / C;
-            s2 = wave_sum(s2) / C;
-#pragma unroll
-            for (int k = 0; k < NV; ++k)
-                o[k] = make_float4(cur.dres[k].x + rstd * (g[k].x - s1 - h[k].x * s2), cur.dres[k].y + rstd * (g[k].y - s1 - h[k].y * s2),
-                                   cur.dres[k].z + rstd * (g[k].z - s1 - h[k].z * s2), cur.dres[k].w + rstd * (g[k].w - s1 - h[k].w * s2));
-        }
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const int i = lane + 64 * k;
-            if (i < nv) {
-                ((float4*)(dx + (size_t)row * C))[i] = o[k];
-                if (cur.cb >= 0) {
-                    const float e0 = o[k].x * cur.dp, e1 = o[k].y * cur.dp, e2 = o[k].z * cur.dp, e3 = o[k].w * cur.dp;
-                    ag.v[k].x += e0 * bf2f(cur.y[k][0]); ag.v[k].y += e1 * bf2f(cur.y[k][1]);
-                    ag.v[k].z += e2 * bf2f(cur.y[k][2]); ag.v[k].w += e3 * bf2f(cur.y[k][3]);
-                    const bf16x4 ob = {f2bf(e0 * gm[k].x), f2bf(e1 * gm[k].y), f2bf(e2 * gm[k].z), f2bf(e3 * gm[k].w)};
-                    ((bf16x4*)(ls.dy + (size_t)cur.cb * C))[i] = ob;
-                    ay.v[k].x += bf2f(ob[0]); ay.v[k].y += bf2f(ob[1]); ay.v[k].z += bf2f(ob[2]); ay.v[k].w += bf2f(ob[3]);
-                }
-            }
-        }
-        if (more) cur = nxt;
-    }
-    const size_t rep = (size_t)(blockIdx.x % nrep) * rep_stride;
-    auto fold = [&](const float4& part, float* dst, int k) {
-        __syncthreads();
-        ((float4*)red[wave])[lane] = part;
-        __syncthreads();
-        if (lane < 32) {
-            const int col = wave * 32 + lane;
-            float sum = 0.f;
-#pragma unroll
-            for (int q = 0; q < LNB_WAVES; ++q) sum += red[q][col];
-            const int c = 256 * k + col;
-            if (c < C) atomicAdd(dst + rep + c, sum);
-        }
-    };
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        if (64 * k < nv) {
-            fold(aw.v[k], dw, k);
-            fold(ab.v[k], db, k);
-            if (ls.dy) { fold(ag.v[k], ls.dgamma, k); fold(ay.v[k], ls.dbias, k); }
-        }
-    }
-}
-
 // acc[i] (+)= layer_norm(x[rowidx[i]] - sub[rowidx[i]])  (no affine; sub == nullptr: 0).  `sub` = the stream before the
 // MLP branch: x - sub is the block's `fc` output, the `--layer_results fc` target (modeling_cyclical.py:199-205).
 template <int NV>
@@ -435,16 +240,7 @@ void target_accum_kernel(const float* __restrict__ x, const float* __restrict__ 
     }
     float mean = 0.f, rstd = 1.f;
     if (ln) row_stats(r, C, lane, eps, mean, rstd);          // ln == 0 (--no_target_layer_norm_last): the rows are summed as they are
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        if (i < nv) {
-            float4 o = make_float4((r.v[k].x - mean) * rstd, (r.v[k].y - mean) * rstd, (r.v[k].z - mean) * rstd,
-                                   (r.v[k].w - mean) * rstd);
-            if (!first) { const float4 a = dst[i]; o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w; }
-            dst[i] = o;
-        }
-    }
+    normalize_store(r, mean, rstd, (float*)dst, !first, nv, lane);
 }
 
 template <int NV>
@@ -461,23 +257,8 @@ void target_finalize_kernel(float* __restrict__ acc, const int* __restrict__ cou
     for (int k = 0; k < NV; ++k) { r.v[k].x *= inv_layers; r.v[k].y *= inv_layers; r.v[k].z *= inv_layers; r.v[k].w *= inv_layers; }
     float mean = 0.f, rstd = 1.f;
     if (post_ln) row_stats(r, C, lane, eps, mean, rstd);
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        if (i < nv)
-            ((float4*)(acc + (size_t)row * C))[i] = make_float4((r.v[k].x - mean) * rstd, (r.v[k].y - mean) * rstd,
-                                                                 (r.v[k].z - mean) * rstd, (r.v[k].w - mean) * rstd);
-    }
+    normalize_store(r, mean, rstd, acc + (size_t)row * C, false, nv, lane);
 }
-
-#define LN_DISPATCH2(KERNEL, FLAG, C, ...) do { const int _nv = ((C) + 255) / 256; \
-    if (_nv <= 1) hipLaunchKernelGGL((KERNEL<1, FLAG>), __VA_ARGS__); else if (_nv == 2) hipLaunchKernelGGL((KERNEL<2, FLAG>), __VA_ARGS__); \
-    else if (_nv == 3) hipLaunchKernelGGL((KERNEL<3, FLAG>), __VA_ARGS__); else if (_nv == 4) hipLaunchKernelGGL((KERNEL<4, FLAG>), __VA_ARGS__); \
-    else if (_nv == 5) hipLaunchKernelGGL((KERNEL<5, FLAG>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<8, FLAG>), __VA_ARGS__); } while (0)
-#define LN_DISPATCH(KERNEL, C, ...) do { const int _nv = ((C) + 255) / 256; \
-    if (_nv <= 1) hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); else if (_nv == 2) hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); \
-    else if (_nv == 3) hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); else if (_nv == 4) hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); \
-    else if (_nv == 5) hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); else hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); } while (0)
 
 // Slabs per CU.  Round 3 tried 2 (512 workgroups that could rebalance when some CUs are held by RCCL channel workgroups): the step was
 // slower with all CUs (25.4 -> 25.7 ms) AND with 240 / 224 CUs masked in (28.2 -> 28.8, 28.7 -> 29.5 ms; tools/cu_mask_bench.sh), so 1 stays.
@@ -496,82 +277,54 @@ static int lnb_rows(int M, int resident_blocks_per_cu) {
     return rows < LNB_WAVES ? LNB_WAVES : rows;
 }
 
-static int ln_shape_ok(int M, int C) { return (M > 0 && C > 0 && (C % 4) == 0 && C <= LN_MAXV * 256) ? UVIT_OK : UVIT_ERR_SHAPE; }
+static int ln_shape_ok(int M, int C) { return (M > 0 && C > 0 && (C % 4) == 0 && C <= ROW_MAXV * 256) ? UVIT_OK : UVIT_ERR_SHAPE; }
+static dim3 ln_grid(int M) { return dim3((M + LN_WAVES - 1) / LN_WAVES); }      // one wave per row
 
-int uvit_ln_fwd_launch(const float* x, const float* w, const float* b, void* y, float* mean, float* rstd, int M, int C,
-                       float eps, hipStream_t s) {
-    if (ln_shape_ok(M, C)) return UVIT_ERR_SHAPE;
-    LN_DISPATCH(ln_fwd_kernel, C, dim3((M + LN_WAVES - 1) / LN_WAVES), dim3(LN_WAVES * 64), 0, s, x, (const int*)nullptr,
-                       (const int*)nullptr, w, b, (bf16*)y, mean, rstd, M, C, eps);
+int uvit_ln_fwd_launch(const LnFwd& p, hipStream_t s) {
+    const bool samples = p.pos || p.xcopy;
+    if (ln_shape_ok(p.M, p.C) || (samples && (p.rowidx || p.count))) return UVIT_ERR_SHAPE;
+    if (samples && (p.tokens <= 0 || (p.M % p.tokens) || !p.pos || !p.xcopy || !p.mean || !p.rstd)) return UVIT_ERR_SHAPE;
+    dispatch_nv(p.C, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((samples ? ln_fwd_kernel<NV, WALK_SAMPLES> : ln_fwd_kernel<NV, WALK_ROWS>), ln_grid(p.M), dim3(LN_WAVES * 64), 0, s,
+                           p.x, p.rowidx, p.count, p.pos, p.w, p.b, p.y, p.mean, p.rstd, p.xcopy, p.M, p.C, p.eps, p.tokens);
+    });
     return uvit_check_launch();
 }
-int uvit_ln_fwd_gather_launch(const float* x, const int* rowidx, const int* count, const float* w, const float* b,
-                              void* y, float* mean, float* rstd, int Mmax, int C, float eps, hipStream_t s) {
-    if (ln_shape_ok(Mmax, C)) return UVIT_ERR_SHAPE;
-    LN_DISPATCH(ln_fwd_kernel, C, dim3((Mmax + LN_WAVES - 1) / LN_WAVES), dim3(LN_WAVES * 64), 0, s, x, rowidx, count,
-                       w, b, (bf16*)y, mean, rstd, Mmax, C, eps);
-    return uvit_check_launch();
-}
-int uvit_ln_bwd_launch(const void* dy, const float* x, const float* mean, const float* rstd, const float* w,
-                       const float* dres, float* dx, float* dw, float* db, int M, int C, int nrep, size_t rep_stride, hipStream_t s) {
-    if (ln_shape_ok(M, C)) return UVIT_ERR_SHAPE;
-    const int rpb = lnb_rows(M, LNB_BLOCKS_PER_CU);
-    LN_DISPATCH2(ln_bwd_kernel, false, C, dim3((M + rpb - 1) / rpb), dim3(LNB_WAVES * 64), 0, s, (const bf16*)dy, x,
-                       (const int*)nullptr, (const int*)nullptr, mean, rstd, w, dres, dx, dw, db, M, C, nrep > 0 ? nrep : 1, rep_stride, LsNext{}, rpb);
-    return uvit_check_launch();
-}
-int uvit_ln_bwd_ls_launch(const void* dy, const float* x, const float* mean, const float* rstd, const float* w,
-                          const float* dres, float* dx, float* dw, float* db, const void* y_next, const float* gamma_next,
-                          const float* rowscale_next, void* dy_next, float* dgamma_next, float* dbias_next, int tokens,
-                          int M, int C, int nrep, size_t rep_stride, hipStream_t s, const int* rowidx, const int* count, const int* pos_next) {
-    if (ln_shape_ok(M, C) || tokens <= 0 || (rowidx && !count)) return UVIT_ERR_SHAPE;
-    const LsNext ls{(const bf16*)y_next, gamma_next, rowscale_next, (bf16*)dy_next, dgamma_next, dbias_next, tokens, pos_next};
-    const int rpb = lnb_rows(M, LNB_BLOCKS_PER_CU);
-    LN_DISPATCH2(ln_bwd_kernel, true, C, dim3((M + rpb - 1) / rpb), dim3(LNB_WAVES * 64), 0, s, (const bf16*)dy, x,
-                       rowidx, count, mean, rstd, w, dres, dx, dw, db, M, C, nrep > 0 ? nrep : 1, rep_stride, ls, rpb);
-    return uvit_check_launch();
-}
-int uvit_ln_fwd_keep_launch(const float* x, const int* pos, const float* w, const float* b, void* y, float* mean, float* rstd,
-                            float* xcopy, int M, int C, int tokens, float eps, hipStream_t s) {
-    if (ln_shape_ok(M, C) || tokens <= 0 || (M % tokens) || !pos || !xcopy || !mean || !rstd) return UVIT_ERR_SHAPE;
-    LN_DISPATCH(ln_fwd_keep_kernel, C, dim3((M + LN_WAVES - 1) / LN_WAVES), dim3(LN_WAVES * 64), 0, s, x, pos, w, b, (bf16*)y, mean, rstd,
-                       xcopy, M, C, eps, tokens);
-    return uvit_check_launch();
-}
-int uvit_ln_bwd_keep_launch(const void* dy, const float* x, const int* posA, const float* mean, const float* rstd, const float* w,
-                            const float* dres, float* dx, float* dw, float* db, const void* y_next, const float* gamma_next,
-                            const float* rowscale_next, void* dy_next, float* dgamma_next, float* dbias_next, const int* posB,
-                            const int* cntB, int tokens, int M, int C, int nrep, size_t rep_stride, hipStream_t s, int pad_base,
-                            void* pad2, int pad2_cols) {
-    if (ln_shape_ok(M, C) || tokens <= 0 || (M % tokens) || !dres || ((posB || cntB) && !dy_next) || pad_base < 0 ||
-        (pad2 && (!cntB || pad2_cols <= 0 || (pad2_cols % 4)))) return UVIT_ERR_SHAPE;
-    const LsNext ls{(const bf16*)y_next, gamma_next, rowscale_next, (bf16*)dy_next, dgamma_next, dbias_next, tokens};
-    const int rpb = lnb_rows(M, LNB_BLOCKS_PER_CU);
-    LN_DISPATCH(ln_bwd_keep_kernel, C, dim3((M + rpb - 1) / rpb), dim3(LNB_WAVES * 64), 0, s, (const bf16*)dy, x, posA, posB, cntB, mean, rstd,
-                       w, dres, dx, dw, db, M, C, nrep > 0 ? nrep : 1, rep_stride, ls, rpb, pad_base, (bf16*)pad2, pad2_cols);
-    return uvit_check_launch();
-}
-int uvit_ln_bwd_scatter_launch(const void* dy, const float* x, const int* rowidx, const int* count, const float* mean,
-                               const float* rstd, const float* w, float* dx, float* dw, float* db, int Mmax, int C,
-                               int nrep, size_t rep_stride, hipStream_t s) {
-    if (ln_shape_ok(Mmax, C)) return UVIT_ERR_SHAPE;
-    const int rpb = lnb_rows(Mmax, 1);
-    LN_DISPATCH2(ln_bwd_kernel, false, C, dim3((Mmax + rpb - 1) / rpb), dim3(LNB_WAVES * 64), 0, s, (const bf16*)dy, x,
-                       rowidx, count, mean, rstd, w, (const float*)nullptr, dx, dw, db, Mmax, C, nrep > 0 ? nrep : 1, rep_stride, LsNext{}, rpb);
+int uvit_ln_bwd_launch(const LnBwd& p, hipStream_t s) {
+    const LsNext& n = p.next;
+    const bool ls = n.dy != nullptr, samples = p.pos || n.cnt || (n.pos && !p.rowidx);
+    if (ln_shape_ok(p.M, p.C) || (p.rowidx && !p.count) || (samples && (p.rowidx || p.count))) return UVIT_ERR_SHAPE;
+    if ((ls || samples) && n.tokens <= 0) return UVIT_ERR_SHAPE;
+    if (samples && ((p.M % n.tokens) || !p.dres)) return UVIT_ERR_SHAPE;
+    if (((n.pos || n.cnt) && !ls) || n.pad_base < 0 || (n.pad2 && (!n.cnt || n.pad2_cols <= 0 || (n.pad2_cols % 4)))) return UVIT_ERR_SHAPE;
+    const int rpb = lnb_rows(p.M, LNB_BLOCKS_PER_CU);
+    dispatch_nv(p.C, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        // samples walk: LS is instantiated both ways, like the rows walk (the parent tested ls.dy at run time there)
+        auto kernel = samples ? (ls ? ln_bwd_kernel<NV, WALK_SAMPLES, true> : ln_bwd_kernel<NV, WALK_SAMPLES, false>)
+                              : (ls ? ln_bwd_kernel<NV, WALK_ROWS, true> : ln_bwd_kernel<NV, WALK_ROWS, false>);
+        hipLaunchKernelGGL(kernel, dim3((p.M + rpb - 1) / rpb), dim3(LNB_WAVES * 64), 0, s, p.dy, p.x, samples ? p.pos : p.rowidx, p.count,
+                           p.mean, p.rstd, p.w, p.dres, p.dx, p.dw, p.db, p.M, p.C, p.nrep > 0 ? p.nrep : 1, p.rep_stride, n, rpb);
+    });
     return uvit_check_launch();
 }
 int uvit_target_accum_launch(const float* x, const int* rowidx, const int* count, float* acc, int first, int Mmax,
                              int C, float eps, hipStream_t s, const float* sub, int ln) {
     if (ln_shape_ok(Mmax, C)) return UVIT_ERR_SHAPE;
-    LN_DISPATCH(target_accum_kernel, C, dim3((Mmax + LN_WAVES - 1) / LN_WAVES), dim3(LN_WAVES * 64), 0, s, x, sub, rowidx,
-                       count, acc, first, Mmax, C, eps, ln);
+    dispatch_nv(C, [&](auto nv) {
+        hipLaunchKernelGGL(target_accum_kernel<decltype(nv)::value>, ln_grid(Mmax), dim3(LN_WAVES * 64), 0, s, x, sub, rowidx, count, acc, first,
+                           Mmax, C, eps, ln);
+    });
     return uvit_check_launch();
 }
 int uvit_target_finalize_launch(float* acc, const int* count, int n_layers, int post_ln, int Mmax, int C, float eps,
                                 hipStream_t s) {
     if (ln_shape_ok(Mmax, C) || n_layers <= 0) return UVIT_ERR_SHAPE;
-    LN_DISPATCH(target_finalize_kernel, C, dim3((Mmax + LN_WAVES - 1) / LN_WAVES), dim3(LN_WAVES * 64), 0, s, acc,
-                       count, 1.0f / n_layers, post_ln, Mmax, C, eps);
+    dispatch_nv(C, [&](auto nv) {
+        hipLaunchKernelGGL(target_finalize_kernel<decltype(nv)::value>, ln_grid(Mmax), dim3(LN_WAVES * 64), 0, s, acc, count, 1.0f / n_layers,
+                           post_ln, Mmax, C, eps);
+    });
     return uvit_check_launch();
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "common.h"
 
 enum { EPI_BF16 = 0, EPI_QKV = 1, EPI_GELU = 2, EPI_RESID = 3, EPI_F32 = 4, EPI_PATCH = 5, EPI_DGELU = 6, EPI_QKV_ELU = 7,
        EPI_GELU_DG = 8,    // out = gelu(h), out2 = gelu'(h) (bf16): what backward needs of h, computed beside gelu (shared erf / exp)
@@ -98,31 +99,68 @@ int uvit_attn2_bwd_launch(const void* qkv_m, const void* qkv_c, const void* o_m,
 int uvit_attn2_dbias_reduce_launch(const void* ds_ws, float* dbias_slab, int accumulate, int B, int H, int N, int NP, hipStream_t s);
 
 // norm.hip
-int uvit_ln_fwd_launch(const float* x, const float* w, const float* b, void* y_bf16, float* mean, float* rstd,
-                       int M, int C, float eps, hipStream_t s);
-int uvit_ln_fwd_gather_launch(const float* x, const int* rowidx, const int* count, const float* w, const float* b,
-                              void* y_bf16, float* mean, float* rstd, int Mmax, int C, float eps, hipStream_t s);
-int uvit_ln_bwd_launch(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* w,
-                       const float* dres, float* dx, float* dw, float* db, int M, int C, int nrep, size_t rep_stride,
-                       hipStream_t s);
-// drop-path sample lists (norm.hip): dense walk of the residual stream, compact branch buffers
-int uvit_ln_fwd_keep_launch(const float* x, const int* pos, const float* w, const float* b, void* y, float* mean, float* rstd,
-                            float* xcopy, int M, int C, int tokens, float eps, hipStream_t s);
-int uvit_ln_bwd_keep_launch(const void* dy, const float* x, const int* posA, const float* mean, const float* rstd, const float* w,
-                            const float* dres, float* dx, float* dw, float* db, const void* y_next, const float* gamma_next,
-                            const float* rowscale_next, void* dy_next, float* dgamma_next, float* dbias_next, const int* posB,
-                            const int* cntB, int tokens, int M, int C, int nrep, size_t rep_stride, hipStream_t s, int pad_base = 0,
-                            void* pad2 = nullptr, int pad2_cols = 0);     // pad2: a second bf16 buffer [rows][pad2_cols] whose pad rows (same range) are zero-filled
-// LayerNorm backward fused with the LayerScale + DropPath backward of the branch that consumes dx next
-int uvit_ln_bwd_ls_launch(const void* dy, const float* x, const float* mean, const float* rstd, const float* w,
-                          const float* dres, float* dx, float* dw, float* db, const void* y_next, const float* gamma_next,
-                          const float* rowscale_next, void* dy_next, float* dgamma_next, float* dbias_next, int tokens,
-                          int M, int C, int nrep, size_t rep_stride, hipStream_t s,
-                          const int* rowidx = nullptr, const int* count = nullptr,    // row list: dy / mean / rstd are compact, everything else lives at rowidx[row]
-                          const int* pos_next = nullptr);                              // (row list only) dy_next compact by this sample map
-int uvit_ln_bwd_scatter_launch(const void* dy_bf16, const float* x, const int* rowidx, const int* count,
-                               const float* mean, const float* rstd, const float* w, float* dx, float* dw, float* db,
-                               int Mmax, int C, int nrep, size_t rep_stride, hipStream_t s);
+// LayerNorm forward, y = bf16((x - mean) * rstd * w + b), one wave per row.  The walk follows from the fields that are set:
+//   rows     (default) y / mean / rstd row r <- x row rowidx[r] (null: r); rows r >= *count (null: M) are padding and get zeros;
+//   samples  (pos) dense walk of x with a COMPACT y: sample b's rows go to slot pos[b] of y / mean / rstd, a dropped sample's (pos[b] < 0)
+//            rows are copied to xcopy -- the branch's output stream, x + 0 * branch, which its residual epilogue then does not touch.
+struct LnFwd {
+    const float* x = nullptr;        // [.., C] f32 residual stream
+    const float* w = nullptr;        // [C]
+    const float* b = nullptr;        // [C]
+    bf16* y = nullptr;               // [M, C] (samples: compact)
+    float* mean = nullptr;           // [M] saved statistics, indexed like y (rows walk: both nullable)
+    float* rstd = nullptr;
+    int M = 0, C = 0;                // rows walked
+    float eps = 0.f;
+    const int* rowidx = nullptr;     // rows walk
+    const int* count = nullptr;
+    const int* pos = nullptr;        // samples walk: [M / tokens]
+    float* xcopy = nullptr;          // samples walk: [M, C]
+    int tokens = 0;                  // samples walk: rows per sample
+};
+int uvit_ln_fwd_launch(const LnFwd& p, hipStream_t s);
+
+// The branch whose LayerScale + DropPath backward rides along in a row-wise backward pass over the residual-stream gradient d
+// (modeling_finetune.py:295-298): with e = d * rowscale[sample]:  dy = bf16(e * gamma),  dgamma += e * y,  dbias += dy.
+struct LsNext {
+    const bf16* y = nullptr;         // branch output before gamma, dense-indexed
+    const float* gamma = nullptr;    // [C]
+    const float* rowscale = nullptr; // per-sample drop-path multiplier (null = 1)
+    bf16* dy = nullptr;              // null: no branch rides along
+    float* dgamma = nullptr;         // replicated column-sum accumulators
+    float* dbias = nullptr;
+    int tokens = 0;                  // rows per sample of the residual stream (a samples-walk LayerNorm backward reads it without a rider, too)
+    // LayerNorm backward only -- dy is COMPACT by the branch's drop-path sample list:
+    const int* pos = nullptr;        // sample -> compact slot, -1 = dropped: writes nothing, adds nothing (null: dense)
+    const int* cnt = nullptr;        // samples walk: kept rows; the last workgroup zero-fills the pad rows of dy, cnt .. the next multiple of 64 of
+    int pad_base = 0;                //   pad_base + cnt (the wgrad's reduction length; pad_base = rows in front of dy in a stacked buffer)
+    bf16* pad2 = nullptr;            //   and the same rows of a second buffer [rows][pad2_cols] (the attention branch's dqkv, which the attention
+    int pad2_cols = 0;               //   backward writes for the kept samples only)
+};
+// LayerNorm backward: dx = dres + rstd * (dy*w - mean(dy*w) - xhat * mean(dy*w*xhat));  dw += dy*xhat;  db += dy, with `next` fused on dx.
+//   rows     (default) dy / mean / rstd row r belongs to residual-stream row rowidx[r] (null: r), where x, dres, dx and next.y live; rows
+//            r >= *count are skipped (dx keeps what it held); next.dy is indexed like dx, or compact by next.pos;
+//   samples  (pos, next.cnt, or next.pos without a row list) dense walk of the residual stream: dy / mean / rstd compact by pos (null: every
+//            sample kept) -- a dropped sample's rows pass dres through (dx = dres) and add nothing to dw / db; next.dy compact by next.pos.
+struct LnBwd {
+    const bf16* dy = nullptr;
+    const float* x = nullptr;
+    const float* mean = nullptr;
+    const float* rstd = nullptr;
+    const float* w = nullptr;
+    const float* dres = nullptr;     // gradient already on the residual stream (rows walk: null = 0)
+    float* dx = nullptr;
+    float* dw = nullptr;             // replicated column-sum accumulators: workgroup g adds into replica g % nrep
+    float* db = nullptr;
+    int M = 0, C = 0;                // rows walked
+    int nrep = 1;
+    size_t rep_stride = 0;
+    const int* rowidx = nullptr;     // rows walk; a row list needs its count
+    const int* count = nullptr;
+    const int* pos = nullptr;        // samples walk
+    LsNext next;
+};
+int uvit_ln_bwd_launch(const LnBwd& p, hipStream_t s);
 int uvit_reduce_replicas_launch(const float* rep, float* out, size_t n, int nrep, size_t stride, hipStream_t s);
 int uvit_target_accum_launch(const float* x, const int* rowidx, const int* count, float* acc, int first, int Mmax,
                              int C, float eps, hipStream_t s, const float* sub = nullptr,     // sub: rows subtracted before the LayerNorm
@@ -144,9 +182,9 @@ int uvit_set_cls_launch(float* x, const float* cls, const float* pos, int B, int
 int uvit_relpos_gather_launch(const float* table, const int* index, float* biasP, int H, int N, int NP, hipStream_t s);
 int uvit_relpos_scatter_launch(const float* slab, int nslab, const int* index, float* dtable, int H, int N, int NP,
                                hipStream_t s);
-int uvit_ls_bwd_launch(const float* dx, const void* branch_bf16, const float* gamma, const float* rowscale,
-                       void* dy_bf16, float* dgamma, float* dbias, int M, int C, int tokens, int nrep, size_t rep_stride,
-                       hipStream_t s, const int* rowidx = nullptr, const int* count = nullptr);   // row list: dy is compact, dx / branch live at rowidx[row]
+// LayerScale + DropPath backward on its own (ls.pos / cnt / pad unused); row list: ls.dy is compact, dx / ls.y live at rowidx[row], rows >= *count get zeros
+int uvit_ls_bwd_launch(const float* dx, const LsNext& ls, int M, int C, int nrep, size_t rep_stride, hipStream_t s,
+                       const int* rowidx = nullptr, const int* count = nullptr);
 int uvit_rows_guard_launch(const int* count, int limit, float* loss, hipStream_t s);   // *count > limit: loss <- NaN (the step is then skipped like any non-finite one)
 int uvit_colsum_launch(const void* y_bf16, int ld, int col0, int ncols, int M, float* out, int nrep, size_t rep_stride,
                        hipStream_t s);
