@@ -366,6 +366,30 @@ int64_t uvit_op_augment_ws_bytes(const uvit_augment_desc* desc, int B, int S);  
 int uvit_op_augment_batch(const uint8_t* pixels, int64_t pixel_bytes, const uvit_augment_desc* desc, int B, int S, const float* mean,
                           const float* std, float* out, void* workspace, int64_t ws_bytes, uvit_stream stream);
 
+/* ---- linear probe on the frozen encoder (run_class_finetuning.py --linear_classifier): everything behind the last block ----
+ * All fp32, no float atomics (the same input gives the same bits on every run), no engine handle: x is the residual stream the
+ * encoder left in its workspace, uvit_engine_ws_ptr(e, "x", depth).  Every call checks its arguments before it touches the device:
+ * UVIT_ERR_ARG for a NULL pointer (or a smoothing outside [0, 1)), UVIT_ERR_SHAPE for a size outside the stated conditions. */
+/* feat[b] (B, C) = LayerNorm without affine (eps) of the mean over tokens 1..N-1 of x[b] (B, N, C): `fc_norm(x[:, 1:].mean(1))`,
+ * modeling_finetune.py:410-412,512-515.  C % 4 == 0, C <= 2048, N >= 2, B <= 65535 (both calls).  scratch: uvit_op_probe_pool_ws_bytes(B, N, C) bytes
+ * (< 0: the UVIT_ERR_* of the call); partial column sums per (sample, token slice), added in slice order. */
+int64_t uvit_op_probe_pool_ws_bytes(int B, int N, int C);
+int uvit_op_probe_pool_norm(const float* x, float* feat, float* scratch, int B, int N, int C, float eps, uvit_stream stream);
+/* logits (B, K) = feat (B, C) . W (K, C)^T + bias (K): the nn.Linear head, modeling_finetune.py:421,522.  K >= 1, C % 4 == 0. */
+int uvit_op_probe_logits(const float* feat, const float* W, const float* bias, float* logits, int B, int K, int C, uvit_stream stream);
+/* timm LabelSmoothingCrossEntropy (smoothing 0: nn.CrossEntropyLoss), run_class_finetuning.py:617-623, one wave per row:
+ *   row_loss[b] = (1 - s) (lse - z_y) + s (lse - mean_k z_k);  *loss_out = mean_b row_loss[b], summed by one wave in row order;
+ *   dlogits (nullable) = (softmax - (1 - s) onehot - s / K) / B, the gradient of *loss_out;
+ *   top1_top5 (nullable, ACCUMULATED int32[2]): [0] += 1 when z_y is the strict row maximum, [1] += 1 when fewer than five logits
+ *   are greater than z_y.
+ * A label outside [0, K) makes row_loss[b], *loss_out and the row of dlogits NaN; nothing is read at that label. */
+int uvit_op_probe_ce(const float* logits, const int64_t* labels, float smoothing, float* dlogits, float* row_loss, float* loss_out,
+                     int32_t* top1_top5, int B, int K, uvit_stream stream);
+/* dW (K, C) = dlogits (B, K)^T . feat (B, C), dbias (K) = column sums of dlogits.  Overwrites both; every element has one owner and
+ * its sum runs over b in ascending order.  The head arena of the update is [W (K C) | bias (K, padded to 4)] with n_decay = K C for
+ * uvit_op_adamw (head.weight decays, head.bias does not: optim_factory.py:58-97). */
+int uvit_op_probe_head_grad(const float* dlogits, const float* feat, float* dW, float* dbias, int B, int K, int C, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,166 @@
+#!/usr/bin/env python
+"""Linear probe of a pre-training checkpoint -- the reference's `run_class_finetuning.py --linear_classifier`, with its flag names,
+types and defaults where the flags exist there:
+
+    python run_linear_probe.py --model beit_base_patch16_224 --finetune ckpt/checkpoint-799.pth \\
+        --data_set image_folder --data_path data/train --eval_data_path data/val --nb_classes 1000 --output_dir probe/
+    python run_linear_probe.py --model beit_base_patch16_224 --finetune ckpt/checkpoint-799.pth --resume probe/probe-29.pth \\
+        --data_set image_folder --eval_data_path data/val --nb_classes 1000 --eval
+
+The encoder is frozen; the patch tokens of its last block (`--target_layer L`: of block L, the encoder is built with L + 1 blocks)
+are mean-pooled, normalised without affine and fed to one nn.Linear, the only thing that trains (uncertainty-vit_amd/linear_probe.py).
+`--finetune` is a checkpoint written by run_cyclical.py (utils.save_model); its `lm_head.*` and `mask_token` entries are loaded but
+never used.  Training reads `--data_path` with flip + RandomResizedCrop (augmentation level 3), evaluation reads `--eval_data_path`
+with resize + center crop (level 1), both augmented on the device.  Single GPU.
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from uncertainty_vit_amd import utils
+
+
+def get_args(argv=None):
+    p = argparse.ArgumentParser("linear probe on the frozen encoder", add_help=True)
+    a = p.add_argument
+    a("--batch_size", default=64, type=int)
+    a("--epochs", default=30, type=int)
+    a("--model", default="deit_base_patch16_224", type=str, metavar="MODEL")
+    a("--input_size", default=224, type=int)
+    a("--clip_grad", type=float, default=None, metavar="NORM")
+    a("--weight_decay", type=float, default=0.05)
+    a("--lr", type=float, default=5e-4, metavar="LR")
+    a("--min_lr", type=float, default=1e-6, metavar="LR")
+    a("--warmup_epochs", type=int, default=5, metavar="N")
+    a("--smoothing", type=float, default=0.1)
+    a("--finetune", default="", help="pre-training checkpoint to probe")
+    a("--model_key", default="model|module", type=str)
+    a("--model_prefix", default="", type=str)
+    a("--target_layer", default=-1, type=int, help="target output layer (0-based)")
+    a("--data_path", default="/datasets01/imagenet_full_size/061417/", type=str)
+    a("--eval_data_path", default=None, type=str)
+    a("--nb_classes", default=0, type=int)
+    a("--imagenet_default_mean_and_std", default=False, action="store_true")
+    a("--data_set", default="IMNET", choices=["CIFAR100", "CIFAR10", "IMNET", "image_folder", "tiny_IMNET"], type=str)
+    a("--output_dir", default="")
+    a("--seed", default=0, type=int)
+    a("--resume", default="", help="head checkpoint (probe-*.pth) to continue from or to evaluate")
+    a("--eval", action="store_true", help="Perform evaluation only")
+    a("--num_workers", default=0, type=int)
+    return p.parse_args(argv)
+
+
+def encoder_kwargs(checkpoint):
+    """Constructor options of the encoder a run_cyclical.py checkpoint was trained with (utils.save_model keeps its args)."""
+    a = checkpoint.get("args") if isinstance(checkpoint, dict) else None
+    return dict(use_shared_rel_pos_bias=getattr(a, "rel_pos_bias", True), use_abs_pos_emb=getattr(a, "abs_pos_emb", False),
+                init_values=getattr(a, "layer_scale_init_value", 0.1))
+
+
+def build_loader(args, encoder, root, aug_level, train):
+    from uncertainty_vit_amd.datasets import FOLDER_DATA_SETS, BEiTAugment, ImageFolderPretrain, collate_packed
+    if args.data_set not in FOLDER_DATA_SETS:
+        raise NotImplementedError(f"--data_set {args.data_set} needs torchvision's archive format; use an image folder")
+    aug = BEiTAugment(args.input_size, aug_level, "bicubic", args.imagenet_default_mean_and_std)
+    ds = ImageFolderPretrain(root, aug, encoder.patch_embed.patch_shape, 0)      # no masked patches: the probe's forward takes no mask
+    print(("Train" if train else "Eval") + " data = %s, %d images, %d classes" % (aug, len(ds), len(ds.classes)))
+    return torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=train, drop_last=train, num_workers=args.num_workers,
+                                       pin_memory=True, collate_fn=collate_packed), ds
+
+
+def save_probe(args, probe, epoch):
+    path = Path(args.output_dir) / f"probe-{epoch}.pth"
+    torch.save({"model": {k: v.cpu() for k, v in probe.state_dict().items()}, "optimizer": probe.optimizer_state_dict(), "epoch": epoch,
+                "args": vars(args)}, path)
+    return path
+
+
+def main(args):
+    from uncertainty_vit_amd.engine_for_cyclical import DevicePrefetcher
+    from uncertainty_vit_amd.linear_probe import LinearProbe, build_probe_encoder, load_encoder_checkpoint
+    print(args)
+    if not torch.cuda.is_available():
+        raise RuntimeError("the linear probe runs as HIP kernels: a GPU is required")
+    if args.nb_classes < 1:
+        raise ValueError("--nb_classes is required")
+    if not args.finetune:
+        raise ValueError("--finetune <pre-training checkpoint> is required")
+    device = torch.device("cuda")
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+
+    ckpt = torch.load(args.finetune, map_location="cpu", weights_only=False)
+    print("Load ckpt from %s" % args.finetune)
+    encoder = build_probe_encoder(args.model, args.target_layer, img_size=args.input_size, **encoder_kwargs(ckpt))
+    unused = load_encoder_checkpoint(encoder, ckpt, args.model_key, args.model_prefix)
+    print(f"encoder: {encoder.depth} blocks, {len(unused)} checkpoint entries not part of it")
+    encoder.to(device)
+    probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
+    print("Trainable weights: %s" % [n for n, _ in probe.named_parameters()])
+    start_epoch = 0
+    if args.resume:
+        st = torch.load(args.resume, map_location="cpu", weights_only=False)
+        probe.load_state_dict(st["model"])
+        probe.load_optimizer_state_dict(st["optimizer"])
+        start_epoch = int(st["epoch"]) + 1
+        print("Resume checkpoint %s" % args.resume)
+
+    eval_root = args.eval_data_path or args.data_path
+    loader_val, _ = build_loader(args, encoder, eval_root, 1, train=False)
+    if args.eval:
+        stats = probe.evaluate(DevicePrefetcher(loader_val, device))
+        print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
+        return stats
+    loader_train, _ = build_loader(args, encoder, args.data_path, 3, train=True)
+    steps_per_epoch = len(loader_train)
+    print("LR = %.8f" % args.lr)
+    print("Batch size = %d" % args.batch_size)
+    print("Number of training steps per epoch = %d" % steps_per_epoch)
+    lr_values = utils.cosine_scheduler(args.lr, args.min_lr, args.epochs, steps_per_epoch, warmup_epochs=args.warmup_epochs)
+
+    def publish(log, loss, gnorm):
+        loss, gnorm = loss.item(), gnorm.item()
+        if not (math.isfinite(loss) and math.isfinite(gnorm)):
+            # engine_for_finetuning.py:101-103.  The step was already enqueued: uvit_op_adamw saw the same values and left the head as
+            # it was, and nothing is saved after this point
+            print("Loss is {}, stopping training".format(loss))
+            sys.exit(1)
+        log.update(loss=loss, grad_norm=gnorm)
+
+    stats, t0 = None, time.time()
+    for epoch in range(start_epoch, args.epochs):
+        log = utils.MetricLogger(delimiter="  ")
+        seen = []
+        for i, ((images, _), labels) in enumerate(log.log_every(DevicePrefetcher(loader_train, device), 10, f"Epoch: [{epoch}]")):
+            lr = float(lr_values[epoch * steps_per_epoch + i])
+            loss, gnorm = probe.train_step(images, labels.to(device, non_blocking=True), lr, args.weight_decay, args.clip_grad)
+            seen.append((loss.clone(), gnorm.clone()))          # device scalars: read one step late, never in the step's way
+            if len(seen) > 1:
+                publish(log, *seen.pop(0))
+            log.update(lr=lr)
+        for l0, g0 in seen:
+            publish(log, l0, g0)
+        stats = probe.evaluate(DevicePrefetcher(loader_val, device))
+        print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f}")
+        print(f"Epoch {epoch}: loss: {log.loss.global_avg:.4f}  lr: {log.lr.value:.8f}  acc1: {stats['acc1']:.3f}  acc5: {stats['acc5']:.3f}")
+        if args.output_dir:
+            save_probe(args, probe, epoch)
+            with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
+                f.write(json.dumps({"epoch": epoch, "train_loss": log.loss.global_avg, "train_lr": log.lr.value,
+                                    **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5")}}) + "\n")
+    print("Training time %.0f s" % (time.time() - t0))
+    return stats
+
+
+if __name__ == "__main__":
+    opts = get_args()
+    if opts.output_dir:
+        Path(opts.output_dir).mkdir(parents=True, exist_ok=True)
+    main(opts)

@@ -18,6 +18,10 @@ done
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function \
     -c augment.hip -o obj/augment.o ) &
 pids+=($!)
+# probe.hip fixes the order of every fp32 sum (bit-identical runs, tile-wise summation of the head GEMM): no fast-math, which
+# would reassociate the tile sums back into one chain
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c probe.hip -o obj/probe.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

@@ -1,0 +1,253 @@
+"""Linear probe on the frozen encoder: the reference's `run_class_finetuning.py --linear_classifier`.
+
+    frozen encoder (eval forward, native) -> mean of the last block's patch tokens -> LayerNorm without affine
+    -> one nn.Linear -> (label-smoothing) cross-entropy          modeling_finetune.py:410-412,421,439-441,476-517
+
+Only `head.weight` / `head.bias` train (run_class_finetuning.py:529-538: every weight the checkpoint provides is frozen).
+Everything behind the last block runs as the HIP kernels of csrc/probe.hip on the stream of the encoder forward; the update is
+uvit_op_adamw on the head's own flat arena [W (K C) | bias (K, padded to 4)] whose decay group (head.weight) comes first.  No gradient
+ever reaches the encoder: its arenas and bf16 shadows are only read.  There is no eager fallback and no torch arithmetic on the
+step path; the one torch call there is the 8-byte fill that clears the gradient sum-of-squares before uvit_op_sumsq adds to it.
+"""
+import ctypes as C
+import math
+
+import torch
+import torch.nn as nn
+
+from . import native
+from .modeling_cyclical import VisionTransformerForCyclicalTraining, _Holder, create_model
+from .native import check, cur_stream, f32, lib, ptr
+
+__all__ = ["LinearProbe", "build_probe_encoder", "load_encoder_checkpoint"]
+
+
+def _timm_trunc_normal_(t, std):
+    """timm's trunc_normal_(t, std=std) as modeling_finetune.py:439 calls it: bounds a = -2, b = 2."""
+    lo = (1.0 + math.erf(-2.0 / std / math.sqrt(2.0))) / 2.0
+    hi = (1.0 + math.erf(2.0 / std / math.sqrt(2.0))) / 2.0
+    with torch.no_grad():
+        t.uniform_(2 * lo - 1, 2 * hi - 1).erfinv_().mul_(std * math.sqrt(2.0)).clamp_(-2.0, 2.0)
+    return t
+
+
+class LinearProbe(nn.Module):
+    """`encoder`: a VisionTransformerForCyclicalTraining in .eval() (it is NOT a sub-module: state_dict() holds `head.weight`
+    (K, C) and `head.bias` (K,), the reference's keys).  Owns the head, gradient and Adam moment arenas."""
+
+    BETAS, EPS = (0.9, 0.999), 1e-8          # create_optimizer's adamw defaults (optim_factory.py:133-134)
+
+    def __init__(self, encoder, num_classes, smoothing=0.1, init_scale=0.001):
+        super().__init__()
+        if getattr(encoder, "_two_stream", False):
+            raise NotImplementedError("the linear probe reads the base model; the two-stream (mean, covariance) model is not supported")
+        if not isinstance(encoder, VisionTransformerForCyclicalTraining):
+            raise TypeError("encoder must be a VisionTransformerForCyclicalTraining")
+        if encoder.training:
+            raise ValueError("the encoder is frozen: call encoder.eval() first (no dropout, no drop-path in the probe's forward)")
+        K, Cd = int(num_classes), int(encoder.embed_dim)
+        if K < 1:
+            raise ValueError(f"num_classes must be >= 1, got {num_classes}")
+        if not 0.0 <= float(smoothing) < 1.0:
+            raise ValueError(f"smoothing must be in [0, 1), got {smoothing}")
+        object.__setattr__(self, "encoder", encoder)
+        self.num_classes, self.embed_dim, self.smoothing = K, Cd, float(smoothing)
+        self._n_decay = K * Cd
+        n = K * Cd + (K + 3) // 4 * 4
+        dev = encoder._arena.device
+        self._arena = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._grad_arena = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.step_count = 0
+        self.head = _Holder()
+        self.head.register_parameter("weight", nn.Parameter(self._arena[:K * Cd].view(K, Cd)))
+        self.head.register_parameter("bias", nn.Parameter(self._arena[K * Cd:K * Cd + K]))
+        self._rebind()
+        _timm_trunc_normal_(self.head.weight.data, std=0.02).mul_(init_scale)     # modeling_finetune.py:439-441
+        self.head.bias.data.zero_()                                               # constant 0 times init_scale
+        self._buf_batch = 0
+
+    # ---- arena plumbing (as the encoder's) ----
+    def _rebind(self):
+        K, Cd = self.num_classes, self.embed_dim
+        for p, lo, hi, shape in ((self.head.weight, 0, K * Cd, (K, Cd)), (self.head.bias, K * Cd, K * Cd + K, (K,))):
+            p.data = self._arena[lo:hi].view(shape)
+            p.grad = self._grad_arena[lo:hi].view(shape)
+
+    def _apply(self, fn, recurse=True):
+        new = fn(self._arena)
+        if new.dtype != torch.float32:
+            raise NotImplementedError("the head stays fp32")
+        self._arena = new.contiguous()
+        self._grad_arena, self.exp_avg, self.exp_avg_sq = (fn(t).contiguous() for t in (self._grad_arena, self.exp_avg, self.exp_avg_sq))
+        self._buf_batch = 0
+        self._rebind()
+        return self
+
+    def _buffers_for(self, B):
+        """Caller-allocated device buffers of the probe's launches, grown to the largest batch seen."""
+        dev = self._arena.device
+        if dev.type != "cuda":
+            raise native.UvitError("the linear probe runs as HIP kernels: move the encoder and the probe to a GPU (no CPU fallback)")
+        if B > self._buf_batch:
+            K, Cd, N = self.num_classes, self.embed_dim, self.encoder.patch_embed.num_patches + 1
+            ws = lib().uvit_op_probe_pool_ws_bytes(B, N, Cd)
+            if ws < 0:
+                check(int(ws), "uvit_op_probe_pool_ws_bytes")
+            z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)      # noqa: E731
+            self._scratch, self._feat, self._logits, self._dlogits = z(ws // 4), z(B, Cd), z(B, K), z(B, K)
+            self._row_loss = z(B)
+            self._stats = z(2)                       # {loss, grad norm} of the last train_step
+            self._sumsq = z(1, dt=torch.float64)
+            self._buf_batch = B
+        return self._buf_batch
+
+    # ---- forward ----
+    def _check_images(self, images):
+        if not torch.is_tensor(images) or not images.is_cuda:
+            raise native.UvitError("the linear probe needs GPU tensors: the HIP path has no CPU fallback")
+        if self.encoder.training:
+            raise native.UvitError("the encoder left eval mode: the probe reads a frozen, dropout-free forward")
+
+    def _features(self, images):
+        """Encoder eval forward, then pool + norm into self._feat[:B] on the current stream; returns B."""
+        self._check_images(images)
+        B = images.shape[0]
+        self._buffers_for(B)
+        enc = self.encoder
+        e = enc.forward_features(images, bool_masked_pos=None, layer_results=None)
+        x = lib().uvit_engine_ws_ptr(e.h, b"x", enc.depth)
+        if not x:
+            raise native.UvitError("no residual stream of the last block in the engine workspace")
+        N = enc.patch_embed.num_patches + 1
+        check(lib().uvit_op_probe_pool_norm(C.c_void_p(x), ptr(self._feat), ptr(self._scratch), B, N, self.embed_dim, f32(enc.ln_eps),
+                                            cur_stream()), "uvit_op_probe_pool_norm")
+        return B
+
+    def _logits_into(self, B):
+        K, Cd = self.num_classes, self.embed_dim
+        check(lib().uvit_op_probe_logits(ptr(self._feat), ptr(self._arena), C.c_void_p(self._arena.data_ptr() + 4 * K * Cd),
+                                         ptr(self._logits), B, K, Cd, cur_stream()), "uvit_op_probe_logits")
+
+    def features(self, images):
+        """(B, C) fp32: fc_norm(x[:, 1:].mean(1)) of the last block (modeling_finetune.py:512-515)."""
+        B = self._features(images)
+        return self._feat[:B].clone()
+
+    def logits(self, images):
+        B = self._features(images)
+        self._logits_into(B)
+        return self._logits[:B].clone()
+
+    forward = logits
+
+    def _labels(self, labels, B):
+        if not torch.is_tensor(labels) or not labels.is_cuda:
+            raise native.UvitError("labels must be a GPU tensor: the HIP path has no CPU fallback")
+        if labels.dtype != torch.int64 or labels.shape != (B,) or not labels.is_contiguous():
+            raise native.UvitError(f"labels must be a contiguous int64 tensor of shape ({B},)")
+        return labels
+
+    # ---- training ----
+    def train_step(self, images, labels, lr, weight_decay, max_norm=None):
+        """One step on the head: forward, smoothed cross-entropy, head gradients, global-norm clip (max_norm) + AdamW.  Returns
+        (loss, grad_norm) as device scalars, valid until the next step; nothing synchronises with the host.  A non-finite loss
+        (an out-of-range label) makes the gradients non-finite and uvit_op_adamw then leaves the head untouched.  `step_count`
+        (Adam's bias correction) counts calls: the host cannot know of a skipped update without reading the loss, so a caller that
+        sees a non-finite loss stops, as the reference and run_linear_probe.py do, or takes the call back with `step_count -= 1`."""
+        B = self._features(images)
+        labels = self._labels(labels, B)
+        K, Cd, L, s = self.num_classes, self.embed_dim, lib(), cur_stream()
+        self._logits_into(B)
+        check(L.uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(self.smoothing), ptr(self._dlogits), ptr(self._row_loss),
+                                 ptr(self._stats), None, B, K, s), "uvit_op_probe_ce")
+        check(L.uvit_op_probe_head_grad(ptr(self._dlogits), ptr(self._feat), ptr(self._grad_arena),
+                                        C.c_void_p(self._grad_arena.data_ptr() + 4 * K * Cd), B, K, Cd, s), "uvit_op_probe_head_grad")
+        n = self._arena.numel()
+        self._sumsq.zero_()
+        check(L.uvit_op_sumsq(ptr(self._grad_arena), n, ptr(self._sumsq), s), "uvit_op_sumsq")
+        self.step_count += 1
+        check(L.uvit_op_adamw(ptr(self._arena), ptr(self._grad_arena), ptr(self.exp_avg), ptr(self.exp_avg_sq), None, n, self._n_decay,
+                              f32(lr), f32(weight_decay), f32(self.BETAS[0]), f32(self.BETAS[1]), f32(self.EPS), self.step_count,
+                              ptr(self._sumsq), f32(max_norm if max_norm is not None and max_norm > 0 else 0.0), f32(1.0),
+                              C.c_void_p(self._stats.data_ptr() + 4), s), "uvit_op_adamw")
+        return self._stats[0], self._stats[1]
+
+    # ---- evaluation ----
+    def evaluate(self, loader):
+        """`loader` yields (images, labels) or ((images, mask), labels) on the GPU (the device prefetcher's items).  Plain cross-entropy
+        (the reference's evaluate() uses nn.CrossEntropyLoss) and top-1 / top-5 accuracy in percent, from device-side per-batch
+        losses and integer counters that are read once, after the last batch."""
+        losses, sizes, counters = [], [], None
+        for item in loader:
+            images, labels = item
+            if isinstance(images, (tuple, list)):
+                images = images[0]
+            B = self._features(images)
+            if torch.is_tensor(labels) and not labels.is_cuda:
+                labels = labels.to(images.device, non_blocking=True)
+            labels = self._labels(labels, B)
+            if counters is None:
+                counters = torch.zeros(2, dtype=torch.int32, device=images.device)
+            if len(losses) % 256 == 0:
+                slab = torch.zeros(256, dtype=torch.float32, device=images.device)
+            self._logits_into(B)
+            slot = C.c_void_p(slab.data_ptr() + 4 * (len(losses) % 256))
+            check(lib().uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(0.0), None, ptr(self._row_loss), slot, ptr(counters), B,
+                                         self.num_classes, cur_stream()), "uvit_op_probe_ce")
+            losses.append((slab, len(losses) % 256))
+            sizes.append(B)
+        if not sizes:
+            return {"loss": float("nan"), "acc1": float("nan"), "acc5": float("nan"), "n": 0}
+        slabs = {id(s): s for s, _ in losses}
+        host = {k: v.cpu() for k, v in slabs.items()}                       # the one read
+        c1, c5 = (int(v) for v in counters.cpu())
+        n = sum(sizes)
+        loss = sum(float(host[id(s)][i]) * b for (s, i), b in zip(losses, sizes)) / n
+        return {"loss": loss, "acc1": 100.0 * c1 / n, "acc5": 100.0 * c5 / n, "n": n, "correct1": c1, "correct5": c5}
+
+    # ---- optimizer state beside head.* in a checkpoint ----
+    def optimizer_state_dict(self):
+        K, Cd = self.num_classes, self.embed_dim
+        cut = lambda t: {"head.weight": t[:K * Cd].view(K, Cd).cpu().clone(), "head.bias": t[K * Cd:K * Cd + K].cpu().clone()}  # noqa: E731
+        return {"step": self.step_count, "exp_avg": cut(self.exp_avg), "exp_avg_sq": cut(self.exp_avg_sq)}
+
+    def load_optimizer_state_dict(self, sd):
+        K, Cd = self.num_classes, self.embed_dim
+        self.step_count = int(sd["step"])
+        for arena, key in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
+            arena[:K * Cd].view(K, Cd).copy_(sd[key]["head.weight"])
+            arena[K * Cd:K * Cd + K].copy_(sd[key]["head.bias"])
+
+
+def build_probe_encoder(model_name, target_layer=-1, **kwargs):
+    """The frozen encoder of a probe: `create_model(model_name, **kwargs)`, or, with target_layer = L >= 0, the same architecture cut
+    after block L (run_class_finetuning.py:520-522 truncates model.blocks), i.e. built with depth = L + 1.  In eval mode."""
+    full = create_model(model_name, pretrained=False, **kwargs)
+    if target_layer is not None and target_layer != -1:
+        if not 0 <= target_layer < full.depth:
+            raise ValueError(f"--target_layer {target_layer} outside [0, {full.depth})")
+        if target_layer + 1 < full.depth:
+            full = type(full)(**{**full._ctor, "depth": target_layer + 1})
+    return full.eval()
+
+
+def load_encoder_checkpoint(encoder, checkpoint, model_key="model|module", model_prefix=""):
+    """Load a pre-training checkpoint (utils.save_model's dict, or a bare state dict) into the encoder.  `model_key` picks the entry as
+    run_class_finetuning.py:400-406 does; `model_prefix` is stripped from the keys.  Every tensor the encoder has must be there;
+    what the encoder does not have (deeper blocks of a truncated encoder) is left out.  Returns the names left out."""
+    sd = checkpoint
+    for key in model_key.split("|"):
+        if isinstance(checkpoint, dict) and key in checkpoint:
+            sd = checkpoint[key]
+            print("Load state_dict by model_key = %s" % key)
+            break
+    if model_prefix:
+        sd = {k[len(model_prefix):]: v for k, v in sd.items() if k.startswith(model_prefix)}
+    own = encoder.state_dict()
+    missing = [k for k in own if k not in sd]
+    if missing:
+        raise KeyError(f"checkpoint lacks encoder tensors: {missing[:8]}{' ...' if len(missing) > 8 else ''}")
+    encoder.load_state_dict({k: sd[k] for k in own}, strict=True)
+    return sorted(k for k in sd if k not in own)

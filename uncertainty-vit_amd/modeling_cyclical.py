@@ -13,6 +13,7 @@ the C ABI (include/uvit.h).  There is no eager/CPU fallback: calling forward off
 """
 import ctypes as C
 import math
+import weakref
 from functools import partial
 
 import numpy as np
@@ -79,7 +80,9 @@ class NativeEngine:
         if dev.type != "cuda":
             raise native.UvitError("the HIP path needs the model on a GPU (no CPU fallback)")
         n = model._arena.numel()
-        self.model, self.teacher, self.batch = model, teacher, batch
+        # the model owns its engine; a strong reference back would be a cycle that keeps the engine's buffers (tens of GB at ViT-H
+        # bs=128) alive until Python's cycle collector happens to run, instead of until the model is dropped
+        self._model, self.teacher, self.batch = weakref.ref(model), teacher, batch
         self.cfg = model._native_config(batch)
         z = lambda dt=torch.float32, k=n: torch.zeros(k, dtype=dt, device=dev)  # noqa: E731
         self.grads = model._grad_arena if model._grad_arena is not None else z()
@@ -119,6 +122,10 @@ class NativeEngine:
         self.drop_path_rows = bool(getattr(model, "drop_path_rows", os.environ.get("UVIT_DP_ROWS", "1") != "0"))
         self.set_drop_path_rows(self.drop_path_rows)
         self.sync_shadows(3)
+
+    @property
+    def model(self):
+        return self._model()
 
     def set_drop_path_rows(self, on):
         self.drop_path_rows = bool(on)

@@ -156,6 +156,11 @@ _PROTOTYPES = {
     "uvit_op_cast_bf16": (_i, [_vp, _vp, _i64, _vp]),
     "uvit_op_augment_ws_bytes": (_i64, [_vp, _i, _i]),
     "uvit_op_augment_batch": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "uvit_op_probe_pool_ws_bytes": (_i64, [_i, _i, _i]),
+    "uvit_op_probe_pool_norm": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "uvit_op_probe_logits": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "uvit_op_probe_ce": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "uvit_op_probe_head_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
