@@ -164,7 +164,8 @@ int uvit_train_step(uvit_engine* e, const float* images, const int64_t* mask, co
  * threads that launch on different streams cannot disturb one another.
  *   nt_variant: NT GEMM kernel for large shapes: 3 = auto by shape (default), 1 = 256x256 tile with staggered wave
  *               groups (one workgroup per CU), 5 = the same kernel with 320x256 tiles, 0 = 128x128 generic kernel,
- *               6 / 7 = ring kernel (two workgroups per CU, 3-deep 32-k ring) with 128- / 160-row tiles;
+ *               6 / 7 = ring kernel (two workgroups per CU, 3-deep 32-k ring) with 128- / 160-row tiles (where it runs, N % 256 == 0
+ *               and M >= 128, K may be any multiple of 32 from 64 on; every other kernel needs K % 64 == 0);
  *   tn_variant: wgrad (TN) GEMM: 3 = auto (default), 1 = 256x256 staggered kernel, 0 = 128x128;
  *   tn_split_target: workgroups the wgrad token split aims for (default 512);
  *   wgrad_group_chunks: token chunks per output tile of uvit_op_wgrad_group (0 = cost model, default);
@@ -230,6 +231,13 @@ int uvit_op_gemm_nt(int mode, const void* A_bf16, const void* W_bf16, int M, int
  * launcher handed to its row-split tail launch (0 = single launch). */
 int uvit_op_gemm_nt_tuned(int mode, const void* A_bf16, const void* W_bf16, int M, int N, int K, int lda, int ldw,
                           const uvit_gemm_epilogue* epi, const uvit_tuning* tune, int* tail_rows, uvit_stream stream);
+/* What that call would launch on a device with num_cu compute units (num_cu <= 0: UVIT_ERR_ARG), and the same error codes for the
+ * shapes and modes it refuses: host arithmetic only, no device is touched.  kernel: 0 = 128x128, 1 = 256-row, 2 = 256-row persistent,
+ * 3 = 320-row, 4 = ring 128-row, 5 = ring 160-row; it runs the first `rows` rows on `grid` workgroups, and tail_rows more rows (0: none)
+ * go to a second, 128x128 launch.  ldo = the epilogue's ldo; row_list != 0: the launch walks a row list (which never splits). */
+typedef struct uvit_gemm_nt_plan_info { int32_t kernel, rows, grid, tail_rows; } uvit_gemm_nt_plan_info;
+int uvit_op_gemm_nt_plan(int mode, int M, int N, int K, int lda, int ldw, int ldo, int row_list,
+                         const uvit_tuning* tuning, int num_cu, uvit_gemm_nt_plan_info* out);
 /* The same with DYNAMIC tile assignment for the persistent 256x256 kernel (round 4): tile_counters = 16 uint32 in device memory, zero
  * before the first launch (every launch leaves them zero again; launches that may run concurrently need their own 16).  The workgroups
  * then take tiles from per-XCD counters instead of by a fixed stride, so a launch that finds CUs occupied by other work (RCCL's channel

@@ -85,9 +85,23 @@ def assert_grads_close(native_grads, ref_grads, names=None, max_tol=5e-2, l2_tol
     assert not bad, f"{what}gradient mismatch (max-norm ratio, relative L2): {bad}"
 
 
+TOKENS = 197
+# model: (C, hidden, largest k of k x 197 rows: the benchmarked batch)
+MODELS = {"vitb": (768, 3072, 128), "vitl": (1024, 4096, 64), "vith": (1280, 5120, 128)}
+# epilogue modes of include/uvit.h, with the operands tests/test_gpu_ops.py::_epilogue_modes gives them
+QKV, RESID, GELU_DG, MULAUX, BF16 = 1, 3, 8, 9, 0
+
+
+def launches(model):
+    """name -> (N, K, epilogue) of the forward and dgrad launches of one Block."""
+    Cd, Hd, _ = MODELS[model]
+    return {"qkv": (3 * Cd, Cd, QKV), "proj": (Cd, Cd, RESID), "fc1": (Hd, Cd, GELU_DG), "fc2": (Cd, Hd, RESID),
+            "dgrad_fc2": (Hd, Cd, MULAUX), "dgrad_fc1": (Cd, Hd, BF16)}
+
+
 def nt_auto_plan(M, N, K, mode, cu=256, persist=True):
-    """The auto dispatch (nt_variant 3) of uvit_gemm_nt_launch for an M x N x K launch, restated from the comments of that
-    function: (kernel, tail_rows) with kernel one of "128" (the 128x128 kernel: N % 256 != 0, M < 1024, K < 128 or K % 64 != 0),
+    """The auto dispatch (nt_variant 3) of uvit_gemm_nt_launch for an M x N x K launch, restated from the comments of its
+    plan function (gemm_nt_plan in csrc/gemm.hip): (kernel, tail_rows) with kernel one of "128" (the 128x128 kernel: N % 256 != 0, M < 1024, K < 128 or K % 64 != 0),
     "320" (320-row tiles, taken when they save more than 10 % of rounds x rows), "256p" (256-row tiles, persistent: more tiles
     than `cu & ~7` workgroups; never for the MULAUX / DGELU epilogues) and "256"; tail_rows > 0 when 256-row tiles overflow whole
     rounds of the CUs by at most a quarter of them: the overflowing row tiles go to a second, 128x128 launch (not PATCH)."""

@@ -97,6 +97,24 @@ def test_gemm_nt_bias_bf16_and_f32(L, M, N, K):
     close(out32, ref, rtol=2e-3, atol=2e-3, what="f32 out")
 
 
+@pytest.mark.parametrize("variant", [6, 7])
+@pytest.mark.parametrize("M,N,K", [(200, 256, 96), (1300, 512, 160)])
+def test_gemm_nt_ring_kernel_k_in_steps_of_32(L, M, N, K, variant):
+    """The ring kernel walks K in steps of 32: a forced ring variant takes K % 64 == 32 (an odd number of K-steps, 3 and 5; ragged last
+    row tile); every other kernel needs K % 64 == 0 and the launcher refuses such a K for it."""
+    a, w, b = bf(rnd(M, K, seed=1)), bf(rnd(N, K, scale=0.05, seed=2)), rnd(N, seed=3)
+    ref = a.double() @ w.double().t() + b.double()
+    out32, out16 = torch.zeros(M, N, device="cuda"), torch.zeros(M, N, dtype=torch.bfloat16, device="cuda")
+    with tuned(nt_variant=variant):
+        ok(nt(L, 4, P(a), P(w), M, N, K, K, K, C.byref(epi(out=out32, bias=b, ldo=N)), S()))
+        ok(nt(L, 0, P(a), P(w), M, N, K, K, K, C.byref(epi(out=out16, bias=b, ldo=N)), S()))
+    close(out32, ref, rtol=2e-3, atol=2e-3, what="f32 out")
+    close(out16, ref, what="bf16 out")
+    for other in (0, 1, 3, 5):
+        with tuned(nt_variant=other):
+            assert nt(L, 4, P(a), P(w), M, N, K, K, K, C.byref(epi(out=out32, bias=b, ldo=N)), S()) == -2
+
+
 @pytest.mark.parametrize("variant", [0, 1, 5, 6, 7])
 @pytest.mark.parametrize("M,N,K", [(25216, 768, 768), (25216, 3072, 768), (2048, 768, 3072), (1100, 2304, 768), (1024, 256, 128), (1024, 256, 64)])
 def test_gemm_nt_large_tile_kernel(L, M, N, K, variant):

@@ -25,25 +25,13 @@ import time
 import pytest
 import torch
 
-from gpu_util import nt_auto_plan, nt_boundary_rows
+from gpu_util import BF16, GELU_DG, MODELS, MULAUX, QKV, RESID, TOKENS, launches, nt_auto_plan, nt_boundary_rows  # noqa: F401
 from test_gpu_ops import LOG2E, L, P, S, bf, close, epi, nt, ok, padded_bias, rnd, rows_rel, tn  # noqa: F401  (L is a fixture)
 
 pytestmark = pytest.mark.gpu
 
-TOKENS = 197
 SLACK = 320                                      # rows behind the largest M: one row tile of the tallest kernel
 SENT16, SENT32 = 0x7B7B, 0x7B7B7B7B              # bf16 / fp32 1.3e36: finite, and no result of these operands
-# model: (C, hidden, largest k of k x 197 rows: the benchmarked batch)
-MODELS = {"vitb": (768, 3072, 128), "vitl": (1024, 4096, 64), "vith": (1280, 5120, 128)}
-# epilogue modes of include/uvit.h, with the operands tests/test_gpu_ops.py::_epilogue_modes gives them
-QKV, RESID, GELU_DG, MULAUX, BF16 = 1, 3, 8, 9, 0
-
-
-def launches(model):
-    """name -> (N, K, epilogue) of the forward and dgrad launches of one Block."""
-    Cd, Hd, _ = MODELS[model]
-    return {"qkv": (3 * Cd, Cd, QKV), "proj": (Cd, Cd, RESID), "fc1": (Hd, Cd, GELU_DG), "fc2": (Cd, Hd, RESID),
-            "dgrad_fc2": (Hd, Cd, MULAUX), "dgrad_fc1": (Cd, Hd, BF16)}
 
 
 def sentinel(rows, cols, dtype):
@@ -135,12 +123,14 @@ def test_gemm_nt_over_run_row_counts(L, model, name):
     """Auto dispatch (nt_variant 3, what the engine uses) of one forward / dgrad launch shape of ViT-B, ViT-L or ViT-H at every M of
     sweep_rows.  The residual launches carry a per-sample drop-path scale that differs for every sample, so that a wrong row offset
     of the split-off tail launch shows; tail_rows_out must be what the dispatch rule (tests/gpu_util.py::nt_auto_plan, restated
-    from the comments of uvit_gemm_nt_launch) gives for this device's CU count, and a shape that can split must have run both ways."""
-    from uncertainty_vit_amd.native import Tuning
+    from the comments of uvit_gemm_nt_launch) gives for this device's CU count, and what uvit_op_gemm_nt_plan reports for it; a shape
+    that can split must have run both ways."""
+    from uncertainty_vit_amd.native import GemmNtPlanInfo, Tuning
     N, K, mode = launches(model)[name]
     ms, bnd = sweep_rows(model, name)
     cu = torch.cuda.get_device_properties(0).multi_processor_count
     persist = bool(Tuning.default().nt_persist)
+    info = GemmNtPlanInfo()
     case = NtCase(L, N, K, mode, ms[-1])
     torch.cuda.synchronize()
     t0 = time.time()
@@ -149,6 +139,8 @@ def test_gemm_nt_over_run_row_counts(L, model, name):
         kern, want_tail = nt_auto_plan(M, N, K, mode, cu, persist)
         got_tail = case.run(M)
         assert got_tail == want_tail, f"M={M}: tail_rows_out {got_tail}, the dispatch rule gives {want_tail}"
+        ok(L.uvit_op_gemm_nt_plan(mode, M, N, K, K, K, N, 0, None, cu, C.byref(info)))
+        assert info.tail_rows == got_tail, f"M={M}: tail_rows_out {got_tail}, uvit_op_gemm_nt_plan at {cu} CUs reports {info.tail_rows}"
         kernels[kern] = kernels.get(kern, 0) + 1
         split += got_tail > 0
     torch.cuda.synchronize()
@@ -156,21 +148,6 @@ def test_gemm_nt_over_run_row_counts(L, model, name):
           f"{dict(sorted(kernels.items()))}, {time.time() - t0:.1f} s")
     if any(nt_auto_plan(M, N, K, mode, cu, persist)[1] > 0 for M in range(1024, ms[-1] + 1)):
         assert 0 < split < len(ms), "a shape that can split must have run split and unsplit launches"
-
-
-def test_boundary_rows_cover_every_change_of_the_dispatch():
-    """The boundary M are computed, not listed: for every shape they contain 1023 / 1024 and both sides of every change of kernel,
-    tile height, persistent form and row split up to the largest M (256 CUs)."""
-    for model in MODELS:
-        for name, (N, K, mode) in launches(model).items():
-            m_max = MODELS[model][2] * TOKENS
-            bnd = set(nt_boundary_rows(N, K, mode, m_max))
-            assert {1023, 1024} <= bnd
-            plans = [None] + [nt_auto_plan(M, N, K, mode) for M in range(1, m_max + 1)]
-            for M in range(2, m_max + 1):
-                if (plans[M][0], plans[M][1] > 0) != (plans[M - 1][0], plans[M - 1][1] > 0):
-                    assert {M - 1, M} <= bnd, (model, name, M)
-            assert {"128", "256"} <= {plans[M][0] for M in bnd}, (model, name)
 
 
 def wgrad_ks(model):

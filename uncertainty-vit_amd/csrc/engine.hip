@@ -1192,6 +1192,17 @@ extern "C" int uvit_op_gemm_nt_tuned(int mode, const void* A, const void* W, int
     GemmEpi g = epi_from_abi(ep);
     return uvit_gemm_nt_launch(mode, A, W, M, N, K, lda, ldw, &g, S(st), &tu, tail_rows);
 }
+extern "C" int uvit_op_gemm_nt_plan(int mode, int M, int N, int K, int lda, int ldw, int ldo, int row_list, const uvit_tuning* tune,
+                                    int num_cu, uvit_gemm_nt_plan_info* out) {
+    if (!out || num_cu <= 0) return UVIT_ERR_ARG;
+    GemmTune tu;
+    const int trc = tune_from_abi(tune, tu);
+    if (trc) return trc;
+    NtPlan p;
+    const int rc = uvit_gemm_nt_plan(mode, M, N, K, lda, ldw, ldo, row_list != 0, &tu, num_cu, &p);
+    if (rc == UVIT_OK) { out->kernel = p.kind; out->rows = p.rows; out->grid = p.grid; out->tail_rows = p.tail_rows; }
+    return rc;
+}
 extern "C" int uvit_op_gemm_nt(int mode, const void* A, const void* W, int M, int N, int K, int lda, int ldw,
                                const uvit_gemm_epilogue* ep, uvit_stream st) {
     return uvit_op_gemm_nt_tuned(mode, A, W, M, N, K, lda, ldw, ep, nullptr, nullptr, st);

@@ -1307,27 +1307,55 @@ void gemm_tn256_group_kernel(const TnGroup G) {
 // host launchers
 // ------------------------------------------------------------------------------------------
 // Tuning knobs travel with the caller (engine object / operator call): no mutable process-wide launcher state.
-// The only process-wide data are write-once caches of device facts (CU count, LDS opt-in), set under std::call_once.
+// The only process-wide data are write-once caches of device facts (CU count, LDS opt-in) and of one environment switch.
 static std::once_flag g_init_flag;
 static int g_num_cu = 256;
 static const GemmTune g_default_tune;
+static bool auto_ring_env() {               // UVIT_AUTO_RING=1: auto dispatch may take the ring kernel again (A/B runs), read once
+    static const bool on = getenv("UVIT_AUTO_RING") && getenv("UVIT_AUTO_RING")[0] == '1';
+    return on;
+}
+
+// f(EpiMode<mode>{}) for a known epilogue mode (false: unknown).  The one list of the modes on the host side.
+template <int MODE> using EpiMode = std::integral_constant<int, MODE>;
 template <typename F>
-static void allow_lds(F f) { (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * STAGE_BYTES); }
+static bool with_epi_mode(int mode, F&& f) {
+    if (mode == EPI_BF16) f(EpiMode<EPI_BF16>{}); else if (mode == EPI_QKV) f(EpiMode<EPI_QKV>{});
+    else if (mode == EPI_GELU) f(EpiMode<EPI_GELU>{}); else if (mode == EPI_RESID) f(EpiMode<EPI_RESID>{});
+    else if (mode == EPI_F32) f(EpiMode<EPI_F32>{}); else if (mode == EPI_PATCH) f(EpiMode<EPI_PATCH>{});
+    else if (mode == EPI_DGELU) f(EpiMode<EPI_DGELU>{}); else if (mode == EPI_QKV_ELU) f(EpiMode<EPI_QKV_ELU>{});
+    else if (mode == EPI_GELU_DG) f(EpiMode<EPI_GELU_DG>{}); else if (mode == EPI_MULAUX) f(EpiMode<EPI_MULAUX>{});
+    else return false;
+    return true;
+}
+// The six forms of the NT kernel share one signature: {kernel, threads, dynamic LDS bytes} of (epilogue mode, kind), by kernel template
+// (the kernels stand in the code object in the order in which they are named here)
+typedef void (*NtKernelFn)(const bf16*, const bf16*, int, int, int, int, int, GemmEpi);
+struct NtKernel { NtKernelFn fn; int threads; int lds; };
+static NtKernel nt_kernel(int mode, int kind) {
+    NtKernel k = {nullptr, 0, 0};                          // unknown mode
+    if (kind == NT_128)
+        with_epi_mode(mode, [&](auto m) { k = {gemm_nt_kernel<m()>, GEMM_THREADS, 4 * STAGE_BYTES}; });
+    else if (kind == NT_256 || kind == NT_256P || kind == NT_320)
+        with_epi_mode(mode, [&](auto m) {
+            k = kind == NT_256  ? NtKernel{gemm_nt256_kernel<m(), 4, false>, T_THREADS, T_LDS_BYTES}
+              : kind == NT_256P ? NtKernel{gemm_nt256_kernel<m(), 4, true>, T_THREADS, TP_LDS_BYTES}
+                                : NtKernel{gemm_nt256_kernel<m(), 5, false>, T_THREADS, T5_LDS_BYTES};
+        });
+    else
+        with_epi_mode(mode, [&](auto m) {
+            k = kind == NT_RING128 ? NtKernel{gemm_ntr_kernel<m(), 8>, R_THREADS, r_lds_bytes(8)}
+                                   : NtKernel{gemm_ntr_kernel<m(), 10>, R_THREADS, r_lds_bytes(10)};
+        });
+    return k;
+}
 
 static void gemm_init_impl() {
-    allow_lds(gemm_nt_kernel<EPI_BF16>); allow_lds(gemm_nt_kernel<EPI_QKV>); allow_lds(gemm_nt_kernel<EPI_GELU>);
-    allow_lds(gemm_nt_kernel<EPI_RESID>); allow_lds(gemm_nt_kernel<EPI_F32>); allow_lds(gemm_nt_kernel<EPI_PATCH>);
-    allow_lds(gemm_nt_kernel<EPI_DGELU>); allow_lds(gemm_nt_kernel<EPI_QKV_ELU>);
-    allow_lds(gemm_nt_kernel<EPI_GELU_DG>); allow_lds(gemm_nt_kernel<EPI_MULAUX>);
-#define ALLOW256(MODE) do { (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<MODE, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES); \
-        (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<MODE, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_BYTES); \
-        (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<MODE, 5, false>, hipFuncAttributeMaxDynamicSharedMemorySize, T5_LDS_BYTES); } while (0)
-    ALLOW256(EPI_BF16); ALLOW256(EPI_QKV); ALLOW256(EPI_GELU); ALLOW256(EPI_RESID); ALLOW256(EPI_F32); ALLOW256(EPI_PATCH); ALLOW256(EPI_DGELU); ALLOW256(EPI_QKV_ELU); ALLOW256(EPI_GELU_DG); ALLOW256(EPI_MULAUX);
-#undef ALLOW256
-#define ALLOWR(MODE) do { (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<MODE, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, r_lds_bytes(8)); \
-        (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<MODE, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, r_lds_bytes(10)); } while (0)
-    ALLOWR(EPI_BF16); ALLOWR(EPI_QKV); ALLOWR(EPI_GELU); ALLOWR(EPI_RESID); ALLOWR(EPI_F32); ALLOWR(EPI_PATCH); ALLOWR(EPI_DGELU); ALLOWR(EPI_QKV_ELU); ALLOWR(EPI_GELU_DG); ALLOWR(EPI_MULAUX);
-#undef ALLOWR
+    for (int mode = 0; nt_kernel(mode, NT_128).fn; ++mode)          // the modes count from 0 without a gap
+        for (int kind = 0; kind < NT_KINDS; ++kind) {
+            const NtKernel k = nt_kernel(mode, kind);
+            (void)hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
+        }
     (void)hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
     (void)hipFuncSetAttribute((const void*)gemm_tn256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
     (void)hipFuncSetAttribute((const void*)gemm_tn256_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES);
@@ -1337,132 +1365,100 @@ static void gemm_init_impl() {
 }
 static void gemm_init_once() { std::call_once(g_init_flag, gemm_init_impl); }
 
+static int nt_grid(int kind, int M, int N) {                       // workgroups, one per tile
+    static const int rows[NT_KINDS] = {BM, T_BM, T_BM, 320, 128, 160};
+    const int cols = kind == NT_128 ? BN : T_BN;
+    return ((M + rows[kind] - 1) / rows[kind]) * ((N + cols - 1) / cols);
+}
+
+// The dispatch of one NT launch: pure arithmetic on its arguments (tests/test_host_gemm_plan.py).  tu.nt_variant: 0 = 128x128 (any
+// shape, two workgroups per CU), 1 = 256x256 staggered (one per CU), 5 = 320x256 (same kernel, 5 row tiles per wave), 6 / 7 = ring kernel
+// (two per CU) with 128- / 160-row tiles, 3 = auto.  A forced variant runs on the 128x128 kernel where its own does not support the
+// shape, and never splits rows.  K is a multiple of 64, or of 32 where the ring kernel runs.
+//  - Auto takes the staggered kernel for every shape it supports.  In warm micro-benchmarks (operands resident in the Infinity Cache)
+//    the 128x128 kernel wins the N = 768 shapes by 10-25 % (profiles/round1_gemm_variants_v2.txt), but inside the step, where operands
+//    come from HBM, its one-K-tile prefetch distance costs it 28-44 % and the deeper ring of the staggered kernel wins everywhere: A/B
+//    of the whole step on one box 30.2 -> 29.6 ms.
+//  - Tile height: 320 rows when that saves > 10 % of rounds x rows (N = 768 at M = 25216: 237 tiles = 1 round instead of 297 = 1.16
+//    rounds of 256-row tiles).
+//  - Auto sends nothing to the ring kernel (since round 4); UVIT_AUTO_RING=1 (auto_ring) restores the old rule for
+//    A/B runs: the residual epilogue on narrow outputs, unless 320-row tiles fill >= 85 % of the CUs in ONE round.
+//  - Row split: 256-row tiles that overflow whole rounds of the CUs by at most a quarter of them would run a nearly empty last round: the
+//    overflowing row tiles go to a second, 128x128 launch (tail_rows).  Not for the patch embedding, and not with a row list, whose rows
+//    are not an offset apart.
+//  - Persistent form of the 256-row kernel whenever a CU would otherwise run several workgroups back to back.  Not for the epilogues
+//    that multiply by a row operand: with the persistent form's 4-KiB staging area their fp32 blocks go through one at a time and they
+//    lose 2-3 % (tools/bench_gemm.py --persist: mulaux 153 vs 149 us, dgelu 169 vs 164 us); all other epilogues gain 6-10 %.
+static int gemm_nt_plan(int mode, int M, int N, int K, int lda, int ldw, int ldo, bool row_list, const GemmTune& tu, int num_cu,
+                        bool auto_ring, NtPlan& p) {
+    if (M <= 0 || N <= 0 || K <= 0 || (N % 8) || (lda % 8) || (ldw % 8) || (ldo % 4)) return UVIT_ERR_SHAPE;
+    const int v = tu.nt_variant, tn = N / T_BN;
+    const bool ring_ok = (N % T_BN) == 0 && M >= 128 && K >= 64 && (K % R_BK) == 0 &&
+                         (size_t)M * lda < 0xFFFFFFFFull && (size_t)N * ldw < 0xFFFFFFFFull;     // 32-bit operand offsets
+    const bool shape_ok = ring_ok && M >= 1024 && K >= 128 && (K % BK) == 0;        // the 256- and 320-row kernel
+    const bool one_full_round5 = shape_ok && nt_grid(NT_320, M, N) <= num_cu && (long)nt_grid(NT_320, M, N) * 100 >= (long)num_cu * 85;
+    p = NtPlan{NT_128, M, 0, 0};
+    if (ring_ok && (v == 6 || v == 7 || (auto_ring && v == 3 && mode == EPI_RESID && N <= 1024 && M >= 160 * 8 && !one_full_round5)))
+        p.kind = v == 6 ? NT_RING128 : NT_RING160;
+    else if (shape_ok && v == 5) p.kind = NT_320;
+    else if (shape_ok && v == 1) p.kind = NT_256;
+    else if (shape_ok && v == 3) {
+        const long c4 = (long)((nt_grid(NT_256, M, N) + num_cu - 1) / num_cu) * 256;      // rounds x rows
+        const long c5 = (long)((nt_grid(NT_320, M, N) + num_cu - 1) / num_cu) * 320;
+        p.kind = c5 * 10 < c4 * 9 ? NT_320 : NT_256;
+        if (p.kind == NT_256 && mode != EPI_PATCH && !row_list) {
+            const int tiles = nt_grid(NT_256, M, N), rounds = tiles / num_cu, over = tiles - rounds * num_cu;
+            const int rows_a = (rounds * num_cu / tn) * T_BM;
+            if (rounds >= 1 && over > 0 && over * 4 <= num_cu && rows_a > 0 && rows_a < M) { p.rows = rows_a; p.tail_rows = M - rows_a; }
+        }
+    }
+    if ((K % BK) && p.kind != NT_RING128 && p.kind != NT_RING160) return UVIT_ERR_SHAPE;       // the ring kernel alone walks K in steps of 32
+    if (!with_epi_mode(mode, [](auto) {})) return UVIT_ERR_ARG;
+    if ((mode == EPI_QKV || mode == EPI_QKV_ELU) && (N % 3)) return UVIT_ERR_SHAPE;
+    p.grid = nt_grid(p.kind, p.rows, N);
+    const int pgrid = num_cu & ~7;
+    if (p.kind == NT_256 && tu.nt_persist && pgrid >= 8 && p.grid > pgrid && mode != EPI_MULAUX && mode != EPI_DGELU) { p.kind = NT_256P; p.grid = pgrid; }
+    return UVIT_OK;
+}
+int uvit_gemm_nt_plan(int mode, int M, int N, int K, int lda, int ldw, int ldo, bool row_list, const GemmTune* tune, int num_cu,
+                      NtPlan* out) {
+    return gemm_nt_plan(mode, M, N, K, lda, ldw, ldo, row_list, tune ? *tune : g_default_tune, num_cu, auto_ring_env(), *out);
+}
+
+// the epilogue of rows [r0, ..): every row-indexed operand moves with the row offset
+static GemmEpi epi_from_row(const GemmEpi& e, int mode, size_t r0) {
+    GemmEpi t = e;
+    const bool f32out = mode == EPI_RESID || mode == EPI_F32 || mode == EPI_PATCH;
+    t.out = f32out ? (void*)((float*)t.out + r0 * t.ldo) : (void*)((bf16*)t.out + r0 * t.ldo);
+    if (t.out2) t.out2 = (void*)((bf16*)t.out2 + r0 * t.ldo);
+    if (t.resid) t.resid = t.resid + r0 * t.ldo;
+    if (t.aux) t.aux = (const void*)((const bf16*)t.aux + r0 * t.ldo);
+    t.row0 = e.row0 + (int)r0;
+    return t;
+}
+static int nt_launch_kind(int mode, int kind, int grid, const bf16* a, const bf16* w, int M, int N, int K, int lda, int ldw,
+                          const GemmEpi& epi, hipStream_t s) {
+    const NtKernel k = nt_kernel(mode, kind);
+    hipLaunchKernelGGL(k.fn, dim3(grid), dim3(k.threads), k.lds, s, a, w, M, N, K, lda, ldw, epi);
+    return uvit_check_launch();
+}
+
 int uvit_gemm_nt_launch(int mode, const void* A, const void* W, int M, int N, int K, int lda, int ldw,
                         const GemmEpi* epi, hipStream_t s, const GemmTune* tune, int* tail_rows_out) {
     const GemmTune& tu = tune ? *tune : g_default_tune;
-    const int nt_variant = tu.nt_variant;
     if (tail_rows_out) *tail_rows_out = 0;
-    if (M <= 0 || N <= 0 || K <= 0 || (K % BK) || (N % 8) || (lda % 8) || (ldw % 8) || (epi->ldo % 4))
-        return UVIT_ERR_SHAPE;
     gemm_init_once();
-    // variant: 0 = 128x128 (any shape, two workgroups per CU), 1 = 256x256 staggered (one per CU), 5 = 320x256 (same
-    // kernel, 5 row tiles per wave), 3 = auto.
-    // Auto takes the staggered kernel for every shape it supports.  In warm micro-benchmarks (operands resident in the
-    // Infinity Cache) the 128x128 kernel wins the N = 768 shapes by 10-25 % (profiles/round1_gemm_variants_v2.txt),
-    // but inside the step, where operands come from HBM, its one-K-tile prefetch distance costs it 28-44 % and the
-    // deeper ring of the staggered kernel wins everywhere: A/B of the whole step on one box 30.2 -> 29.6 ms.
-    // Tile height: 320 rows when that saves > 10 % of rounds x rows (N = 768 at M = 25216: 237 tiles = 1 round
-    // instead of 297 = 1.16 rounds of 256-row tiles).
-    const bool shape_ok = (N % 256) == 0 && M >= 1024 && K >= 128 && (K % 64) == 0 &&
-                          (size_t)M * lda < 0xFFFFFFFFull && (size_t)N * ldw < 0xFFFFFFFFull;     // 32-bit operand offsets
-    int variant = shape_ok ? nt_variant : 0;
-    int mt = 4;
-    // ring kernel (2 workgroups per CU): 6 = 128-row tiles, 7 = 160-row tiles
-    const bool ring_ok = (N % R_BN) == 0 && M >= 128 && K >= 64 && (K % R_BK) == 0 &&
-                         (size_t)M * lda < 0xFFFFFFFFull && (size_t)N * ldw < 0xFFFFFFFFull;
-    // auto: the residual epilogue (fp32 stream read + write + bf16 branch copy: the heaviest epilogue per flop) on narrow
-    // outputs goes to the ring kernel, whose two workgroups per CU overlap one's epilogue with the other's K loop -- unless the
-    // 320-row tiles of the staggered kernel fill the CUs in ONE round (>= 85 % of them busy), where its stronger K loop wins
-    // (tools/bench_gemm_variants.py, M = 25216, N = 768: K = 3072 122.8 vs 152.7 us, K = 768 54.0 vs 53.8 us -- since the
-    // 320-row kernel no longer spills inside its K loop; ViT-L at bs = 64 gives 160 such tiles on 256 CUs and stays on the ring)
-    const long tiles5 = (long)((M + 319) / 320) * (N / 256 > 0 ? N / 256 : 1);
-    const bool one_full_round5 = shape_ok && tiles5 <= g_num_cu && tiles5 * 100 >= (long)g_num_cu * 85;
-    // Round 4: auto no longer sends anything to the ring kernel.  Re-measured at the ViT-L shapes it was kept for (tools/bench_gemm.py --cold style,
-    // residual epilogue, M = 12608 / 25216, N = 1024): K = 1024: ring 85.8 / 146.0 us against 67.7 / 117.9 us for the 256-row staggered kernel,
-    // K = 4096: 191.4 / 305.6 against 125.1 / 239.9 us -- the staggered kernel's K loop and epilogue have moved since round 2, the ring's have not
-    // (profiles/round4_gemm_large_resid_variants.txt).  UVIT_AUTO_RING=1 restores the old rule for A/B runs; variants 6 / 7 still select it.
-    static const bool auto_ring_env = getenv("UVIT_AUTO_RING") && getenv("UVIT_AUTO_RING")[0] == '1';
-    const bool auto_ring = auto_ring_env && nt_variant == 3 && mode == EPI_RESID && ring_ok && N <= 1024 && M >= 160 * 8 && !one_full_round5;
-    if (((nt_variant == 6 || nt_variant == 7) && ring_ok) || auto_ring) {
-        const int rmt = nt_variant == 6 ? 8 : 10;
-        const int rgrid = ((M + 16 * rmt - 1) / (16 * rmt)) * (N / R_BN);
-        const bf16* a_ = (const bf16*)A; const bf16* w_ = (const bf16*)W;
-#define LR(MODE) do { if (rmt == 8) hipLaunchKernelGGL((gemm_ntr_kernel<MODE, 8>), dim3(rgrid), dim3(R_THREADS), r_lds_bytes(8), s, a_, w_, M, N, K, lda, ldw, *epi); \
-        else hipLaunchKernelGGL((gemm_ntr_kernel<MODE, 10>), dim3(rgrid), dim3(R_THREADS), r_lds_bytes(10), s, a_, w_, M, N, K, lda, ldw, *epi); } while (0)
-        switch (mode) {
-            case EPI_BF16: LR(EPI_BF16); break;
-            case EPI_QKV: if (N % 3) return UVIT_ERR_SHAPE; LR(EPI_QKV); break;
-            case EPI_GELU: LR(EPI_GELU); break;
-            case EPI_RESID: LR(EPI_RESID); break;
-            case EPI_F32: LR(EPI_F32); break;
-            case EPI_PATCH: LR(EPI_PATCH); break;
-            case EPI_DGELU: LR(EPI_DGELU); break;
-            case EPI_GELU_DG: LR(EPI_GELU_DG); break;
-            case EPI_MULAUX: LR(EPI_MULAUX); break;
-            case EPI_QKV_ELU: if (N % 3) return UVIT_ERR_SHAPE; LR(EPI_QKV_ELU); break;
-            default: return UVIT_ERR_ARG;
-        }
-#undef LR
-        return uvit_check_launch();
-    }
-    if (variant == 6 || variant == 7) variant = 3;          // shape not supported by the ring kernel: auto
-    if (variant == 5) { variant = 1; mt = 5; }
-    else if (variant == 3) {
-        variant = 1;
-        const int tn_ = N / T_BN;
-        const long c4 = (long)((((M + 255) / 256) * tn_ + g_num_cu - 1) / g_num_cu) * 256;
-        const long c5 = (long)((((M + 319) / 320) * tn_ + g_num_cu - 1) / g_num_cu) * 320;
-        if (c5 * 10 < c4 * 9) mt = 5;
-    }
-    // 256-row tiles that overflow whole rounds of the CUs by only a few tiles would run a nearly empty last round: the
-    // overflowing row tiles go to the 128x128 kernel instead (second launch below)
-    int m_tail = 0;
-    if (variant == 1 && mt == 4 && nt_variant == 3 && mode != EPI_PATCH && !epi->rowmap) {      // (a row list does not split: its rows are not an offset apart)
-        const int tiles_n = N / T_BN, tiles = ((M + T_BM - 1) / T_BM) * tiles_n;
-        const int rounds = tiles / g_num_cu, over = tiles - rounds * g_num_cu;
-        // (round 3 tried half a round of overflow -- QKV at bs = 128: 891 tiles = 3 rounds + 123: 93.2 -> 88.9 us alone, but inside the
-        //  step the 3-round launch + its 128x128 tail take the same 91.7 us as the 4-round launch: profiles/round3_gemm_pair_kernel_experiment.txt)
-        if (rounds >= 1 && over > 0 && over * 4 <= g_num_cu) {
-            const int rows_a = (rounds * g_num_cu / tiles_n) * T_BM;
-            if (rows_a > 0 && rows_a < M) { m_tail = M - rows_a; M = rows_a; }
-        }
-    }
-    GemmEpi epi_g = *epi;
-    epi_g.ngroup = tu.nt_group;
-    epi = &epi_g;
-    const int bm = mt == 5 ? 320 : T_BM;
-    const int grid = variant == 1 ? ((M + bm - 1) / bm) * (N / T_BN) : ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    const size_t lds = 4 * STAGE_BYTES;
+    NtPlan p;
+    int rc = gemm_nt_plan(mode, M, N, K, lda, ldw, epi->ldo, epi->rowmap != nullptr, tu, g_num_cu, auto_ring_env(), p);
+    if (rc != UVIT_OK) return rc;
+    GemmEpi e = *epi;
+    e.ngroup = tu.nt_group;
     const bf16* a = (const bf16*)A; const bf16* w = (const bf16*)W;
-    // persistent form of the 256-row kernel whenever a CU would otherwise run several workgroups back to back
-    const int pgrid = g_num_cu & ~7;
-    // (not for the epilogues that multiply by a row operand: with the persistent form's 4-KiB staging area their fp32 blocks go
-    // through one at a time and they lose 2-3 %, tools/bench_gemm.py --persist: mulaux 153 vs 149 us, dgelu 169 vs 164 us;
-    // all other epilogues gain 6-10 %)
-    const bool persist = variant == 1 && mt == 4 && tu.nt_persist && pgrid >= 8 && grid > pgrid && mode != EPI_MULAUX && mode != EPI_DGELU;
-#define L(MODE) do { if (variant == 1 && mt == 5) hipLaunchKernelGGL((gemm_nt256_kernel<MODE, 5, false>), dim3(grid), dim3(T_THREADS), T5_LDS_BYTES, s, a, w, M, N, K, lda, ldw, *epi); \
-        else if (persist) hipLaunchKernelGGL((gemm_nt256_kernel<MODE, 4, true>), dim3(pgrid), dim3(T_THREADS), TP_LDS_BYTES, s, a, w, M, N, K, lda, ldw, *epi); \
-        else if (variant == 1) hipLaunchKernelGGL((gemm_nt256_kernel<MODE, 4, false>), dim3(grid), dim3(T_THREADS), T_LDS_BYTES, s, a, w, M, N, K, lda, ldw, *epi); \
-        else hipLaunchKernelGGL(gemm_nt_kernel<MODE>, dim3(grid), dim3(GEMM_THREADS), lds, s, a, w, M, N, K, lda, ldw, *epi); } while (0)
-    switch (mode) {
-        case EPI_BF16: L(EPI_BF16); break;
-        case EPI_QKV: if (N % 3) return UVIT_ERR_SHAPE; L(EPI_QKV); break;
-        case EPI_GELU: L(EPI_GELU); break;
-        case EPI_RESID: L(EPI_RESID); break;
-        case EPI_F32: L(EPI_F32); break;
-        case EPI_PATCH: L(EPI_PATCH); break;
-        case EPI_DGELU: L(EPI_DGELU); break;
-        case EPI_GELU_DG: L(EPI_GELU_DG); break;
-        case EPI_MULAUX: L(EPI_MULAUX); break;
-        case EPI_QKV_ELU: if (N % 3) return UVIT_ERR_SHAPE; L(EPI_QKV_ELU); break;
-        default: return UVIT_ERR_ARG;
-    }
-#undef L
-    int rc = uvit_check_launch();
-    if (rc == UVIT_OK && m_tail > 0) {
-        // remaining rows: every row-indexed epilogue operand moves with the row offset
-        GemmEpi t = *epi;
-        const size_t r0 = (size_t)M;
-        const bool f32out = mode == EPI_RESID || mode == EPI_F32 || mode == EPI_PATCH;
-        t.out = f32out ? (void*)((float*)t.out + r0 * t.ldo) : (void*)((bf16*)t.out + r0 * t.ldo);
-        if (t.out2) t.out2 = (void*)((bf16*)t.out2 + r0 * t.ldo);
-        if (t.resid) t.resid = t.resid + r0 * t.ldo;
-        if (t.aux) t.aux = (const void*)((const bf16*)t.aux + r0 * t.ldo);
-        t.row0 = epi->row0 + (int)r0;
-        GemmTune generic;                                  // the tail always runs on the 128x128 kernel
-        generic.nt_variant = 0;
-        rc = uvit_gemm_nt_launch(mode, a + r0 * lda, W, m_tail, N, K, lda, ldw, &t, s, &generic, nullptr);
-        if (tail_rows_out) *tail_rows_out = m_tail;
+    rc = nt_launch_kind(mode, p.kind, p.grid, a, w, p.rows, N, K, lda, ldw, e, s);
+    if (rc == UVIT_OK && p.tail_rows > 0) {                // the tail always runs on the 128x128 kernel
+        rc = nt_launch_kind(mode, NT_128, nt_grid(NT_128, p.tail_rows, N), a + (size_t)p.rows * lda, w, p.tail_rows, N, K, lda, ldw,
+                            epi_from_row(e, mode, (size_t)p.rows), s);
+        if (tail_rows_out) *tail_rows_out = p.tail_rows;
     }
     return rc;
 }

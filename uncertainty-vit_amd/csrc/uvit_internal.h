@@ -45,6 +45,13 @@ struct GemmTune {
     int nt_group = 0;        // 256x256 NT kernel: column tiles per row-tile group of the tile order (0 = default 6)
     int nt_persist = 1;      // 256x256 NT kernel, more tiles than CUs: persistent workgroups, operand pipeline across tiles
 };
+// What one NT launch runs (the dispatch of uvit_gemm_nt_launch): kind = the kernel of the first `rows` rows on `grid` workgroups,
+// tail_rows = the remaining rows, which go to a second launch of the 128x128 kernel (0: none).
+enum { NT_128 = 0, NT_256 = 1, NT_256P = 2, NT_320 = 3, NT_RING128 = 4, NT_RING160 = 5, NT_KINDS = 6 };
+struct NtPlan { int kind; int rows; int grid; int tail_rows; };
+// The plan of a launch on a device with num_cu CUs: host arithmetic only, no device is touched.  Returns the launcher's error codes.
+int uvit_gemm_nt_plan(int mode, int M, int N, int K, int lda, int ldw, int ldo, bool row_list, const GemmTune* tune, int num_cu,
+                      NtPlan* out);
 // tune == nullptr: defaults.  tail_rows_out (nullable) receives the rows that went to the row-split tail launch.
 int uvit_gemm_nt_launch(int mode, const void* A, const void* W, int M, int N, int K, int lda, int ldw,
                         const GemmEpi* epi, hipStream_t s, const GemmTune* tune = nullptr, int* tail_rows_out = nullptr);

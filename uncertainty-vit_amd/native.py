@@ -84,6 +84,11 @@ class Tuning(C.Structure):
         return t
 
 
+class GemmNtPlanInfo(C.Structure):
+    """uvit_gemm_nt_plan_info (include/uvit.h): what uvit_op_gemm_nt_plan reports."""
+    _fields_ = [("kernel", C.c_int32), ("rows", C.c_int32), ("grid", C.c_int32), ("tail_rows", C.c_int32)]
+
+
 class AugmentDesc(C.Structure):
     """uvit_augment_desc (include/uvit.h): one sample of uvit_op_augment_batch."""
     _fields_ = [("offset", C.c_int64)] + \
@@ -127,6 +132,7 @@ _PROTOTYPES = {
     "uvit_engine_profile_read_kind": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "uvit_op_gemm_nt": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "uvit_op_gemm_nt_tuned": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "uvit_op_gemm_nt_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "uvit_op_gemm_nt_sched": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "uvit_op_gemm_tn": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "uvit_op_wasserstein_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _vp]),
