@@ -398,6 +398,40 @@ int uvit_op_probe_ce(const float* logits, const int64_t* labels, float smoothing
  * uvit_op_adamw (head.weight decays, head.bias does not: optim_factory.py:58-97). */
 int uvit_op_probe_head_grad(const float* dlogits, const float* feat, float* dW, float* dbias, int B, int K, int C, uvit_stream stream);
 
+/* ---- calibration metrics of a classifier's batch (uncertainty_evaluations.py: ECELoss, TACELoss, NLL; AUROC one-vs-rest) ----
+ * 1 <= B <= 1024, K >= 1, 1 <= n_bins <= 64.  Every call checks its arguments before it touches the device (UVIT_ERR_ARG for a NULL
+ * pointer, UVIT_ERR_SHAPE for a size outside these limits, outputs untouched) and is asynchronous on `stream`.  No float atomics;
+ * every floating sum has one owner and a fixed order, so the same input gives the same bits on every run.  probs is (B, K) fp32,
+ * labels int64[B].  Comparisons widen the fp32 probability to double and compare with a double bound, so bin membership is what a
+ * float64 restatement finds on the same fp32 values.  A label outside [0, K) makes ECE, NLL, TACE and the AUROC sum of the call NaN;
+ * nothing is read at such a label. */
+/* probs = softmax(logits) per row: fp32, max-shifted, one wave per row.  The only place where logits become probabilities. */
+int uvit_op_calib_softmax(const float* logits, float* probs, int B, int K, uvit_stream stream);
+/* Per row: row_conf[b] = max_k p, row_pred_correct[b] = the lowest index attaining it, row_pred_correct[B + b] = (pred == y),
+ * row_nll[b] = -log(clamp(p_y / sum_k p_k, 2^-23, 1 - 2^-23)) (sum and quotient in double: Categorical(probs).log_prob).
+ * bounds: HOST array double[n_bins + 1], the values of np.linspace(0, 1, n_bins + 1); it is read during the call and travels by value.
+ * Bin i holds the rows with bounds[i] < conf <= bounds[i + 1] (a conf of exactly 0 falls in no bin).  bin_table = double[3 n_bins],
+ * (prop, acc, conf) per bin with prop = count / B, zeros for an empty bin, each bin summed in row order.
+ * positional_acc (0 or 1, else UVIT_ERR_ARG) chooses the bin accuracy, here and in uvit_op_calib_tace: 0 = the mean of the hit flag
+ * a[b] (correct; [y_b == c] for TACE) over the rows of the bin; 1 = what the reference's compute_bins returns, whose
+ * `accuracies[in_bin]` indexes rows 0 and 1 by position: (count a[1] + (B - count) a[0]) / B (a[1] := a[0] at B = 1, where the
+ * reference cannot run).  The reference's published ECE / TACE are mode 1;
+ * ece_nll[0] = sum_i prop_i |conf_i - acc_i| in bin order, ece_nll[1] = mean of row_nll in row order. */
+int uvit_op_calib_confidence(const float* probs, const int64_t* labels, const double* bounds, int n_bins, int positional_acc, float* row_conf,
+                             int32_t* row_pred_correct, double* row_nll, double* bin_table, double* ece_nll, int B, int K,
+                             uvit_stream stream);
+/* Thresholded adaptive calibration error.  Per class c: v_b = p[b, c] < threshold ? 0 : p[b, c]; sorted ascending; bin_n = B / n_bins
+ * (integer; 0 when B < n_bins); lo_i = sorted[i bin_n], up_i = lo_{i+1}, up_last = 1.0; bin i holds the b with lo_i < v_b <= up_i;
+ * per_class[c] (double[K]) = sum_i (count_i / B) |mean v - acc_i| in bin order, acc_i by positional_acc (see above); *tace = (sum_c per_class[c]) / K in class
+ * order.  One workgroup per group of adjacent classes sorts its columns in LDS. */
+int uvit_op_calib_tace(const float* probs, const int64_t* labels, double threshold, int n_bins, int positional_acc, double* per_class,
+                       double* tace, int B, int K, uvit_stream stream);
+/* One-vs-rest AUROC over the classes present in the batch.  rows = int32[3 B]: u2_i = sum over j with y_j != y_i of
+ * 2 [p_i > p_j] + [p_i == p_j] in column y_i | n_pos_i = rows that carry y_i | first_i = no earlier row carries y_i.
+ * out[0] = sum_i u2_i / (2 n_pos_i (B - n_pos_i)) over the samples whose class has a negative row, in sample order = sum_c AUC_c;
+ * out[1] = the number of classes counted. */
+int uvit_op_calib_auroc(const float* probs, const int64_t* labels, int32_t* rows, double* out, int B, int K, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

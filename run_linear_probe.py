@@ -11,7 +11,9 @@ The encoder is frozen; the patch tokens of its last block (`--target_layer L`: o
 are mean-pooled, normalised without affine and fed to one nn.Linear, the only thing that trains (uncertainty-vit_amd/linear_probe.py).
 `--finetune` is a checkpoint written by run_cyclical.py (utils.save_model); its `lm_head.*` and `mask_token` entries are loaded but
 never used.  Training reads `--data_path` with flip + RandomResizedCrop (augmentation level 3), evaluation reads `--eval_data_path`
-with resize + center crop (level 1), both augmented on the device.  Single GPU.
+with resize + center crop (level 1), both augmented on the device.  Single GPU.  `--calibration` adds the reference's calibration
+metrics to every evaluation: a second line `* ECE ... TACE ... NLL ... AUROC ...` and `test_ECE`, `test_TACE`, `test_NLL`,
+`test_AUROC` in log.txt (with --eval: one entry of the test figures, when --output_dir is given).
 """
 import argparse
 import json
@@ -54,7 +56,17 @@ def get_args(argv=None):
     a("--resume", default="", help="head checkpoint (probe-*.pth) to continue from or to evaluate")
     a("--eval", action="store_true", help="Perform evaluation only")
     a("--num_workers", default=0, type=int)
+    # absent unless given (SUPPRESS): without the flag the parsed arguments, and so the first line printed, are what they were
+    a("--calibration", action="store_true", default=argparse.SUPPRESS,
+      help="also report ECE, TACE, NLL and AUROC of the evaluation (the reference's evaluate() beside Acc@1 / Acc@5)")
     return p.parse_args(argv)
+
+
+CALIB_KEYS = ("ECE", "TACE", "NLL", "AUROC")
+
+
+def calibration_line(stats):
+    return "* ECE {ECE:.5f} TACE {TACE:.5f} NLL {NLL:.5f} AUROC {AUROC:.5f}".format(**stats)
 
 
 def encoder_kwargs(checkpoint):
@@ -114,9 +126,17 @@ def main(args):
 
     eval_root = args.eval_data_path or args.data_path
     loader_val, _ = build_loader(args, encoder, eval_root, 1, train=False)
+    calibration = getattr(args, "calibration", False)
+    evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration)      # noqa: E731
     if args.eval:
-        stats = probe.evaluate(DevicePrefetcher(loader_val, device))
+        stats = evaluate()
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
+        if calibration:
+            print(calibration_line(stats))
+            if args.output_dir:
+                with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
+                    f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5")},
+                                        **{f"test_{k}": stats[k] for k in CALIB_KEYS}}) + "\n")
         return stats
     loader_train, _ = build_loader(args, encoder, args.data_path, 3, train=True)
     steps_per_epoch = len(loader_train)
@@ -147,14 +167,17 @@ def main(args):
             log.update(lr=lr)
         for l0, g0 in seen:
             publish(log, l0, g0)
-        stats = probe.evaluate(DevicePrefetcher(loader_val, device))
+        stats = evaluate()
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f}")
+        if calibration:
+            print(calibration_line(stats))
         print(f"Epoch {epoch}: loss: {log.loss.global_avg:.4f}  lr: {log.lr.value:.8f}  acc1: {stats['acc1']:.3f}  acc5: {stats['acc5']:.3f}")
         if args.output_dir:
             save_probe(args, probe, epoch)
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({"epoch": epoch, "train_loss": log.loss.global_avg, "train_lr": log.lr.value,
-                                    **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5")}}) + "\n")
+                                    **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + (CALIB_KEYS if calibration else ())}})
+                        + "\n")
     print("Training time %.0f s" % (time.time() - t0))
     return stats
 

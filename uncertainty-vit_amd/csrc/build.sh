@@ -22,6 +22,9 @@ pids+=($!)
 # would reassociate the tile sums back into one chain
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c probe.hip -o obj/probe.o ) &
 pids+=($!)
+# calib.hip compares in IEEE double and fixes the order of every sum (bin membership is exact, bit-identical runs): no fast-math
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c calib.hip -o obj/calib.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

@@ -12,6 +12,7 @@ step path; the one torch call there is the 8-byte fill that clears the gradient 
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -20,6 +21,9 @@ from .modeling_cyclical import VisionTransformerForCyclicalTraining, _Holder, cr
 from .native import check, cur_stream, f32, lib, ptr
 
 __all__ = ["LinearProbe", "build_probe_encoder", "load_encoder_checkpoint"]
+
+CALIB_MAX_BINS = 64          # csrc/calib.hip: 1 <= n_bins <= 64, 1 <= B <= 1024
+ECE_BINS, TACE_BINS, TACE_THRESHOLD = 15, 30, 0.01      # the reference's defaults (uncertainty_evaluations.py:200,243)
 
 
 def _timm_trunc_normal_(t, std):
@@ -66,7 +70,7 @@ class LinearProbe(nn.Module):
         self._rebind()
         _timm_trunc_normal_(self.head.weight.data, std=0.02).mul_(init_scale)     # modeling_finetune.py:439-441
         self.head.bias.data.zero_()                                               # constant 0 times init_scale
-        self._buf_batch = 0
+        self._buf_batch = self._calib_batch = 0
 
     # ---- arena plumbing (as the encoder's) ----
     def _rebind(self):
@@ -81,12 +85,13 @@ class LinearProbe(nn.Module):
             raise NotImplementedError("the head stays fp32")
         self._arena = new.contiguous()
         self._grad_arena, self.exp_avg, self.exp_avg_sq = (fn(t).contiguous() for t in (self._grad_arena, self.exp_avg, self.exp_avg_sq))
-        self._buf_batch = 0
+        self._buf_batch = self._calib_batch = 0
         self._rebind()
         return self
 
-    def _buffers_for(self, B):
-        """Caller-allocated device buffers of the probe's launches, grown to the largest batch seen."""
+    def _buffers_for(self, B, calibration=False):
+        """Caller-allocated device buffers of the probe's launches, grown to the largest batch seen; with `calibration`, those of the
+        calibration ops (csrc/calib.hip) as well."""
         dev = self._arena.device
         if dev.type != "cuda":
             raise native.UvitError("the linear probe runs as HIP kernels: move the encoder and the probe to a GPU (no CPU fallback)")
@@ -101,6 +106,14 @@ class LinearProbe(nn.Module):
             self._stats = z(2)                       # {loss, grad norm} of the last train_step
             self._sumsq = z(1, dt=torch.float64)
             self._buf_batch = B
+        if calibration and B > self._calib_batch:
+            K = self.num_classes
+            z = lambda *s, dt=torch.float64: torch.zeros(*s, dtype=dt, device=dev)      # noqa: E731
+            self._probs, self._row_conf = z(B, K, dt=torch.float32), z(B, dt=torch.float32)
+            self._row_pred, self._auroc_rows = z(2 * B, dt=torch.int32), z(3 * B, dt=torch.int32)
+            self._row_nll, self._bin_table, self._per_class = z(B), z(3 * CALIB_MAX_BINS), z(K)
+            self._calib_out = z(5)                   # {ECE, NLL, TACE, AUROC sum, AUROC class count} of the last calibration_batch
+            self._calib_batch = B
         return self._buf_batch
 
     # ---- forward ----
@@ -174,12 +187,58 @@ class LinearProbe(nn.Module):
                               C.c_void_p(self._stats.data_ptr() + 4), s), "uvit_op_adamw")
         return self._stats[0], self._stats[1]
 
+    # ---- calibration ----
+    def _calibration_into(self, logits, labels, B, out, ece_bins=ECE_BINS, tace_bins=TACE_BINS, tace_threshold=TACE_THRESHOLD,
+                          reference_bin_accuracy=True):
+        """Softmax plus the three metric ops of csrc/calib.hip on `logits` (B, K) on the current stream; `out` is a device pointer to
+        five doubles: ECE, NLL, TACE, AUROC sum over the classes counted, number of classes counted."""
+        K, L, s = self.num_classes, lib(), cur_stream()
+        if not 1 <= int(ece_bins) <= CALIB_MAX_BINS:
+            raise native.UvitError(f"ece_bins must be in [1, {CALIB_MAX_BINS}], got {ece_bins}")
+        bounds = np.linspace(0, 1, int(ece_bins) + 1)            # the reference's bin edges, bit for bit (uncertainty_evaluations.py:116)
+        at = lambda i: C.c_void_p(out + 8 * i)                   # noqa: E731
+        pos = 1 if reference_bin_accuracy else 0
+        check(L.uvit_op_calib_softmax(ptr(logits), ptr(self._probs), B, K, s), "uvit_op_calib_softmax")
+        check(L.uvit_op_calib_confidence(ptr(self._probs), ptr(labels), bounds.ctypes.data_as(C.c_void_p), int(ece_bins), pos,
+                                         ptr(self._row_conf), ptr(self._row_pred), ptr(self._row_nll), ptr(self._bin_table), at(0), B, K,
+                                         s), "uvit_op_calib_confidence")
+        check(L.uvit_op_calib_tace(ptr(self._probs), ptr(labels), C.c_double(float(tace_threshold)), int(tace_bins), pos, ptr(self._per_class),
+                                   at(2), B, K, s), "uvit_op_calib_tace")
+        check(L.uvit_op_calib_auroc(ptr(self._probs), ptr(labels), ptr(self._auroc_rows), at(3), B, K, s), "uvit_op_calib_auroc")
+
+    def calibration_batch(self, logits, labels, ece_bins=ECE_BINS, tace_bins=TACE_BINS, tace_threshold=TACE_THRESHOLD,
+                          reference_bin_accuracy=True):
+        """The reference's four per-batch calibration numbers (engine_for_finetuning.py:199-204) of caller-supplied GPU logits (B, K)
+        fp32, B <= 1024: (ECE, TACE, NLL, AUROC) as float64 device scalars, valid until the next call; nothing synchronises with the
+        host.  AUROC is the one-vs-rest mean over the classes with a positive and a negative row in the batch (NaN when there is
+        none); a label outside [0, K) makes all four NaN.  `reference_bin_accuracy`: ECE and TACE as the reference's classes return them,
+        whose bin accuracy indexes rows 0 and 1 of the batch by position (include/uvit.h, positional_acc); False
+        gives the mean over the rows of each bin, the textbook ECE / TACE.  The bin table, the per-class TACE values and the per-row outputs of the
+        ops stay in self._bin_table, self._per_class, self._row_conf, self._row_pred, self._auroc_rows, the sum and count of the
+        AUROC in self._calib_out[3:5]."""
+        if not torch.is_tensor(logits) or not logits.is_cuda:
+            raise native.UvitError("logits must be a GPU tensor: the HIP path has no CPU fallback")
+        if logits.dtype != torch.float32 or logits.ndim != 2 or logits.shape[1] != self.num_classes or not logits.is_contiguous():
+            raise native.UvitError(f"logits must be a contiguous float32 tensor of shape (B, {self.num_classes})")
+        B = logits.shape[0]
+        labels = self._labels(labels, B)
+        self._buffers_for(B, calibration=True)
+        self._calibration_into(logits, labels, B, self._calib_out.data_ptr(), ece_bins, tace_bins, tace_threshold, reference_bin_accuracy)
+        o = self._calib_out
+        return o[0], o[2], o[1], o[3] / o[4]
+
     # ---- evaluation ----
-    def evaluate(self, loader):
+    def evaluate(self, loader, calibration=False):
         """`loader` yields (images, labels) or ((images, mask), labels) on the GPU (the device prefetcher's items).  Plain cross-entropy
         (the reference's evaluate() uses nn.CrossEntropyLoss) and top-1 / top-5 accuracy in percent, from device-side per-batch
-        losses and integer counters that are read once, after the last batch."""
+        losses and integer counters that are read once, after the last batch.  With `calibration`, every batch (at most 1024 samples)
+        also runs the calibration ops on its logits and the result gains ECE, TACE, NLL and AUROC: batch-size-weighted means of the
+        per-batch values, the reference's meters (engine_for_finetuning.py:207-213), ECE and TACE with the reference's bin accuracy
+        (calibration_batch's reference_bin_accuracy=True).  A batch in which no class has both a positive
+        and a negative row has no AUROC and is left out of that mean only; AUROC_zero_absent is the weighted mean of
+        (sum of the per-class values) / K, i.e. with every class absent from a batch scored 0."""
         losses, sizes, counters = [], [], None
+        calib = []
         for item in loader:
             images, labels = item
             if isinstance(images, (tuple, list)):
@@ -196,16 +255,34 @@ class LinearProbe(nn.Module):
             slot = C.c_void_p(slab.data_ptr() + 4 * (len(losses) % 256))
             check(lib().uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(0.0), None, ptr(self._row_loss), slot, ptr(counters), B,
                                          self.num_classes, cur_stream()), "uvit_op_probe_ce")
+            if calibration:
+                self._buffers_for(B, calibration=True)
+                if len(calib) % 256 == 0:
+                    cslab = torch.zeros(256, 5, dtype=torch.float64, device=images.device)
+                self._calibration_into(self._logits, labels, B, cslab.data_ptr() + 40 * (len(calib) % 256))
+                calib.append((cslab, len(calib) % 256))
             losses.append((slab, len(losses) % 256))
             sizes.append(B)
         if not sizes:
-            return {"loss": float("nan"), "acc1": float("nan"), "acc5": float("nan"), "n": 0}
+            empty = {"loss": float("nan"), "acc1": float("nan"), "acc5": float("nan"), "n": 0}
+            if calibration:
+                empty.update({k: float("nan") for k in ("ECE", "TACE", "NLL", "AUROC", "AUROC_zero_absent")})
+            return empty
         slabs = {id(s): s for s, _ in losses}
         host = {k: v.cpu() for k, v in slabs.items()}                       # the one read
         c1, c5 = (int(v) for v in counters.cpu())
         n = sum(sizes)
         loss = sum(float(host[id(s)][i]) * b for (s, i), b in zip(losses, sizes)) / n
-        return {"loss": loss, "acc1": 100.0 * c1 / n, "acc5": 100.0 * c5 / n, "n": n, "correct1": c1, "correct5": c5}
+        stats = {"loss": loss, "acc1": 100.0 * c1 / n, "acc5": 100.0 * c5 / n, "n": n, "correct1": c1, "correct5": c5}
+        if calibration:
+            chost = {k: v.cpu() for k, v in {id(s): s for s, _ in calib}.items()}          # read with the losses, after the last batch
+            rows = [chost[id(s)][i].tolist() for s, i in calib]                            # per batch: ECE, NLL, TACE, AUROC sum, count
+            for key, col in (("ECE", 0), ("TACE", 2), ("NLL", 1)):
+                stats[key] = sum(r[col] * b for r, b in zip(rows, sizes)) / n
+            have = [(r[3] / r[4], b) for r, b in zip(rows, sizes) if r[4] > 0]
+            stats["AUROC"] = sum(a * b for a, b in have) / sum(b for _, b in have) if have else float("nan")
+            stats["AUROC_zero_absent"] = sum(r[3] / self.num_classes * b for r, b in zip(rows, sizes)) / n
+        return stats
 
     # ---- optimizer state beside head.* in a checkpoint ----
     def optimizer_state_dict(self):

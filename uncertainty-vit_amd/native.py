@@ -167,6 +167,10 @@ _PROTOTYPES = {
     "uvit_op_probe_logits": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "uvit_op_probe_ce": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "uvit_op_probe_head_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "uvit_op_calib_softmax": (_i, [_vp, _vp, _i, _i, _vp]),
+    "uvit_op_calib_confidence": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "uvit_op_calib_tace": (_i, [_vp, _vp, C.c_double, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "uvit_op_calib_auroc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
