@@ -35,7 +35,7 @@ typedef struct uvit_config {
     float ln_eps;                     /* 1e-6, modeling_cyclical.py:294 */
     float attn_drop_rate;             /* --attn_drop_rate */
     float drop_path_rate;             /* --drop_path; per-layer linspace(0, rate, depth) */
-    int32_t bias_chunk;               /* batch elements summed in registers per rel-pos-bias slab (0 = chosen to fill one round of dQ workgroups) */
+    int32_t bias_chunk;               /* ignored (it sized the retired dQ kernels); kept for the struct layout */
     int32_t two_stream;               /* 1: DistVisionTransformerForCyclicalTraining (mean, cov) model, modeling_cyclical_dist.py:14-165 */
 } uvit_config;
 
@@ -117,7 +117,12 @@ int uvit_layout_get(const uvit_config* cfg, int index, uvit_layout_entry* out);
 int64_t uvit_arena_numel(const uvit_config* cfg, int64_t* n_decay_out);
 int64_t uvit_workspace_bytes(const uvit_config* cfg);
 
-/* ---- engine ---- */
+/* ---- engine ----
+ * Calls on ONE engine must be stream-ordered with respect to one another: issue them on one stream, or order the streams with events, so
+ * that no two of them can be in flight at once (a uvit_engine_forward_features on a second stream while a step is still running is not
+ * allowed).  They share the workspace and the tile counters of the persistent GEMMs: the engine keeps 2 x 16 counters, the second block
+ * for the teacher pass of a step (which it runs beside the student pass itself), the first for every other pass -- chosen by the role of
+ * the call, never by the stream it is given.  Different engines are independent. */
 uvit_engine* uvit_engine_create(const uvit_config* cfg, const uvit_buffers* bufs, uvit_stream stream, int* err_out);
 void uvit_engine_destroy(uvit_engine* e);
 

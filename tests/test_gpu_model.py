@@ -414,3 +414,64 @@ def test_drop_path_sample_lists_equal_all_samples(shape):
     assert sl[1]["loss"] == pytest.approx(sa[1]["loss"], rel=1e-3) and sl[1]["grad_norm"] == pytest.approx(sa[1]["grad_norm"], rel=2e-2)
     for n in ("blocks.1.mlp.fc1.weight", "blocks.2.attn.proj.weight", "blocks.0.norm1.weight"):
         torch.testing.assert_close(pl[n], pa[n], rtol=0, atol=2 * 2e-3 * 2 + 1e-6)     # two AdamW steps: a sign flip on a ~0 gradient is 2 lr apart
+
+
+def _persistent_fc1_batch(cfg):
+    """Smallest B <= 128 in steps of 4 (104 first: the shape the test was sized for, 256 CUs) at which fc1 of both forwards -- bias + GELU
+    for the teacher, GELU + GELU' for the student -- runs as the persistent 256-row kernel, the one that takes its tiles from counters."""
+    import ctypes as C
+    from uncertainty_vit_amd import native
+    cu = torch.cuda.get_device_properties(0).multi_processor_count
+    info = native.GemmNtPlanInfo()
+    Cd, Hd = cfg.embed_dim, int(cfg.embed_dim * cfg.mlp_ratio)
+    for B in [104] + list(range(4, 129, 4)):
+        kernels = []
+        for mode in (2, 8):          # UVIT_EPI_GELU, UVIT_EPI_GELU_DG
+            assert native.lib().uvit_op_gemm_nt_plan(mode, B * 197, Hd, Cd, Cd, Cd, Hd, 0, None, cu, C.byref(info)) == 0
+            kernels.append(info.kernel)
+        if kernels == [2, 2]:        # uvit_gemm_nt_plan_info.kernel: 2 = 256-row persistent
+            return B, cu
+    pytest.fail(f"no batch <= 128 runs fc1 ({Hd} x {Cd}) as the persistent kernel on {cu} CUs")
+
+
+@pytest.mark.parametrize("two_stream", [False, True], ids=["base", "two_stream"])
+def test_step_single_stream_equals_two_streams(two_stream, monkeypatch):
+    """uvit_engine_set_streams (include/uvit.h): 0 runs the whole step on the caller's stream, 1 / 2 run the teacher forward and the weight
+    gradients on a second stream (2: of lower priority).  Same model, batch and seeds under the three modes: the same step, and the same
+    step again behind it.  The teacher pass of a step takes the second block of tile counters of the persistent GEMMs in every mode, the
+    student pass the first; every launch has to leave its counters at zero, which the second step would find out.  The model is the
+    smallest whose forward reaches the persistent 256-row kernel: C = 256, 4 heads, hidden 1024, 2 blocks, 224 px; at B = 104 (20,488 token
+    rows) fc1 is 81 x 4 = 324 tiles on 256 workgroups.  Train mode with drop-path and attention dropout: the student runs its sample lists.
+    Bounds: those of the two tests above that compare two launch plans of the same arithmetic (first step: the masked-row last block's;
+    second step: the drop-path sample lists'), with one exception.  The first step's loss leaves no room at rel 1e-6: the loss kernel sums
+    7,800 rows with fp32 atomics, and at 0.31 .. 0.39 one ulp of the fp32 loss is already 0.8 .. 0.95e-7 of it.  The commit before the
+    engine's pass descriptor, three runs of this test (12 comparisons) on an MI355X: 4.75, 0.95, 3.09, 1.54, 1.90, 2.85, 1.54, 2.32, 2.85,
+    7.59, 6.18, 2.32 (x 1e-7), and one run of the same loss kernel in this commit reached 9.49e-7.  The bound is twice the worst of the
+    earlier commit's: 1.52e-6.  The other figures of those runs stay far inside their bounds: first-step grad norm identical in every run,
+    worst gradient tensor 3.4e-7 relative L2; second step loss <= 1.31e-6, grad norm <= 1.30e-5."""
+    cfg = vo.VitConfig(embed_dim=256, depth=2, num_heads=4, init_values=0.1, drop_path_rate=0.25, attn_drop_rate=0.05)
+    B, cu = _persistent_fc1_batch(cfg)
+    print(f"B = {B} on {cu} CUs")
+    x, mask = closed_form_images("streams", B, 224).cuda(), exact_masks(B, 196, 75, 13).cuda()
+    res = {}
+    for mode in (0, 1, 2):
+        monkeypatch.setenv("UVIT_STREAM_MODE", str(mode))
+        model, _ = native_model(cfg, two_stream=two_stream)
+        ema, opt = native_trainer(model)
+        model.train()
+        torch.manual_seed(4321)
+        sts = native_steps(model, ema, opt, [(x, mask)], [0, 1], start=3, stochastic=two_stream)
+        grads = {n: q.grad.detach().float().cpu().clone() for n, q in model.named_parameters()}
+        sts += native_steps(model, ema, opt, [(x, mask)], [0, 1], start=4, stochastic=two_stream)
+        assert model._engine.stream_mode == mode
+        res[mode] = (sts, grads)
+        print(f"mode {mode}: " + ", ".join(f"loss {s['loss']!r} grad_norm {s['grad_norm']!r}" for s in sts))
+    s0, g0 = res[0]
+    for mode in (1, 2):
+        print(f"mode {mode} vs 0: " + ", ".join(f"loss rel {abs(a['loss'] / b['loss'] - 1):.2e} grad_norm rel {abs(a['grad_norm'] / b['grad_norm'] - 1):.2e}"
+                                               for a, b in zip(res[mode][0], s0)))
+    for mode in (1, 2):
+        sm, gm = res[mode]
+        assert sm[0]["loss"] == pytest.approx(s0[0]["loss"], rel=1.52e-6) and sm[0]["grad_norm"] == pytest.approx(s0[0]["grad_norm"], rel=1e-5)
+        assert_grads_close(gm, g0, max_tol=1e-4, l2_tol=1e-4, what=f"[stream mode {mode} vs single stream] ")
+        assert sm[1]["loss"] == pytest.approx(s0[1]["loss"], rel=1e-3) and sm[1]["grad_norm"] == pytest.approx(s0[1]["grad_norm"], rel=2e-2)

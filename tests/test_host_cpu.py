@@ -89,6 +89,29 @@ def test_arena_layout_matches_reference_state_dict(native):
     assert L.uvit_arena_numel(C.byref(bad), None) < 0
 
 
+# (img, patch, chans, embed, depth, heads, mlp hidden, rel-pos bias, abs pos, batch, ln eps, attn drop, drop path, bias_chunk, two_stream)
+WORKSPACE_BYTES = {
+    "ViT-B/16 bs128": ((224, 16, 3, 768, 12, 12, 3072, 1, 0, 128, 1e-6, 0.05, 0.25, 0, 0), 11_990_577_152),
+    "ViT-B/16 two-stream bs128": ((224, 16, 3, 768, 12, 12, 3072, 1, 0, 128, 1e-6, 0.05, 0.25, 0, 1), 23_444_799_488),
+    "ViT-L/16 bs64": ((224, 16, 3, 1024, 24, 16, 4096, 1, 0, 64, 1e-6, 0.05, 0.25, 0, 0), 14_303_064_064),
+    "ViT-H/16 (head_dim 80) bs128": ((224, 16, 3, 1280, 32, 16, 5120, 1, 0, 128, 1e-6, 0.05, 0.25, 0, 0), 45_761_351_680),
+    "tiny_model, 48 px, abs pos, bs4": ((48, 16, 3, 128, 2, 2, 512, 1, 1, 4, 1e-6, 0.0, 0.0, 0, 0), 5_451_776),
+}
+
+
+@pytest.mark.parametrize("name", list(WORKSPACE_BYTES))
+def test_workspace_plan_is_pinned(native, name):
+    """uvit_workspace_bytes of five configurations, as recorded from the commit before the engine's forward passes got their
+    descriptor: the workspace plan is host arithmetic on the configuration alone (no device is queried), and the retired
+    `bias_chunk` field does not enter it."""
+    L = native.lib()
+    fields, want = WORKSPACE_BYTES[name]
+    assert L.uvit_workspace_bytes(C.byref(native.Config(*fields))) == want
+    with_chunk = list(fields)
+    with_chunk[13] = 7
+    assert L.uvit_workspace_bytes(C.byref(native.Config(*with_chunk))) == want
+
+
 def test_model_surface_matches_reference(native, golden_dir):
     m = tiny_model()
     cfg = vo.VitConfig(img_size=48, embed_dim=128, depth=2, num_heads=2, init_values=0.1)

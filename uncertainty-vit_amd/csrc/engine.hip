@@ -25,11 +25,10 @@
 // ------------------------------------------------------------------------------------------
 // layout
 // ------------------------------------------------------------------------------------------
-struct LayerOff { size_t n1w, n1b, qkvw, qb, vb, projw, projb, g1, n2w, n2b, fc1w, fc1b, fc2w, fc2b, g2;
-                  size_t cqkvw, cqb, cvb, cprojw, cprojb; };   // two-stream model only
+// x[2]: per stream, 0 = mean (the only one of the base model), 1 = covariance (the "cov_" tensors; filled, like cqkvw, for the two-stream model only)
+struct LayerOff { size_t n1w, n1b, qkvw, qb[2], vb[2], projw[2], projb[2], g1, n2w, n2b, fc1w, fc1b, fc2w, fc2b, g2, cqkvw; };
 struct Layout {
-    size_t cls, mask_tok, pew, peb, relt, normw, normb, lmw, lmb, pos;
-    size_t ccls, cmask_tok, cpew, cpeb, clmw, clmb;          // two-stream model only
+    size_t cls[2], mask_tok[2], pew[2], peb[2], relt, normw, normb, lmw[2], lmb[2], pos;
     LayerOff L[UVIT_MAX_DEPTH];
     size_t n_total, n_decay, n_live;     // [0, n_decay) decay | [n_decay, n_live) no-decay | [n_live, n_total) frozen
     std::vector<uvit_layout_entry> entries;
@@ -52,7 +51,6 @@ static int cfg_ok(const uvit_config* c) {
 
 static void build_layout(const uvit_config* c, Layout& lo) {
     const int64_t C = c->embed_dim, Hd = c->mlp_hidden, g = c->img_size / c->patch_size;
-    const int64_t Kpe = (int64_t)c->in_chans * c->patch_size * c->patch_size;
     size_t off = 0;
     auto add = [&](const std::string& name, std::vector<int64_t> shape, int decay) -> size_t {
         uvit_layout_entry e;
@@ -68,41 +66,40 @@ static void build_layout(const uvit_config* c, Layout& lo) {
     auto blk = [](int i, const char* s) { return "blocks." + std::to_string(i) + "." + s; };
     // ---- decay group: everything that is not 1-D, not *.bias, not in {pos_embed, cls_token} ----
     const bool two = c->two_stream != 0;
-    lo.mask_tok = add("mask_token", {1, 1, C}, 1);
-    if (two) lo.cmask_tok = add("cov_mask_token", {1, 1, C}, 1);
+    lo.mask_tok[0] = add("mask_token", {1, 1, C}, 1);
+    if (two) lo.mask_tok[1] = add("cov_mask_token", {1, 1, C}, 1);
     // 'cov_cls_token' is not in the no_weight_decay() skip list {'pos_embed','cls_token'} and is 3-D: decay group
-    if (two) lo.ccls = add("cov_cls_token", {1, 1, C}, 1);
+    if (two) lo.cls[1] = add("cov_cls_token", {1, 1, C}, 1);
     if (c->use_shared_rel_pos_bias) lo.relt = add("rel_pos_bias.relative_position_bias_table", {(2 * g - 1) * (2 * g - 1) + 3, c->num_heads}, 1);
     else lo.relt = (size_t)-1;
-    lo.pew = add("patch_embed.proj.weight", {C, c->in_chans, c->patch_size, c->patch_size}, 1);
-    if (two) lo.cpew = add("cov_patch_embed.proj.weight", {C, c->in_chans, c->patch_size, c->patch_size}, 1);
-    (void)Kpe;
+    lo.pew[0] = add("patch_embed.proj.weight", {C, c->in_chans, c->patch_size, c->patch_size}, 1);
+    if (two) lo.pew[1] = add("cov_patch_embed.proj.weight", {C, c->in_chans, c->patch_size, c->patch_size}, 1);
     for (int i = 0; i < c->depth; ++i) {
         lo.L[i].qkvw = add(blk(i, "attn.qkv.weight"), {3 * C, C}, 1);
-        lo.L[i].projw = add(blk(i, "attn.proj.weight"), {C, C}, 1);
-        if (two) lo.L[i].cprojw = add(blk(i, "attn.cov_proj.weight"), {C, C}, 1);
+        lo.L[i].projw[0] = add(blk(i, "attn.proj.weight"), {C, C}, 1);
+        if (two) lo.L[i].projw[1] = add(blk(i, "attn.cov_proj.weight"), {C, C}, 1);
         lo.L[i].fc1w = add(blk(i, "mlp.fc1.weight"), {Hd, C}, 1);
         lo.L[i].fc2w = add(blk(i, "mlp.fc2.weight"), {C, Hd}, 1);
     }
-    lo.lmw = add("lm_head.weight", {C, C}, 1);
-    if (two) lo.clmw = add("cov_lm_head.weight", {C, C}, 1);
+    lo.lmw[0] = add("lm_head.weight", {C, C}, 1);
+    if (two) lo.lmw[1] = add("cov_lm_head.weight", {C, C}, 1);
     lo.n_decay = off;
     // ---- no-decay group ----
-    lo.cls = add("cls_token", {1, 1, C}, 0);
+    lo.cls[0] = add("cls_token", {1, 1, C}, 0);
     // 'pos_embed' (1, N, C) is 3-D but sits in the no_weight_decay() skip list (modeling_cyclical.py:163-165)
     lo.pos = c->use_abs_pos_emb ? add("pos_embed", {1, g * g + 1, C}, 0) : (size_t)-1;
-    lo.peb = add("patch_embed.proj.bias", {C}, 0);
-    if (two) lo.cpeb = add("cov_patch_embed.proj.bias", {C}, 0);
+    lo.peb[0] = add("patch_embed.proj.bias", {C}, 0);
+    if (two) lo.peb[1] = add("cov_patch_embed.proj.bias", {C}, 0);
     for (int i = 0; i < c->depth; ++i) {
         lo.L[i].g1 = add(blk(i, "gamma_1"), {C}, 0);
         lo.L[i].g2 = add(blk(i, "gamma_2"), {C}, 0);
         lo.L[i].n1w = add(blk(i, "norm1.weight"), {C}, 0);
         lo.L[i].n1b = add(blk(i, "norm1.bias"), {C}, 0);
-        lo.L[i].qb = add(blk(i, "attn.q_bias"), {C}, 0);
-        lo.L[i].vb = add(blk(i, "attn.v_bias"), {C}, 0);
-        if (two) { lo.L[i].cqb = add(blk(i, "attn.cov_q_bias"), {C}, 0); lo.L[i].cvb = add(blk(i, "attn.cov_v_bias"), {C}, 0); }
-        lo.L[i].projb = add(blk(i, "attn.proj.bias"), {C}, 0);
-        if (two) lo.L[i].cprojb = add(blk(i, "attn.cov_proj.bias"), {C}, 0);
+        lo.L[i].qb[0] = add(blk(i, "attn.q_bias"), {C}, 0);
+        lo.L[i].vb[0] = add(blk(i, "attn.v_bias"), {C}, 0);
+        if (two) { lo.L[i].qb[1] = add(blk(i, "attn.cov_q_bias"), {C}, 0); lo.L[i].vb[1] = add(blk(i, "attn.cov_v_bias"), {C}, 0); }
+        lo.L[i].projb[0] = add(blk(i, "attn.proj.bias"), {C}, 0);
+        if (two) lo.L[i].projb[1] = add(blk(i, "attn.cov_proj.bias"), {C}, 0);
         lo.L[i].n2w = add(blk(i, "norm2.weight"), {C}, 0);
         lo.L[i].n2b = add(blk(i, "norm2.bias"), {C}, 0);
         lo.L[i].fc1b = add(blk(i, "mlp.fc1.bias"), {Hd}, 0);
@@ -110,8 +107,8 @@ static void build_layout(const uvit_config* c, Layout& lo) {
     }
     lo.normw = add("norm.weight", {C}, 0);
     lo.normb = add("norm.bias", {C}, 0);
-    lo.lmb = add("lm_head.bias", {C}, 0);
-    if (two) lo.clmb = add("cov_lm_head.bias", {C}, 0);
+    lo.lmb[0] = add("lm_head.bias", {C}, 0);
+    if (two) lo.lmb[1] = add("cov_lm_head.bias", {C}, 0);
     lo.n_live = off;
     // attn.cov_qkv.weight is never used by the reference's forward (modeling_finetune_dist.py:127 reuses qkv.weight):
     // its .grad stays None, so torch's AdamW never touches it (no weight decay either).  It lives at the END of the
@@ -137,7 +134,7 @@ struct uvit_engine {
     uvit_config cfg;
     uvit_buffers buf;
     Layout lo;
-    int B, P, N, NP, C, Hd, H, Kpe, M, Mpad, BP, BPpad, chunk, nchunk;     // (Hd: the MLP hidden size)
+    int B, P, N, NP, C, Hd, H, Kpe, M, Mpad, BP, BPpad;     // (Hd: the MLP hidden size)
     int head_dim;          // C / H: 64 or 80
     float attn_scale;      // head_dim ** -0.5 (0.125f for 64)
     int S;                 // streams: 1 or 2
@@ -158,7 +155,7 @@ struct uvit_engine {
     float *dXa, *dXb;
     bf16 *dY1[2], *dY2[2], *dH[2], *dLN, *dAttn, *dqkv[2];   // [layer parity]: read by the wgrad stream while the next layer runs
     float *dp_scales, *dp_rates;
-    // drop-path sample lists (training step): per (layer, draw) list lb = 2 S l + k, k as in dp_ptr (base: attn, mlp; two-stream: mean attn,
+    // drop-path sample lists (training step): per (layer, draw) list lb = 2 S l + k, k as in dp_draw (base: attn, mlp; two-stream: mean attn,
     // mean mlp, cov attn, cov mlp -- only the two MLP lists are used there: the two-stream attention needs both streams of a sample)
     int *dpl_pos = nullptr, *dpl_bmap = nullptr, *dpl_rows = nullptr, *dpl_cnt = nullptr;
     size_t dpl_stride = 0;                 // ints per rows list
@@ -177,7 +174,7 @@ struct uvit_engine {
     float* grep;           // [NREP][no-decay region] replicated column-sum accumulators
     size_t n_nd;           // floats in the live (not frozen) part of the no-decay region
     bool slab_started;
-    bool last_dropout; uint32_t last_seed, last_it;
+    bool last_dropout; uint32_t last_seed;
     int bwd_next = -1;      // the layer uvit_step_backward_layer takes next: depth-1 after uvit_step_begin, then down to 0 (-1: none)
     int compact_R = 0;      // > 0: this step runs the last block's MLP on the masked rows only, in R (multiple of 64) compact rows (uvit_step_params.n_rows_hint)
     // second stream: teacher forward beside student forward; wgrad GEMMs beside the dgrad chain
@@ -273,27 +270,10 @@ static void fill_dims(uvit_engine* e) {
     e->attn_scale = e->head_dim == 64 ? 0.125f : (float)(1.0 / std::sqrt((double)e->head_dim));
     e->S = c.two_stream ? 2 : 1;
     e->M = e->B * e->N; e->Mpad = (int)roundup(e->M, 128); e->BP = e->B * e->P; e->BPpad = (int)roundup(e->BP, 128);
-    if (c.bias_chunk > 0) {
-        e->chunk = c.bias_chunk;
-    } else {
-        // the dQ kernel runs (heads x chunks x 2 halves) workgroups, two resident per CU: take the most chunks that still
-        // fit one round (ViT-B bs=128 on 256 CUs: 19 chunks of 7 samples = 456 workgroups instead of 16 x 8 = 384)
-        int ncu = 256, dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            ncu = prop.multiProcessorCount;
-        const int nhalf = (e->N + 15) / 16 > 7 ? 2 : 1;
-        const int resident = 1;                       // both dQ kernels hold four 28-KiB images (double-buffered K, V): one workgroup per CU
-        int max_chunks = (resident * ncu) / (e->H * nhalf);
-        if (max_chunks < 1) max_chunks = 1;
-        e->chunk = (e->B + max_chunks - 1) / max_chunks;
-        if (e->chunk < 1) e->chunk = 1;
-    }
-    e->nchunk = (e->B + e->chunk - 1) / e->chunk;
     e->cur_B = e->B;
     Layout tmp_lo; build_layout(&e->cfg, tmp_lo);
     e->n_nd = tmp_lo.n_live - tmp_lo.n_decay;      // span of the replicated accumulators: live no-decay tensors only
 }
-
 
 extern "C" void uvit_engine_destroy(uvit_engine* e);
 extern "C" int uvit_version(void) { return UVIT_VERSION; }
@@ -360,12 +340,11 @@ extern "C" uvit_engine* uvit_engine_create(const uvit_config* cfg, const uvit_bu
         td.push_back(d);
     };
     for (int i = 0; i < cfg->depth; ++i) {
-        addT(e->lo.L[i].qkvw, 3 * e->C, e->C); addT(e->lo.L[i].projw, e->C, e->C);
+        addT(e->lo.L[i].qkvw, 3 * e->C, e->C); addT(e->lo.L[i].projw[0], e->C, e->C);
         addT(e->lo.L[i].fc1w, e->Hd, e->C); addT(e->lo.L[i].fc2w, e->C, e->Hd);
-        if (e->S == 2) addT(e->lo.L[i].cprojw, e->C, e->C);
+        if (e->S == 2) addT(e->lo.L[i].projw[1], e->C, e->C);
     }
-    addT(e->lo.lmw, e->C, e->C);
-    if (e->S == 2) addT(e->lo.clmw, e->C, e->C);
+    for (int st = 0; st < e->S; ++st) addT(e->lo.lmw[st], e->C, e->C);
     e->n_tdesc = (int)td.size(); e->n_ttiles = tiles;
     {
         std::vector<int> idr(e->BP);
@@ -378,7 +357,7 @@ extern "C" uvit_engine* uvit_engine_create(const uvit_config* cfg, const uvit_bu
     if (hipMemcpyAsync(e->dp_rates, rates.data(), rates.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(e->tdesc, td.data(), td.size() * sizeof(TransposeDesc), hipMemcpyHostToDevice, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) { delete e; return fail(UVIT_ERR_LAUNCH); }
-    e->slab_started = false; e->last_dropout = false; e->last_seed = 0; e->last_it = 0;
+    e->slab_started = false; e->last_dropout = false; e->last_seed = 0;
     {
         const char* env = getenv("UVIT_SINGLE_STREAM");
         e->dual = !(env && env[0] == '1');
@@ -515,19 +494,15 @@ extern "C" int uvit_engine_sync_shadows(uvit_engine* e, int which, uvit_stream s
 
 // ---- forward ----
 struct Weights { const float* f; const bf16* b; };
+static Weights weights_of(const uvit_engine* e, int which) {      // which = 0: the student's weights, 1: the EMA teacher's
+    return which ? Weights{e->buf.ema, (const bf16*)e->buf.ema_bf16} : Weights{e->buf.params, (const bf16*)e->buf.params_bf16};
+}
 
-// per-stream parameter offsets (stream 1 = covariance stream of the two-stream model)
-static size_t off_projw(const LayerOff& o, int st) { return st ? o.cprojw : o.projw; }
-static size_t off_projb(const LayerOff& o, int st) { return st ? o.cprojb : o.projb; }
-static size_t off_qb(const LayerOff& o, int st) { return st ? o.cqb : o.qb; }
-static size_t off_vb(const LayerOff& o, int st) { return st ? o.cvb : o.vb; }
-
-// drop-path multipliers: 2 draws per block (base) or 4 (two-stream: mean attn, mean mlp, cov attn, cov mlp;
-// modeling_finetune_dist.py:51-55)
-static const float* dp_ptr(uvit_engine* e, bool on, int l, int st, int branch, int Bc) {
-    if (!on) return nullptr;
-    const int nbr = 2 * e->S, k = e->S == 2 ? 2 * st + branch : branch;
-    return e->dp_scales + (size_t)(nbr * l + k) * Bc;
+// drop-path draw (and sample list) of (layer, stream, branch): 2 draws per block (base) or 4 (two-stream: mean attn, mean mlp, cov attn,
+// cov mlp; modeling_finetune_dist.py:51-55)
+static int dp_draw(const uvit_engine* e, int l, int st, int branch) { return 2 * e->S * l + 2 * st + branch; }
+static const float* dp_ptr(uvit_engine* e, bool on, int l, int st, int branch, int Bc) {      // the draw's multipliers
+    return on ? e->dp_scales + (size_t)dp_draw(e, l, st, branch) * Bc : nullptr;
 }
 
 // Drop-path sample lists (base model, training step with drop_path > 0; round 4).  A branch that dropped a sample adds exactly 0 for it in the
@@ -537,7 +512,7 @@ static const float* dp_ptr(uvit_engine* e, bool on, int l, int st, int branch, i
 // The host evaluates the same integer hash as droppath_kernel to size the launches; the lists themselves are built on the device.
 struct DpList { const int *pos, *bmap, *rows, *cnt; int K; };
 static void dp_list_get(const uvit_engine* e, int l, int st, int branch, DpList& d) {
-    const int lb = 2 * e->S * l + (e->S == 2 ? 2 * st + branch : branch);
+    const int lb = dp_draw(e, l, st, branch);
     d.pos = e->dpl_pos + (size_t)lb * e->B; d.bmap = e->dpl_bmap + (size_t)lb * e->B;
     d.rows = e->dpl_rows + (size_t)lb * e->dpl_stride; d.cnt = e->dpl_cnt + lb; d.K = e->dpl_K[lb];
 }
@@ -596,7 +571,7 @@ static int dp_lists_begin(uvit_engine* e, uint32_t seed, uint32_t it, int Bc, hi
 //                final-norm backward go through the same list).
 // A list runs when it drops somebody and nobody's list drops everybody (nobody dropped: the dense launches; everybody: dense too, 0 x branch).
 enum RowMode { ROWS_ALL, ROWS_LIST, ROWS_LIST2, ROWS_MASKED };
-enum Pass { PASS_DENSE, PASS_TEACHER, PASS_STUDENT };     // drop-in forward or dense-target teacher / teacher of a step / student of a step
+enum Pass { PASS_DENSE, PASS_TEACHER, PASS_STUDENT };     // drop-in forward (as rows: also a dense-target teacher) / teacher of a step / student of a step
 struct BranchRows {
     RowMode mode = ROWS_ALL;
     int K = 0;                    // samples of the attention core
@@ -633,30 +608,60 @@ static BranchRows branch_rows(const uvit_engine* e, int l, int branch, Pass pass
     return r;
 }
 
-static int forward_layer(uvit_engine* e, const Weights& w, int l, const float* x_in, float* x_mid, float* x_out,
-                         LayerActs& a, const float* biasP, bool dp_on, float pdrop, uint32_t seed, int Bc, Pass pass, hipStream_t s) {
+// One forward pass, as its three callers name it: the drop-in forward (uvit_engine_forward_features: either weight set, every layer kept), the teacher of
+// a step (feeds the target builder) and the student of a step (keeps what backward needs).  fwd_pass derives the rest from the call's inputs, once.
+struct Draw { bool on; uint32_t seed, it; };      // train-mode dropout / drop-path of a pass and the (seed, iteration) of its draws
+struct FwdPass {
+    Pass kind;                      // PASS_DENSE: the drop-in forward
+    Pass rows;                      // what branch_rows is asked: the kind, but PASS_DENSE for a teacher whose targets take every patch row
+    int which;                      // weight set: 0 student, 1 EMA teacher
+    Weights w;
+    float* biasP;                   // the weight set's relative-position bias in the attention kernels' layout
+    unsigned* tile_cnt;             // the pass's 16 counters of the persistent GEMMs' dynamic tile assignment
+    Draw draw;
+    bool dp_on; float pdrop;        // drop-path multipliers / attention dropout in effect (train mode and student weights)
+    uint32_t aseed;                 // attention-dropout seed of (seed, it); no kernel reads it while pdrop is 0
+    int Bc; hipStream_t s;
+    const uvit_step_params* hp;     // teacher of a step: the target builder's flags (null otherwise)
+    bool dense;                     // ... and whether stream 0's targets go through the dense (batch- / instance-norm) builder
+};
+static FwdPass fwd_pass(uvit_engine* e, Pass kind, int which, int Bc, Draw draw, const uvit_step_params* hp, hipStream_t s) {
+    FwdPass p;
+    p.kind = kind; p.which = which; p.w = weights_of(e, which); p.biasP = which ? e->biasP_t : e->biasP_s;
+    // The teacher of a step runs beside its student (on the second stream, when there is one): it takes the second block of counters, every
+    // other pass the first.  By the role of the call, not by the stream it is given: calls on one engine are stream-ordered (include/uvit.h).
+    p.tile_cnt = e->tile_cnt + (kind == PASS_TEACHER ? 16 : 0);
+    const bool train = draw.on && !which;
+    p.dp_on = train && e->cfg.drop_path_rate > 0.f; p.pdrop = train ? e->cfg.attn_drop_rate : 0.f;
+    p.aseed = uvit_hash32(draw.seed ^ (draw.it * 0x85EBCA6Bu + 0x1234567u));
+    p.draw = draw; p.Bc = Bc; p.s = s; p.hp = hp;
+    p.dense = hp && (hp->target_batch_norm || hp->target_instance_norm || hp->post_target_instance_norm || !hp->target_layer_norm_last);
+    p.rows = p.dense ? PASS_DENSE : kind;
+    return p;
+}
+
+static int forward_layer(uvit_engine* e, const FwdPass& p, int l, const float* x_in, float* x_mid, float* x_out, LayerActs& a) {
     const LayerOff& o = e->lo.L[l];
-    const int M = Bc * e->N, C = e->C, Hd = e->Hd, S = e->S;
+    const Weights& w = p.w; hipStream_t s = p.s;
+    const int Bc = p.Bc, M = Bc * e->N, C = e->C, Hd = e->Hd, S = e->S;
     const size_t Mp = e->Mpad;                                   // row offset of stream 1 in the residual stream
-    const bool save = pass == PASS_STUDENT;                      // keep what backward needs
-    const BranchRows at = branch_rows(e, l, 0, pass, Bc), ml = branch_rows(e, l, 1, pass, Bc);
-    // counters of the persistent GEMMs' dynamic tile assignment: one block per stream (the teacher and student forwards run side by side)
-    unsigned* const tcnt = e->tile_cnt + ((e->dual && s == e->aux) ? 16 : 0);
+    const bool save = p.kind == PASS_STUDENT;                    // keep what backward needs
+    const BranchRows at = branch_rows(e, l, 0, p.rows, Bc), ml = branch_rows(e, l, 1, p.rows, Bc);
     LnFwd n1; n1.x = x_in; n1.w = w.f + o.n1w; n1.b = w.f + o.n1b; n1.y = a.ln1; n1.mean = a.mean1; n1.rstd = a.rstd1; n1.M = at.rows; n1.C = C;
     n1.eps = e->cfg.ln_eps;
     if (at.mode == ROWS_LIST) { n1.pos = at.d[0].pos; n1.xcopy = x_mid; n1.tokens = e->N; n1.M = M; }      // the dropped rows copied to x_mid
     CHECK(uvit_ln_fwd_launch(n1, s));
     for (int st = 0; st < S; ++st) {     // same qkv.weight for both streams (modeling_finetune_dist.py:121,127)
-        GemmEpi q; q.out = a.qkv + at.off[st] * 3 * C; q.bias = w.f + off_qb(o, st); q.bias2 = w.f + off_vb(o, st); q.ldo = 3 * C;
-        q.tile_counter = tcnt;
+        GemmEpi q; q.out = a.qkv + at.off[st] * 3 * C; q.bias = w.f + o.qb[st]; q.bias2 = w.f + o.vb[st]; q.ldo = 3 * C;
+        q.tile_counter = p.tile_cnt;
         CHECK(GEMM_NT(st ? EPI_QKV_ELU : EPI_QKV, a.ln1 + at.off[st] * C, w.b + o.qkvw, at.n[st], 3 * C, C, C, C, &q, s));
     }
     if (S == 1) {
-        CHECK(uvit_attn_fwd_launch(a.qkv, biasP, a.attn, a.lse, at.K, e->H, e->N, e->NP, e->attn_scale, pdrop, seed, (uint32_t)l, s, at.d[0].bmap,
+        CHECK(uvit_attn_fwd_launch(a.qkv, p.biasP, a.attn, a.lse, at.K, e->H, e->N, e->NP, e->attn_scale, p.pdrop, p.aseed, (uint32_t)l, s, at.d[0].bmap,
                                    e->head_dim));
     } else {
-        CHECK(uvit_attn2_fwd_launch(a.qkv, a.qkv + Mp * 3 * C, biasP, a.attn, a.attn + Mp * C, a.lse, Bc, e->H, e->N, e->NP, 0.125f,
-                                    pdrop, seed, (uint32_t)l, s));
+        CHECK(uvit_attn2_fwd_launch(a.qkv, a.qkv + Mp * 3 * C, p.biasP, a.attn, a.attn + Mp * C, a.lse, Bc, e->H, e->N, e->NP, 0.125f,
+                                    p.pdrop, p.aseed, (uint32_t)l, s));
     }
     // optional HIP-event brackets around the block's forward Linears, each with the rows of its launch (bench.py's roofline block)
     auto prof_begin = [&](int kind, int rows) -> bool {
@@ -667,11 +672,11 @@ static int forward_layer(uvit_engine* e, const Weights& w, int l, const float* x
     };
     auto prof_end = [&](bool on) { if (on) { (void)hipEventRecord(e->prof_ev[e->prof_used + 1], s); e->prof_used += 2; } };
     for (int st = 0; st < S; ++st) {
-        GemmEpi p; p.out = x_mid + st * Mp * C; p.out2 = save ? a.projout + st * Mp * C : nullptr; p.bias = w.f + off_projb(o, st);
-        p.gamma = w.f + o.g1; p.resid = x_in + st * Mp * C; p.rowscale = dp_ptr(e, dp_on, l, st, 0, Bc); p.ldo = C; p.tokens = e->N;
-        p.rowmap = at.rowmap[st]; p.rowcount = at.rowcnt[st];
+        GemmEpi pj; pj.out = x_mid + st * Mp * C; pj.out2 = save ? a.projout + st * Mp * C : nullptr; pj.bias = w.f + o.projb[st];
+        pj.gamma = w.f + o.g1; pj.resid = x_in + st * Mp * C; pj.rowscale = dp_ptr(e, p.dp_on, l, st, 0, Bc); pj.ldo = C; pj.tokens = e->N;
+        pj.rowmap = at.rowmap[st]; pj.rowcount = at.rowcnt[st];
         const bool pp = prof_begin(UVIT_PROF_PROJ, at.n[st]);
-        CHECK(GEMM_NT(EPI_RESID, a.attn + at.off[st] * C, w.b + off_projw(o, st), at.n[st], C, C, C, C, &p, s));
+        CHECK(GEMM_NT(EPI_RESID, a.attn + at.off[st] * C, w.b + o.projw[st], at.n[st], C, C, C, C, &pj, s));
         prof_end(pp);
     }
     LnFwd n2; n2.x = x_mid; n2.w = w.f + o.n2w; n2.b = w.f + o.n2b; n2.y = a.ln2; n2.mean = a.mean2; n2.rstd = a.rstd2; n2.M = ml.rows; n2.C = C;
@@ -687,14 +692,14 @@ static int forward_layer(uvit_engine* e, const Weights& w, int l, const float* x
         n2.rowidx = ml.rowmap[0]; n2.count = ml.rowcnt[0];
         CHECK(uvit_ln_fwd_launch(n2, s));
     }
-    GemmEpi f1; f1.out = a.a; f1.out2 = save ? a.h : nullptr; f1.bias = w.f + o.fc1b; f1.ldo = Hd; f1.tile_counter = tcnt;
+    GemmEpi f1; f1.out = a.a; f1.out2 = save ? a.h : nullptr; f1.bias = w.f + o.fc1b; f1.ldo = Hd; f1.tile_counter = p.tile_cnt;
     const bool prof = prof_begin(save ? UVIT_PROF_FC1_S : UVIT_PROF_FC1_T, ml.rows);
     // student (save): a.h receives gelu'(h) -- all that backward needs of h -- computed beside gelu(h)
     CHECK(GEMM_NT(save ? EPI_GELU_DG : EPI_GELU, a.ln2, w.b + o.fc1w, ml.rows, Hd, C, C, C, &f1, s));
     prof_end(prof);
     for (int st = 0; st < S; ++st) {
         GemmEpi f2; f2.out = x_out + st * Mp * C; f2.out2 = save ? a.mlpout + st * Mp * C : nullptr; f2.bias = w.f + o.fc2b;
-        f2.gamma = w.f + o.g2; f2.resid = x_mid + st * Mp * C; f2.rowscale = dp_ptr(e, dp_on, l, st, 1, Bc); f2.ldo = C; f2.tokens = e->N;
+        f2.gamma = w.f + o.g2; f2.resid = x_mid + st * Mp * C; f2.rowscale = dp_ptr(e, p.dp_on, l, st, 1, Bc); f2.ldo = C; f2.tokens = e->N;
         f2.rowmap = ml.rowmap[st]; f2.rowcount = ml.rowcnt[st];
         const bool pf2 = prof_begin(UVIT_PROF_FC2, ml.n[st]);
         CHECK(GEMM_NT(EPI_RESID, a.a + ml.off[st] * Hd, w.b + o.fc2w, ml.n[st], C, Hd, Hd, Hd, &f2, s));
@@ -707,92 +712,86 @@ static int forward_layer(uvit_engine* e, const Weights& w, int l, const float* x
 static int embed(uvit_engine* e, const Weights& w, const int64_t* mask, float* x0, int Bc, hipStream_t s) {
     for (int st = 0; st < e->S; ++st) {
         float* x = x0 + (size_t)st * e->Mpad * e->C;
-        GemmEpi pe; pe.out = x; pe.bias = w.f + (st ? e->lo.cpeb : e->lo.peb); pe.mask = mask;
-        pe.mask_token = w.f + (st ? e->lo.cmask_tok : e->lo.mask_tok); pe.ldo = e->C; pe.patches = e->P;
-        CHECK(GEMM_NT(EPI_PATCH, e->cols, w.b + (st ? e->lo.cpew : e->lo.pew), Bc * e->P, e->C, e->Kpe, e->Kpe, e->Kpe, &pe, s));
-        CHECK(uvit_set_cls_launch(x, w.f + (st ? e->lo.ccls : e->lo.cls), nullptr, Bc, e->N, e->C, s));
+        GemmEpi pe; pe.out = x; pe.bias = w.f + e->lo.peb[st]; pe.mask = mask; pe.mask_token = w.f + e->lo.mask_tok[st]; pe.ldo = e->C; pe.patches = e->P;
+        CHECK(GEMM_NT(EPI_PATCH, e->cols, w.b + e->lo.pew[st], Bc * e->P, e->C, e->Kpe, e->Kpe, e->Kpe, &pe, s));
+        CHECK(uvit_set_cls_launch(x, w.f + e->lo.cls[st], nullptr, Bc, e->N, e->C, s));
         // x = x + pos_embed (modeling_cyclical.py:193-194; --abs_pos_emb, off in every BASELINE config)
         if (e->cfg.use_abs_pos_emb) CHECK(uvit_add_pos_launch(x, w.f + e->lo.pos, Bc, e->N, e->C, s));
     }
     return UVIT_OK;
 }
 
-static int run_forward(uvit_engine* e, int which, const float* images, const int64_t* mask, int Bc, bool save_student,
-                       bool dropout, uint32_t seed, uint32_t it, const uvit_step_params* hp_targets, bool cols_ready,
-                       hipStream_t s) {
+// Target builder of a step's teacher pass (engine_for_cyclical.py:92-122): what follows teacher layer l, and the finalisation.
+struct TargetBuild { bool dense; int n; };      // FwdPass::dense; target layers accumulated so far
+static int targets_after_layer(uvit_engine* e, const FwdPass& p, TargetBuild& t, int l, const float* xout) {
+    const uvit_step_params* hp = p.hp; const int Bc = p.Bc; hipStream_t s = p.s;
+    if (t.dense && Bc != e->B) return UVIT_ERR_ARG;
+    // `[targets[i] for i in target_layers]` (engine_for_cyclical.py:92): a layer listed twice is summed twice and the
+    // mean divides by len(target_layers); the host has already mapped negative indices and refused out-of-range ones
+    for (int k = 0; k < hp->n_target_layers; ++k) {
+        if (hp->target_layers[k] != l) continue;
+        const float* sub = hp->layer_results_fc ? e->tXM : nullptr;     // --layer_results fc: x_out - x_mid
+        // Stream 0 (the only one of the base model; the MEAN targets of a stochastic step, engine_for_cyclical.py:93-118)
+        // takes the dense builder when a batch- / instance-norm variant is on; the covariance targets (:73-86) only know
+        // `target_layer_norm_last` and `post_target_layer_norm` and always go through the masked-row builder.
+        for (int st = t.dense ? 1 : 0; st < e->S; ++st)
+            CHECK(uvit_target_accum_launch(xout + (size_t)st * e->Mpad * e->C, e->rowidx, e->count, e->targets[st], t.n == 0,
+                                           Bc * e->P, e->C, 1e-5f, s, sub ? sub + (size_t)st * e->Mpad * e->C : nullptr,
+                                           hp->target_layer_norm_last ? 1 : 0));
+        if (t.dense) {
+            // all patch tokens of this layer -> [batch norm] -> [instance norm] -> [LayerNorm] -> accumulate
+            CHECK(uvit_gather_patch_rows_launch(xout, sub, e->dense_v, Bc, e->P, e->C, s));
+            if (hp->target_batch_norm) CHECK(uvit_colnorm_launch(e->dense_v, 1, Bc * e->P, e->C, 1e-5f, s));
+            if (hp->target_instance_norm) CHECK(uvit_colnorm_launch(e->dense_v, Bc, e->P, e->C, 1e-5f, s));
+            if (hp->target_layer_norm_last)
+                CHECK(uvit_target_accum_launch(e->dense_v, e->idrows, e->idcount, e->dense_acc, t.n == 0, Bc * e->P, e->C, 1e-5f, s));
+            else CHECK(uvit_axpy_rows_launch(e->dense_acc, e->dense_v, t.n == 0, (size_t)Bc * e->P * e->C, s));
+        }
+        ++t.n;
+    }
+    return UVIT_OK;
+}
+static int targets_finalize(uvit_engine* e, const FwdPass& p, const TargetBuild& t) {
+    const uvit_step_params* hp = p.hp; const int Bc = p.Bc; hipStream_t s = p.s;
+    if (t.n != hp->n_target_layers) return UVIT_ERR_ARG;     // an index outside [0, depth) reached the C ABI
+    for (int st = t.dense ? 1 : 0; st < e->S; ++st)
+        CHECK(uvit_target_finalize_launch(e->targets[st], e->count, t.n, hp->post_target_layer_norm, Bc * e->P, e->C, 1e-5f, s));
+    if (t.dense) {
+        const bool pin = hp->post_target_instance_norm != 0;
+        CHECK(uvit_target_finalize_launch(e->dense_acc, e->idcount, t.n, hp->post_target_layer_norm && !pin, Bc * e->P, e->C, 1e-5f, s));
+        if (pin) {
+            CHECK(uvit_colnorm_launch(e->dense_acc, Bc, e->P, e->C, 1e-5f, s));
+            if (hp->post_target_layer_norm)
+                CHECK(uvit_target_finalize_launch(e->dense_acc, e->idcount, 1, 1, Bc * e->P, e->C, 1e-5f, s));
+        }
+        CHECK(uvit_gather_masked_rows_launch(e->dense_acc, e->rowidx, e->count, e->targets[0], Bc * e->P, e->P, e->C, s));
+    }
+    return UVIT_OK;
+}
+
+static int run_forward(uvit_engine* e, const FwdPass& p, const float* images, const int64_t* mask) {
+    const int Bc = p.Bc; hipStream_t s = p.s;
     if (Bc < 1 || Bc > e->B) return UVIT_ERR_SHAPE;
-    const bool teacher = which == 1;
-    Weights w{teacher ? e->buf.ema : e->buf.params, (const bf16*)(teacher ? e->buf.ema_bf16 : e->buf.params_bf16)};
-    if (!cols_ready) CHECK(uvit_im2col_launch(images, e->cols, Bc, e->cfg.in_chans, e->cfg.img_size, e->cfg.patch_size, s));
-    float* biasP = teacher ? e->biasP_t : e->biasP_s;
-    CHECK(uvit_relpos_gather_launch(e->cfg.use_shared_rel_pos_bias ? w.f + e->lo.relt : nullptr, e->buf.rel_index, biasP,
+    // (a step builds the patch columns once, for both of its passes)
+    if (p.kind == PASS_DENSE) CHECK(uvit_im2col_launch(images, e->cols, Bc, e->cfg.in_chans, e->cfg.img_size, e->cfg.patch_size, s));
+    CHECK(uvit_relpos_gather_launch(e->cfg.use_shared_rel_pos_bias ? p.w.f + e->lo.relt : nullptr, e->buf.rel_index, p.biasP,
                                     e->H, e->N, e->NP, s));
-    const bool dp_on = dropout && !teacher && e->cfg.drop_path_rate > 0.f;
-    const float pdrop = (dropout && !teacher) ? e->cfg.attn_drop_rate : 0.f;
-    if (dp_on) CHECK(uvit_droppath_launch(e->dp_scales, e->dp_rates, e->cfg.depth, 2 * e->S, Bc, seed, it, s));
-    if (!teacher) {
+    if (p.dp_on) CHECK(uvit_droppath_launch(e->dp_scales, e->dp_rates, e->cfg.depth, 2 * e->S, Bc, p.draw.seed, p.draw.it, s));
+    if (!p.which) {
         e->dpl_on = false;
-        if (dp_on && save_student && e->dpl_enable && Bc == e->B) CHECK(dp_lists_begin(e, seed, it, Bc, s));
+        if (p.dp_on && p.kind == PASS_STUDENT && e->dpl_enable && Bc == e->B) CHECK(dp_lists_begin(e, p.draw.seed, p.draw.it, Bc, s));
+        e->last_dropout = p.draw.on; e->last_seed = p.aseed;
     }
-    const uint32_t aseed = uvit_hash32(seed ^ (it * 0x85EBCA6Bu + 0x1234567u));
-    if (!teacher) { e->last_dropout = dropout; e->last_seed = aseed; e->last_it = it; }
-    const bool use_saved = !teacher || !hp_targets;   // drop-in forward keeps every layer for either weight set
-    float* x0 = use_saved ? e->X[0] : e->tX[0];
-    CHECK(embed(e, w, mask, x0, Bc, s));
-    int n_t = 0;
+    // the teacher of a step alternates between two residual streams and keeps nothing; every other pass keeps every layer
+    const bool keep = p.kind != PASS_TEACHER;
+    CHECK(embed(e, p.w, mask, keep ? e->X[0] : e->tX[0], Bc, s));
+    TargetBuild tb{p.dense, 0};
     for (int l = 0; l < e->cfg.depth; ++l) {
-        if (use_saved) {
-            CHECK(forward_layer(e, w, l, e->X[l], e->XM[l], e->X[l + 1], e->acts[l], biasP, dp_on, pdrop, aseed, Bc,
-                                save_student && !teacher ? PASS_STUDENT : PASS_DENSE, s));
-        } else {
-            float* xin = e->tX[l & 1]; float* xout = e->tX[(l + 1) & 1];
-            // `[targets[i] for i in target_layers]` (engine_for_cyclical.py:92): a layer listed twice is summed twice and the
-            // mean divides by len(target_layers); the host has already mapped negative indices and refused out-of-range ones
-            const bool dense = hp_targets->target_batch_norm || hp_targets->target_instance_norm ||
-                               hp_targets->post_target_instance_norm || !hp_targets->target_layer_norm_last;
-            // the teacher's last block feeds nothing but the target rows: with a masked-row bound its MLP runs on those rows only
-            CHECK(forward_layer(e, w, l, xin, e->tXM, xout, e->tacts, biasP, false, 0.f, 0, Bc, dense ? PASS_DENSE : PASS_TEACHER, s));
-            if (dense && Bc != e->B) return UVIT_ERR_ARG;
-            for (int k = 0; k < hp_targets->n_target_layers; ++k) {
-                if (hp_targets->target_layers[k] != l) continue;
-                const float* sub = hp_targets->layer_results_fc ? e->tXM : nullptr;     // --layer_results fc: x_out - x_mid
-                // Stream 0 (the only one of the base model; the MEAN targets of a stochastic step, engine_for_cyclical.py:93-118)
-                // takes the dense builder when a batch- / instance-norm variant is on; the covariance targets (:73-86) only know
-                // `target_layer_norm_last` and `post_target_layer_norm` and always go through the masked-row builder.
-                for (int st = dense ? 1 : 0; st < e->S; ++st)
-                    CHECK(uvit_target_accum_launch(xout + (size_t)st * e->Mpad * e->C, e->rowidx, e->count, e->targets[st], n_t == 0,
-                                                   Bc * e->P, e->C, 1e-5f, s, sub ? sub + (size_t)st * e->Mpad * e->C : nullptr,
-                                                   hp_targets->target_layer_norm_last ? 1 : 0));
-                if (dense) {
-                    // all patch tokens of this layer -> [batch norm] -> [instance norm] -> [LayerNorm] -> accumulate
-                    CHECK(uvit_gather_patch_rows_launch(xout, sub, e->dense_v, Bc, e->P, e->C, s));
-                    if (hp_targets->target_batch_norm) CHECK(uvit_colnorm_launch(e->dense_v, 1, Bc * e->P, e->C, 1e-5f, s));
-                    if (hp_targets->target_instance_norm) CHECK(uvit_colnorm_launch(e->dense_v, Bc, e->P, e->C, 1e-5f, s));
-                    if (hp_targets->target_layer_norm_last)
-                        CHECK(uvit_target_accum_launch(e->dense_v, e->idrows, e->idcount, e->dense_acc, n_t == 0, Bc * e->P, e->C, 1e-5f, s));
-                    else CHECK(uvit_axpy_rows_launch(e->dense_acc, e->dense_v, n_t == 0, (size_t)Bc * e->P * e->C, s));
-                }
-                ++n_t;
-            }
-        }
+        float* xout = keep ? e->X[l + 1] : e->tX[(l + 1) & 1];
+        CHECK(forward_layer(e, p, l, keep ? e->X[l] : e->tX[l & 1], keep ? e->XM[l] : e->tXM, xout, keep ? e->acts[l] : e->tacts));
+        if (!keep) CHECK(targets_after_layer(e, p, tb, l, xout));
     }
-    if (teacher && hp_targets) {
-        if (n_t != hp_targets->n_target_layers) return UVIT_ERR_ARG;     // an index outside [0, depth) reached the C ABI
-        const bool dense = hp_targets->target_batch_norm || hp_targets->target_instance_norm ||
-                           hp_targets->post_target_instance_norm || !hp_targets->target_layer_norm_last;
-        for (int st = dense ? 1 : 0; st < e->S; ++st)
-            CHECK(uvit_target_finalize_launch(e->targets[st], e->count, n_t, hp_targets->post_target_layer_norm, Bc * e->P, e->C, 1e-5f, s));
-        if (dense) {
-            const bool pin = hp_targets->post_target_instance_norm != 0;
-            CHECK(uvit_target_finalize_launch(e->dense_acc, e->idcount, n_t, hp_targets->post_target_layer_norm && !pin, Bc * e->P, e->C, 1e-5f, s));
-            if (pin) {
-                CHECK(uvit_colnorm_launch(e->dense_acc, Bc, e->P, e->C, 1e-5f, s));
-                if (hp_targets->post_target_layer_norm)
-                    CHECK(uvit_target_finalize_launch(e->dense_acc, e->idcount, 1, 1, Bc * e->P, e->C, 1e-5f, s));
-            }
-            CHECK(uvit_gather_masked_rows_launch(e->dense_acc, e->rowidx, e->count, e->targets[0], Bc * e->P, e->P, e->C, s));
-        }
-    }
+    if (!keep) CHECK(targets_finalize(e, p, tb));
     e->cur_B = Bc;
     return UVIT_OK;
 }
@@ -802,14 +801,15 @@ extern "C" int uvit_engine_forward_features(uvit_engine* e, int which, const flo
     if (!e || !images || (which != 0 && which != 1)) return UVIT_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (mask) CHECK(uvit_mask_compact_launch(mask, e->rowidx, e->count, batch, e->P, s));
-    return run_forward(e, which, images, mask, batch, false, train_dropout != 0, seed, it, nullptr, false, s);
+    const FwdPass drop_in = fwd_pass(e, PASS_DENSE, which, batch, Draw{train_dropout != 0, seed, it}, nullptr, s);
+    return run_forward(e, drop_in, images, mask);
 }
 
 // final norm (shared) + drop cls + masked-row gather + per-stream head (modeling_cyclical.py:207,215-225)
 static int head_forward(uvit_engine* e, const Weights& w, int Bc, int st, bool all_tokens, float* out, hipStream_t s, int rows = 0) {
     const int BP = rows > 0 ? rows : Bc * e->P;        // rows > 0: a host-side bound on the masked rows (training step with n_rows_hint)
     const float* x = e->X[e->cfg.depth] + (size_t)st * e->Mpad * e->C;
-    const size_t lmw = st ? e->lo.clmw : e->lo.lmw, lmb = st ? e->lo.clmb : e->lo.lmb;
+    const size_t lmw = e->lo.lmw[st], lmb = e->lo.lmb[st];
     LnFwd fn; fn.x = x; fn.w = w.f + e->lo.normw; fn.b = w.f + e->lo.normb; fn.C = e->C; fn.eps = e->cfg.ln_eps;
     if (all_tokens) {
         // normalise all tokens, then run the head on the patch rows of each sample
@@ -832,11 +832,9 @@ static int head_forward(uvit_engine* e, const Weights& w, int Bc, int st, bool a
 extern "C" int uvit_engine_head(uvit_engine* e, int which, int all_tokens, float* out, int32_t* count_dev, uvit_stream stream) {
     if (!e || !out) return UVIT_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const bool teacher = (which & 1) != 0;
     const int st = (which >> 1) & 1;                     // bit 1 selects the covariance stream of the two-stream model
     if (st >= e->S) return UVIT_ERR_ARG;
-    Weights w{teacher ? e->buf.ema : e->buf.params, (const bf16*)(teacher ? e->buf.ema_bf16 : e->buf.params_bf16)};
-    CHECK(head_forward(e, w, e->cur_B, st, all_tokens != 0, out, s));
+    CHECK(head_forward(e, weights_of(e, which & 1), e->cur_B, st, all_tokens != 0, out, s));
     if (count_dev && !all_tokens) HIPCHECK(hipMemcpyAsync(count_dev, e->count, sizeof(int), hipMemcpyDeviceToDevice, s));
     return UVIT_OK;
 }
@@ -915,12 +913,13 @@ extern "C" int uvit_step_begin(uvit_engine* e, const float* images, const int64_
     // teacher (EMA weights, eval mode, no grad: engine_for_cyclical.py:68-122) runs on the second stream,
     // beside the student forward (engine_for_cyclical.py:124-128); they share only read-only inputs
     if (e->dual) { HIPCHECK(hipEventRecord(e->ev_fork, s)); HIPCHECK(hipStreamWaitEvent(ts, e->ev_fork, 0)); }   // im2col / mask list
-    CHECK(run_forward(e, 1, images, nullptr, Bc, false, false, 0, 0, hp, true, ts));
+    const FwdPass teacher = fwd_pass(e, PASS_TEACHER, 1, Bc, Draw{false, 0, 0}, hp, ts);
+    const FwdPass student = fwd_pass(e, PASS_STUDENT, 0, Bc, Draw{hp->train_dropout != 0, hp->seed, hp->it}, nullptr, s);
+    CHECK(run_forward(e, teacher, images, nullptr));
     if (e->dual) HIPCHECK(hipEventRecord(e->ev_teacher, ts));
-    CHECK(run_forward(e, 0, images, mask, Bc, true, hp->train_dropout != 0, hp->seed, hp->it, nullptr, true, s));
-    Weights w{e->buf.params, (const bf16*)e->buf.params_bf16};
+    CHECK(run_forward(e, student, images, mask));
     const int Rh = e->compact_R > 0 ? e->compact_R : BP;      // rows of the head and of its backward (rows beyond the device-side count are zero)
-    for (int st = 0; st < e->S; ++st) CHECK(head_forward(e, w, Bc, st, false, e->outputs[st], s, e->compact_R));
+    for (int st = 0; st < e->S; ++st) CHECK(head_forward(e, student.w, Bc, st, false, e->outputs[st], s, e->compact_R));
     if (e->dual) HIPCHECK(hipStreamWaitEvent(s, e->ev_teacher, 0));
     // loss + dLoss/dOutputs: engine_for_cyclical.py:130-163 (+ WassersteinLoss for the two-stream model, :152-161)
     const float ls = hp->loss_scale == -1.0f ? 1.0f : hp->loss_scale;
@@ -937,7 +936,7 @@ extern "C" int uvit_step_begin(uvit_engine* e, const float* images, const int64_
     float* g = e->buf.grads;
     const bf16* wt = (const bf16*)e->buf.params_bf16_t;
     for (int st = 0; st < e->S; ++st) {
-        const size_t lmw = st ? lo.clmw : lo.lmw, lmb = st ? lo.clmb : lo.lmb;
+        const size_t lmw = lo.lmw[st], lmb = lo.lmb[st];
         // lm_head weight gradient + bias column sum: one launch of the grouped wgrad kernel when the shapes qualify (was a column-sum launch
         // and the plain TN kernel, 50 us, on the critical chain between the loss and the first dgrad)
         TnProb hw; hw.Y = e->dout[st]; hw.X = e->normed[st]; hw.C = g + lmw; hw.M = e->compact_R > 0 ? e->compact_R : e->BPpad; hw.Nn = C; hw.Kk = C;
@@ -993,14 +992,14 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
         TnProb& f1 = wg[nwg++]; f1.Y = dH; f1.X = a.ln2; f1.C = g + o.fc1w; f1.M = ml.red; f1.Nn = Hd; f1.Kk = C; f1.ldy = Hd; f1.ldx = C; f1.ldc = C;
         f1.bias = RP(o.fc1b); f1.bias_end = Hd;
         for (int st = 0; st < S; ++st) {
-            TnProb& pj = wg[nwg++]; pj.Y = dY2 + at.off[st] * C; pj.X = a.attn + at.off[st] * C; pj.C = g + off_projw(o, st);
+            TnProb& pj = wg[nwg++]; pj.Y = dY2 + at.off[st] * C; pj.X = a.attn + at.off[st] * C; pj.C = g + o.projw[st];
             pj.M = (int)roundup(at.n[st], 64); pj.Nn = C; pj.Kk = C; pj.ldy = C; pj.ldx = C; pj.ldc = C;
         }
         TnProb& qk = wg[nwg++]; qk.Y = dqkv; qk.X = a.ln1; qk.C = g + o.qkvw; qk.M = at.red; qk.Nn = 3 * C; qk.Kk = C; qk.ldy = 3 * C; qk.ldx = C; qk.ldc = C;
-        qk.bias = RP(off_qb(o, 0)); qk.bias_end = C; qk.bias2 = RP(off_vb(o, 0)); qk.bias2_begin = 2 * C;
+        qk.bias = RP(o.qb[0]); qk.bias_end = C; qk.bias2 = RP(o.vb[0]); qk.bias2_begin = 2 * C;
         // two-stream: the q / v biases differ per stream while the stacked wgrad reduces over both: the token chunks of stream 1
         // (rows from Mpad on) sum into the covariance stream's biases (round 4; was 4 colsum launches per layer)
-        if (S == 2) { qk.bias_s1 = RP(off_qb(o, 1)); qk.bias2_s1 = RP(off_vb(o, 1)); qk.s1_row = (int)Mp; }
+        if (S == 2) { qk.bias_s1 = RP(o.qb[1]); qk.bias2_s1 = RP(o.vb[1]); qk.s1_row = (int)Mp; }
     }
     // --- MLP branch: x_out = x_mid + dp * gamma2 * fc2(gelu(fc1(ln2(x_mid))))   (weights shared by the streams)
     // (the LayerScale backward of a branch rides in the LayerNorm backward that produces its input -- below the top layer, the MLP branch's
@@ -1032,14 +1031,14 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
         b.dres = e->dXa + eo; b.dx = e->dXb + eo; b.dw = RP(o.n2w); b.db = RP(o.n2b); b.C = C; b.nrep = NREP; b.rep_stride = e->n_nd;
         LsNext& n = b.next;
         n.y = a.projout + eo; n.gamma = pf + o.g1; n.rowscale = dp_ptr(e, dp_on, l, st, 0, e->B); n.dy = dY2 + at.off[st] * C;
-        n.dgamma = RP(o.g1); n.dbias = RP(off_projb(o, st)); n.tokens = e->N; n.pos = at.d[st].pos;
+        n.dgamma = RP(o.g1); n.dbias = RP(o.projb[st]); n.tokens = e->N; n.pos = at.d[st].pos;
         if (ln2_samples) { b.M = M; b.pos = ml.d[st].pos; n.cnt = at.d[st].cnt; if (at.mode == ROWS_LIST) { n.pad2 = dqkv; n.pad2_cols = 3 * C; } }
         else { b.M = ml.n[st]; b.rowidx = ml.rowmap[st]; b.count = ml.rowcnt[st]; }
         CHECK(uvit_ln_bwd_launch(b, s));
     }
     for (int st = 0; st < S; ++st) {
         GemmEpi d3; d3.out = e->dAttn + at.off[st] * C; d3.ldo = C;
-        CHECK(GEMM_NT(EPI_BF16, dY2 + at.off[st] * C, wt + off_projw(o, st), at.n[st], C, C, C, C, &d3, s));
+        CHECK(GEMM_NT(EPI_BF16, dY2 + at.off[st] * C, wt + o.projw[st], at.n[st], C, C, C, C, &d3, s));
     }
     const float* biasP = e->biasP_s;
     float* slabs = e->cfg.use_shared_rel_pos_bias ? e->slabs : nullptr;
@@ -1105,10 +1104,9 @@ extern "C" int uvit_step_backward_embed(uvit_engine* e, uvit_stream stream) {
     // very end of backward) when the shapes qualify
     TnProb pe[2];
     for (int st = 0; st < e->S; ++st) {
-        CHECK(uvit_token_bwd_launch(e->dXa + (size_t)st * e->Mpad * C, e->mask_copy, e->dpatch[st], g + (st ? lo.ccls : lo.cls),
-                                    g + (st ? lo.cmask_tok : lo.mask_tok), e->B, e->P, C, s));
-        TnProb& q = pe[st]; q.Y = e->dpatch[st]; q.X = e->cols; q.C = g + (st ? lo.cpew : lo.pew); q.M = (int)roundup(BP, 64); q.Nn = C; q.Kk = e->Kpe;
-        q.ldy = C; q.ldx = e->Kpe; q.ldc = e->Kpe; q.bias = RP(st ? lo.cpeb : lo.peb); q.bias_end = C;
+        CHECK(uvit_token_bwd_launch(e->dXa + (size_t)st * e->Mpad * C, e->mask_copy, e->dpatch[st], g + lo.cls[st], g + lo.mask_tok[st], e->B, e->P, C, s));
+        TnProb& q = pe[st]; q.Y = e->dpatch[st]; q.X = e->cols; q.C = g + lo.pew[st]; q.M = (int)roundup(BP, 64); q.Nn = C; q.Kk = e->Kpe;
+        q.ldy = C; q.ldx = e->Kpe; q.ldc = e->Kpe; q.bias = RP(lo.peb[st]); q.bias_end = C;
     }
     CHECK(wgrad(e, pe, e->S, s));
     if (e->cfg.use_abs_pos_emb) CHECK(uvit_pos_bwd_launch(e->dXa, g + lo.pos, e->B, e->N, C, s));     // d pos_embed = sum_b dX[b]
@@ -1120,7 +1118,6 @@ extern "C" int uvit_step_backward_embed(uvit_engine* e, uvit_stream stream) {
     CHECK(uvit_poison_if_nonfinite_launch(e->loss, g + lo.n_decay, e->poisoned, s));     // non-finite loss -> every rank's norm is NaN
     return UVIT_OK;
 }
-
 
 extern "C" int uvit_step_wait_layer_grads(uvit_engine* e, int layer, uvit_stream stream) {
     if (!e || layer < 0 || layer >= e->cfg.depth) return UVIT_ERR_ARG;
