@@ -279,3 +279,154 @@ def full_size_step_properties(cfg_drop, cfg_nodrop, B, img, n_patches, n_mask, t
         rl2 = float((gfull[n] - ref).norm() / (ref.norm() + 1e-30))
         assert rl2 <= 2e-2, (n, "relative L2", rl2)
     return st
+
+
+# ---- the multi-step epoch of tests/test_gpu_epoch.py (its properties are asserted without a GPU by tests/test_host_epoch.py) ----
+# One train_one_epoch call: 9 iterations from global iteration 3 (step != it; more than two laps of the 4-slot metrics ring).  The lr and
+# weight-decay tables are indexed by GLOBAL iteration, neighbouring entries a factor >= 2 apart and not monotone, no lr entry equal to a
+# weight-decay or EMA-decay value: a scalar read at a neighbouring index, or from another row of the device table, is far outside every bound.
+# EMA: iterations 3..6 anneal (it < ema_start_at), 7..9 keep the value of iteration 6, 10..11 skip the update (it > start_lr_decay_at_step).
+# n_mask / scale: masked patches per image and image scale of batch i.  The targets are layer-normed rows, so at the closed-form weights every
+# batch of noise images has a loss near 0.28 whatever its scale; what moves the loss is learning.  The images of scale 0.02 are nearly constant:
+# their targets are nearly one vector, which the student learns within a step, while the scale-2 noise batches between them stay near 0.28 --
+# consecutive losses are >= 25 % apart, and not monotone.
+EPOCH = dict(cfg=dict(img_size=48, embed_dim=128, depth=2, num_heads=2), B=3, target_layers=[1], start_steps=3, n_iters=9,
+             ema_start_at=7, decay_init=0.99, decay=0.9998, start_lr_decay_at_step=9, max_norm=3.0, betas=(0.9, 0.999), eps=1e-8,
+             lr=[7.5e-4, 2e-4, 6e-4, 1.5e-3, 5e-4, 1.25e-3, 2.5e-4, 1e-3, 4e-4, 1.4e-3, 4.5e-4, 1.2e-3],
+             wd=[0.05, 0.2, 0.02, 0.1, 0.03, 0.12, 0.04, 0.16, 0.01, 0.08, 0.025, 0.11],
+             n_mask=[2, 7, 3, 8, 1, 6, 2, 8, 4], scale=[0.02, 0.02, 2.0, 0.02, 2.0, 0.02, 2.0, 0.02, 2.0])
+
+
+def epoch_cfg():
+    return vo.VitConfig(init_values=0.1, **EPOCH["cfg"])
+
+
+def epoch_batch(i, tag="epoch"):
+    """(images, mask) of iteration i of the epoch: CPU tensors."""
+    from oracle.closed_form import closed_form_images, exact_masks
+    cfg = epoch_cfg()
+    return (closed_form_images(f"{tag}/{i}", EPOCH["B"], cfg.img_size, EPOCH["scale"][i % len(EPOCH["scale"])]),
+            exact_masks(EPOCH["B"], cfg.num_patches, EPOCH["n_mask"][i % len(EPOCH["n_mask"])], 200 + i))
+
+
+def epoch_table(optimizer=None):
+    """[(lr, weight_decay, ema_decay or -1.0)] of the epoch's iterations, from the product's epoch_scalars (float32 values)."""
+    from types import SimpleNamespace
+    from uncertainty_vit_amd.engine_for_cyclical import epoch_scalars
+    E = EPOCH
+    opt = optimizer or SimpleNamespace(param_groups=[dict(lr=Args.lr, weight_decay=Args.weight_decay, lr_scale=1.0)])
+    return epoch_scalars(opt, E["start_steps"], E["n_iters"], E["lr"], E["wd"], E["ema_start_at"], E["decay_init"], E["decay"],
+                         E["start_lr_decay_at_step"])
+
+
+_oracle_epoch = None
+
+
+def oracle_epoch():
+    """The epoch in the oracle, computed once per process: per-iteration (loss, grad_norm) lists.  A skipped EMA update is decay = 1.0,
+    which leaves the oracle's teacher bit for bit (1.0 * e + 0.0 * p)."""
+    global _oracle_epoch
+    if _oracle_epoch is None:
+        cfg = epoch_cfg()
+        p, e, m, v = oracle_state(closed_form_state(vo.param_shapes(cfg), gamma=cfg.init_values))
+        hp = vo.StepHParams(target_layers=tuple(EPOCH["target_layers"]), clip_grad=EPOCH["max_norm"], betas=EPOCH["betas"], eps=EPOCH["eps"])
+        loss, gnorm = [], []
+        for i, (lr, wd, d) in enumerate(epoch_table()):
+            if d < 0:
+                before = {k: t.clone() for k, t in e.items()}
+            x, mask = epoch_batch(i)
+            r = vo.train_step(p, e, m, v, cfg, hp, x, mask, i + 1, lr=lr, wd=wd, decay=1.0 if d < 0 else d)
+            if d < 0:
+                assert all(torch.equal(before[k], e[k]) for k in e)
+            loss.append(r.loss)
+            gnorm.append(r.grad_norm)
+        _oracle_epoch = (loss, gnorm)
+    return _oracle_epoch
+
+
+def epoch_run(model, ema, opt, loader, writer, **kw):
+    """One train_one_epoch call with the EPOCH schedules (kw overrides) over `loader`."""
+    from uncertainty_vit_amd import engine_for_cyclical as eng, utils
+    E = EPOCH
+    args = dict(max_norm=E["max_norm"], l1_beta=2.0, log_writer=writer, start_steps=E["start_steps"], lr_schedule_values=E["lr"],
+                wd_schedule_values=E["wd"], start_lr_decay_at_step=E["start_lr_decay_at_step"], target_layer_norm_last=True,
+                post_target_layer_norm=True)
+    args.update(kw)
+    return eng.train_one_epoch(model, ema, E["ema_start_at"], E["decay_init"], E["decay"], E["target_layers"], loader, opt,
+                               torch.device("cuda"), 0, utils.NativeScalerWithGradNormCount(), **args)
+
+
+class RecordingLoader:
+    """An iterable of ((images, mask), label) batches that records the training state each time the next batch is requested.
+
+    DevicePrefetcher.__iter__ asks for batch k on the compute stream after steps 0 .. k-2 have been enqueued and before step k-1 is, so
+    snapshot k (clones enqueued on the current stream: no synchronisation, no launch between two steps' kernels other than the copies)
+    is the state after k-1 steps with the raw gradients, the loss words and compact_rows() of step k-2.  When the loader runs out, one
+    more snapshot is taken (index n: after n-1 steps); the test appends the last one after the epoch has returned."""
+
+    def __init__(self, batches, model, ema, opt):
+        self.batches, self.model, self.ema, self.opt = list(batches), model, ema, opt
+        self.requested, self.snapshots = [], []
+
+    def __len__(self):
+        return len(self.batches)
+
+    def snapshot(self):
+        m, e = self.model, self.model._engine
+        s = {"params": m._arena.clone(), "teacher": self.ema.module._arena.clone()}
+        if self.opt.exp_avg is not None:
+            s["m"], s["v"] = self.opt.exp_avg.clone(), self.opt.exp_avg_sq.clone()
+        if m._grad_arena is not None:
+            s["grads"] = m._grad_arena.clone()
+        if e is not None:
+            s["params_bf16"], s["ema_bf16"] = e.params_bf16.clone(), e.ema_bf16.clone()
+            s["stats"] = e.ws_tensor("loss", 0, (8,)).clone()
+            s["compact"] = e.compact_rows()
+        self.snapshots.append(s)
+        return s
+
+    def __iter__(self):
+        for k, (x, mask) in enumerate(self.batches):
+            self.requested.append(k)
+            self.snapshot()
+            yield (x, mask), torch.zeros(1)
+        self.snapshot()
+
+
+class RecordingWriter:
+    """utils.TensorboardLogger's update(head=..., **kw) / set_step() interface; one dict per set_step() with what was published."""
+
+    def __init__(self):
+        self.records, self._cur = [], {}
+
+    def update(self, head="scalar", step=None, **kw):
+        self._cur.update(kw)
+
+    def set_step(self, step=None):
+        self.records.append(self._cur)
+        self._cur = {}
+
+    def flush(self):
+        pass
+
+
+def expected_update(P0, M0, V0, E0, g, lr, wd, ema_decay, step, n_decay, clip, betas, eps):
+    """Float64 restatement, on flat arenas, of global-norm clip (utils.py:375-376), torch.optim.AdamW with weight decay on [0, n_decay)
+    only, and the EMA e <- d e + (1 - d) p_new; `step` is 1-based, ema_decay None = the teacher is returned unchanged.  The scalars are
+    rounded to float32 first, as the C ABI carries them.  Returns (P, M, V, E, unclipped norm) as float64 CPU tensors."""
+    import numpy as np
+    f32 = lambda x: float(np.float32(x))  # noqa: E731
+    d64 = lambda t: t.detach().cpu().double()  # noqa: E731
+    lr, wd, b1, b2, eps = f32(lr), f32(wd), f32(betas[0]), f32(betas[1]), f32(eps)
+    P, M, V, E, g = d64(P0).clone(), d64(M0), d64(V0), d64(E0), d64(g)
+    norm = float(torch.sqrt((g * g).sum()))
+    if clip:
+        g = g * min(1.0, f32(clip) / (norm + 1e-6))
+    P[:n_decay] *= 1.0 - lr * wd
+    M = b1 * M + (1.0 - b1) * g
+    V = b2 * V + (1.0 - b2) * g * g
+    P -= (lr / (1.0 - b1 ** step)) * M / (V.sqrt() / (1.0 - b2 ** step) ** 0.5 + eps)
+    if ema_decay is not None:
+        d = f32(ema_decay)
+        E = d * E + (1.0 - d) * P
+    return P, M, V, E, norm

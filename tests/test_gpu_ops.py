@@ -551,6 +551,33 @@ def test_ema_adamw_sumsq_against_torch(L):
     assert torch.equal(pb, p.to(torch.bfloat16))
 
 
+def test_adamw_skips_a_non_finite_norm(L):
+    """A step whose gradient norm is not finite leaves the weights untouched (include/uvit.h): *sumsq NaN, +inf, and 1e40 -- finite as a
+    double, infinite as the float the kernel tests.  p, m, v and the bf16 shadow keep their bits and the reported norm is not finite (the
+    host stops on it); with a finite sum the same call moves them.  Found: the 1e40 step was skipped but reported the finite norm 1e20."""
+    n, n_decay = 64 * 100, 64 * 60
+    p = rnd(n, seed=63); g = rnd(n, seed=64)
+    m = rnd(n, seed=65) * 0.1; v = rnd(n, seed=66).abs() * 0.01
+    pb = p.to(torch.bfloat16)
+    gn = torch.zeros(1, device="cuda")
+    before = [t.clone() for t in (p, m, v, pb)]
+
+    def call(sumsq):
+        ss = torch.tensor([sumsq], dtype=torch.float64, device="cuda")
+        gn.zero_()
+        ok(L.uvit_op_adamw(P(p), P(g), P(m), P(v), P(pb), n, n_decay, C.c_float(2e-3), C.c_float(0.05), C.c_float(0.9),
+                           C.c_float(0.999), C.c_float(1e-8), 1, P(ss), C.c_float(3.0), C.c_float(1.0), P(gn), S()))
+        return gn.item()
+
+    for bad in (float("nan"), float("inf"), 1e40):
+        norm = call(bad)
+        assert all(torch.equal(a, b) for a, b in zip((p, m, v, pb), before)), f"sumsq = {bad}: the step moved the weights"
+        assert not math.isfinite(norm), f"sumsq = {bad}: reported norm {norm}"
+    norm = call(float((g.double() ** 2).sum()))
+    assert math.isfinite(norm) and norm == pytest.approx(float(g.double().norm()), rel=1e-4)
+    assert not any(torch.equal(a, b) for a, b in zip((p, m, v, pb), before))
+
+
 @pytest.mark.parametrize("beta,l2", [(2.0, 0), (0.12, 0), (1.0, 1)])
 def test_smooth_l1_fwd_bwd(L, beta, l2):
     Mmax, Cd, cnt = 64, 128, 50

@@ -71,7 +71,10 @@ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __r
     // the new weights are in registers, so the separate EMA kernel's second read of the 345 MB parameter arena disappears
     float coef = grad_scale;
     if (sumsq) {
-        const float norm = (float)sqrt(*sumsq) * grad_scale;
+        float norm = (float)sqrt(*sumsq) * grad_scale;
+        // a sum beyond the float range (finite as a double) poisons the step below: report the float that is tested there, not the
+        // finite sqrt -- the host stops on a non-finite norm, and must not go on with weights that no longer move
+        if (not_finite((float)*sumsq)) norm = (float)*sumsq;
         if (gnorm_out && blockIdx.x == 0 && threadIdx.x == 0) *gnorm_out = norm;
         if (max_norm > 0.f) coef *= fminf(max_norm / (norm + 1e-6f), 1.0f);
     }
