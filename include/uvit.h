@@ -437,6 +437,26 @@ int uvit_op_calib_tace(const float* probs, const int64_t* labels, double thresho
  * out[1] = the number of classes counted. */
 int uvit_op_calib_auroc(const float* probs, const int64_t* labels, int32_t* rows, double* out, int B, int K, uvit_stream stream);
 
+/* ---- stability under perturbation sequences (uncertainty_evaluations.py: p_evaluate, flip_prob, ranking_dist, dist) ----
+ * 1 <= K <= 4096, 1 <= R <= 65535 * 256, 2 <= F <= 256, 1 <= V <= 65535.  Every call checks its arguments before it touches the
+ * device (UVIT_ERR_ARG for a NULL pointer or a noise other than 0 / 1, UVIT_ERR_SHAPE for a size outside these limits, outputs
+ * untouched) and is asynchronous on `stream`.  No atomics; every sum has one owner and a fixed order, so the same input gives the
+ * same bits on every run. */
+/* ranks (R, K) int32 = the ordinal ranks of logits (R, K) fp32, row by row: r[k] = 1 + #{j : z_j > z_k} + #{j < k : z_j == z_k},
+ * i.e. rankdata(-z, method='ordinal'): rank 1 is the largest logit (the row's prediction: argmax, first index on ties), ties go to the
+ * lower index, +0 == -0, +-inf order like any other value.  A row that holds a NaN gets the rank 0 for every class.  Each row is
+ * sorted in LDS as 64-bit keys (order-preserving image of -z, class index) by a bitonic network over K padded to a power of two. */
+int uvit_op_stability_ranks(const float* logits, int32_t* ranks, int R, int K, uvit_stream stream);
+/* ranks (V F, K): the F frames of a sequence adjacent.  The reference frame of frame t >= 1 is frame t - 1 (noise = 0) or frame 0
+ * (noise = 1).  With a = ranks of the reference frame and b = ranks of frame t, each of the F - 1 pairs gives
+ *   flip = #{c : a[c] == 1 and b[c] != 1} (= [pred_ref != pred_t] on permutations),
+ *   top5 = sum over c with a[c] <= 5 of |(a[c] - 1) - min(b[c] - 1, 5)|,   zipf = sum over c of |1 / a[c] - 1 / b[c]| / a[c].
+ * seq (V, 3) double = {flip, top5, zipf} summed over the sequence's pairs (the caller divides by F - 1).  flip and top5 are summed
+ * as integers; zipf is formed and summed in double, the classes of a pair one by one in ascending order, the pairs in frame order,
+ * each sum by one owner.  A rank below 1 anywhere in a sequence (a NaN row) makes its three values NaN; nothing is indexed by a
+ * rank. */
+int uvit_op_stability_sequences(const int32_t* ranks, double* seq, int V, int F, int K, int noise, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

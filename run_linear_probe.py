@@ -14,6 +14,12 @@ never used.  Training reads `--data_path` with flip + RandomResizedCrop (augment
 with resize + center crop (level 1), both augmented on the device.  Single GPU.  `--calibration` adds the reference's calibration
 metrics to every evaluation: a second line `* ECE ... TACE ... NLL ... AUROC ...` and `test_ECE`, `test_TACE`, `test_NLL`,
 `test_AUROC` in log.txt (with --eval: one entry of the test figures, when --output_dir is given).
+
+`--eval --perturbation_path DIR [--perturbations NAME ...]` adds the reference's p_evaluate() behind the evaluation: every `DIR/NAME.npy`
+(without --perturbations: every `DIR/*.npy`, sorted) is an (N, F, H, W, 3) uint8 array of N sequences of F frames (the CIFAR-100-P
+layout).  Per perturbation the flipping probability, the top-5 distance and the Zipf distance are printed in the reference's format
+and, with --output_dir, appended to log.txt as `test_flip_NAME`, `test_top5_NAME`, `test_zipf_NAME`; `Mean Flipping Prob` closes
+the list.  A perturbation with `noise` in its name compares every frame with frame 0, any other with the frame before it.
 """
 import argparse
 import json
@@ -59,6 +65,10 @@ def get_args(argv=None):
     # absent unless given (SUPPRESS): without the flag the parsed arguments, and so the first line printed, are what they were
     a("--calibration", action="store_true", default=argparse.SUPPRESS,
       help="also report ECE, TACE, NLL and AUROC of the evaluation (the reference's evaluate() beside Acc@1 / Acc@5)")
+    a("--perturbation_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
+      help="with --eval: directory of perturbation sequences, NAME.npy of shape (N, F, H, W, 3) uint8 (the reference's p_evaluate())")
+    a("--perturbations", type=str, nargs="+", default=argparse.SUPPRESS, metavar="NAME",
+      help="the perturbations to evaluate (default: every *.npy of --perturbation_path, sorted)")
     return p.parse_args(argv)
 
 
@@ -67,6 +77,48 @@ CALIB_KEYS = ("ECE", "TACE", "NLL", "AUROC")
 
 def calibration_line(stats):
     return "* ECE {ECE:.5f} TACE {TACE:.5f} NLL {NLL:.5f} AUROC {AUROC:.5f}".format(**stats)
+
+
+def perturbation_files(args):
+    """[(name, path)] of the perturbations to evaluate: --perturbations as given, else every *.npy of --perturbation_path, sorted."""
+    root = args.perturbation_path
+    names = getattr(args, "perturbations", None)
+    if names is None:
+        names = sorted(f[:-4] for f in os.listdir(root) if f.endswith(".npy"))
+    if not names:
+        raise FileNotFoundError(f"no *.npy under --perturbation_path {root}")
+    return [(n, os.path.join(root, n + ".npy")) for n in names]
+
+
+def evaluate_perturbations(args, probe, device):
+    """The reference's p_evaluate() (uncertainty_evaluations.py:614-658) over perturbation_files(args), V = max(1, batch_size // F)
+    sequences per forward; prints its lines and returns {name: evaluate_stability's result}."""
+    from uncertainty_vit_amd.datasets import BEiTAugment, PerturbationSequences, collate_sequences
+    from uncertainty_vit_amd.engine_for_cyclical import DevicePrefetcher
+    aug = BEiTAugment(args.input_size, 1, "bicubic", args.imagenet_default_mean_and_std)
+    print("Perturbed dataset evaluation :")
+    results, flip_list = {}, []
+    for name, path in perturbation_files(args):
+        print("Perturbation : " + name)
+        ds = PerturbationSequences(path, aug)
+        loader = torch.utils.data.DataLoader(ds, batch_size=max(1, args.batch_size // ds.frames), shuffle=False, drop_last=False,
+                                             num_workers=args.num_workers, pin_memory=True, collate_fn=collate_sequences)
+        r = probe.evaluate_stability(DevicePrefetcher(loader, device), ds.frames, "noise" in name, n_sequences=len(ds))
+        results[name] = r
+        flip_list.append(r["flip_prob"])
+        print("\n" + name, "Flipping Prob")
+        print(r["flip_prob"])
+        print("Top5 Distance\t{:.5f}".format(r["top5_dist"]))
+        print("Zipf Distance\t{:.5f}".format(r["zipf_dist"]))
+        if r["nan_sequences"]:
+            print("%d of %d sequences hold a NaN logit and are left out" % (r["nan_sequences"], r["n_sequences"]))
+        if args.output_dir:
+            with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
+                f.write(json.dumps({f"test_flip_{name}": r["flip_prob"], f"test_top5_{name}": r["top5_dist"],
+                                    f"test_zipf_{name}": r["zipf_dist"]}) + "\n")
+    print(flip_list)
+    print("\nMean Flipping Prob\t{:.5f}".format(np.mean(flip_list)))
+    return results
 
 
 def encoder_kwargs(checkpoint):
@@ -104,6 +156,8 @@ def main(args):
         raise ValueError("--nb_classes is required")
     if not args.finetune:
         raise ValueError("--finetune <pre-training checkpoint> is required")
+    if (hasattr(args, "perturbation_path") or hasattr(args, "perturbations")) and not (args.eval and hasattr(args, "perturbation_path")):
+        raise ValueError("--perturbation_path / --perturbations belong to an evaluation: give --eval and --perturbation_path DIR")
     device = torch.device("cuda")
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
@@ -137,6 +191,8 @@ def main(args):
                 with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                     f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5")},
                                         **{f"test_{k}": stats[k] for k in CALIB_KEYS}}) + "\n")
+        if hasattr(args, "perturbation_path"):
+            stats["stability"] = evaluate_perturbations(args, probe, device)
         return stats
     loader_train, _ = build_loader(args, encoder, args.data_path, 3, train=True)
     steps_per_epoch = len(loader_train)

@@ -265,6 +265,47 @@ class ImageFolderPretrain(torch.utils.data.Dataset):
         return (img, desc, self.masks(), a.size, a.mean, a.std), target
 
 
+class PerturbationSequences(torch.utils.data.Dataset):
+    """One perturbation of a CIFAR-100-P style data set: a `.npy` of shape (N, F, H, W, 3) uint8, N sequences of F frames, the file
+    the reference's build_p_dataset reads (uncertainty_evaluations.py:784-799).  It is opened with mmap_mode="r"; one item is one
+    sequence, ((pixels (F, H, W, 3), F descriptors, size, mean, std), 0), for `collate_sequences`.  `augment` is the evaluation
+    pipeline of the classifier (BEiTAugment(input_size, 1, "bicubic", ...): bicubic resize of the short side + centre crop on the
+    device, with the mean and std the head was trained with), not the reference's process_raw_data, which always normalises with the
+    inception constants and then applies `* 2 - 1` once more."""
+
+    def __init__(self, npy_path, augment):
+        self.path, self.augment = npy_path, augment
+        self.data = np.load(npy_path, mmap_mode="r")
+        if self.data.ndim != 5 or self.data.shape[-1] != 3 or self.data.dtype != np.uint8:
+            raise ValueError(f"{npy_path}: expected a uint8 array of shape (N, F, H, W, 3), found {self.data.dtype} {self.data.shape}")
+        if self.data.shape[1] < 2:
+            raise ValueError(f"{npy_path}: a sequence needs at least two frames")
+        self.frames = int(self.data.shape[1])
+        d = augment(int(self.data.shape[2]), int(self.data.shape[3]))       # level 1 draws nothing: every frame has these parameters
+        self._desc = np.repeat(d.reshape(1), self.frames).astype(AUG_DESC_DTYPE)
+
+    def __len__(self):
+        return self.data.shape[0]
+
+    def __getitem__(self, index):
+        a = self.augment
+        return (np.ascontiguousarray(self.data[index]), self._desc, a.size, a.mean, a.std), 0
+
+
+def collate_sequences(batch):
+    """[((pixels (F, H, W, 3) uint8, F desc records, size, mean, std), 0)] -> PackedBatch of V F images, sequence-major: the frames of
+    a sequence stay adjacent and in frame order.  Labels are 0 and the mask is (V F, 1) zeros: the probe's forward takes none."""
+    items = [b[0] for b in batch]
+    desc = np.concatenate([it[1] for it in items]).astype(AUG_DESC_DTYPE)
+    sizes = np.concatenate([[it[0][f].size for f in range(it[0].shape[0])] for it in items])
+    desc["offset"] = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    pixels = torch.from_numpy(np.concatenate([it[0].reshape(-1) for it in items]))
+    n = desc.shape[0]
+    first = items[0]
+    return PackedBatch(pixels, torch.from_numpy(desc.view(np.uint8).reshape(-1)), torch.zeros(n, 1, dtype=torch.int64),
+                       torch.zeros(n, dtype=torch.int64), first[2], first[3], first[4])
+
+
 def build_pretraining_dataset(args):
     """build_beit_pretraining_dataset (reference datasets.py:131-139) for the folder data sets."""
     if args.data_set in ("CIFAR10", "CIFAR100"):

@@ -24,6 +24,7 @@ __all__ = ["LinearProbe", "build_probe_encoder", "load_encoder_checkpoint"]
 
 CALIB_MAX_BINS = 64          # csrc/calib.hip: 1 <= n_bins <= 64, 1 <= B <= 1024
 ECE_BINS, TACE_BINS, TACE_THRESHOLD = 15, 30, 0.01      # the reference's defaults (uncertainty_evaluations.py:200,243)
+STABILITY_MAX_FRAMES = 256   # csrc/stability.hip: 2 <= F <= 256, 1 <= V <= 65535, 1 <= K <= 4096
 
 
 def _timm_trunc_normal_(t, std):
@@ -70,7 +71,7 @@ class LinearProbe(nn.Module):
         self._rebind()
         _timm_trunc_normal_(self.head.weight.data, std=0.02).mul_(init_scale)     # modeling_finetune.py:439-441
         self.head.bias.data.zero_()                                               # constant 0 times init_scale
-        self._buf_batch = self._calib_batch = 0
+        self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
 
     # ---- arena plumbing (as the encoder's) ----
     def _rebind(self):
@@ -85,7 +86,7 @@ class LinearProbe(nn.Module):
             raise NotImplementedError("the head stays fp32")
         self._arena = new.contiguous()
         self._grad_arena, self.exp_avg, self.exp_avg_sq = (fn(t).contiguous() for t in (self._grad_arena, self.exp_avg, self.exp_avg_sq))
-        self._buf_batch = self._calib_batch = 0
+        self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
         self._rebind()
         return self
 
@@ -283,6 +284,96 @@ class LinearProbe(nn.Module):
             stats["AUROC"] = sum(a * b for a, b in have) / sum(b for _, b in have) if have else float("nan")
             stats["AUROC_zero_absent"] = sum(r[3] / self.num_classes * b for r, b in zip(rows, sizes)) / n
         return stats
+
+    # ---- stability under perturbation sequences ----
+    def _stability_buffers_for(self, R, V):
+        """Ranks (R, K) int32 and per-sequence sums (V, 3) float64 of the stability ops (csrc/stability.hip), grown on demand."""
+        dev = self._arena.device
+        if dev.type != "cuda":
+            raise native.UvitError("the stability ops run as HIP kernels: move the encoder and the probe to a GPU (no CPU fallback)")
+        if R > self._rank_rows:
+            self._ranks = torch.zeros(R, self.num_classes, dtype=torch.int32, device=dev)
+            self._rank_rows = R
+        if V > self._seq_rows:
+            self._seq = torch.zeros(V, 3, dtype=torch.float64, device=dev)
+            self._seq_rows = V
+
+    def _stability_into(self, logits, V, F, noise, out):
+        """The two ops on `logits` (V F, K) on the current stream; `out` is a device pointer to V x 3 doubles."""
+        K, L, s = self.num_classes, lib(), cur_stream()
+        check(L.uvit_op_stability_ranks(ptr(logits), ptr(self._ranks), V * F, K, s), "uvit_op_stability_ranks")
+        check(L.uvit_op_stability_sequences(ptr(self._ranks), C.c_void_p(out), V, F, K, 1 if noise else 0, s), "uvit_op_stability_sequences")
+
+    @staticmethod
+    def _frames(frames):
+        F = int(frames)
+        if not 2 <= F <= STABILITY_MAX_FRAMES:
+            raise native.UvitError(f"frames must be in [2, {STABILITY_MAX_FRAMES}], got {frames}")
+        return F
+
+    def stability_batch(self, logits, frames, noise):
+        """The reference's per-sequence stability sums (uncertainty_evaluations.py: flip_prob, ranking_dist) of caller-supplied GPU
+        logits (V * frames, K) fp32, the frames of a sequence adjacent: a (V, 3) float64 device tensor {flips, top-5 distance, Zipf
+        distance} summed over each sequence's frames - 1 pairs (divide by frames - 1 for the sequence's values), valid until the next
+        call; nothing synchronises with the host.  `noise`: every frame is compared with frame 0 instead of with the frame before it
+        (the reference's rule for perturbations with 'noise' in their name).  A sequence that holds a NaN logit gives three NaNs.  The
+        ordinal ranks (rank 1 = the largest logit, ties to the lower index, 0 in a row with a NaN) stay in self._ranks[:V * frames]."""
+        if not torch.is_tensor(logits) or not logits.is_cuda:
+            raise native.UvitError("logits must be a GPU tensor: the HIP path has no CPU fallback")
+        if logits.dtype != torch.float32 or logits.ndim != 2 or logits.shape[1] != self.num_classes or not logits.is_contiguous():
+            raise native.UvitError(f"logits must be a contiguous float32 tensor of shape (V * frames, {self.num_classes})")
+        F = self._frames(frames)
+        R = logits.shape[0]
+        if R < F or R % F:
+            raise native.UvitError(f"{R} logit rows are not whole sequences of {F} frames")
+        V = R // F
+        self._stability_buffers_for(R, V)
+        self._stability_into(logits, V, F, noise, self._seq.data_ptr())
+        return self._seq[:V]
+
+    def evaluate_stability(self, loader, frames, noise, n_sequences=None):
+        """The reference's p_evaluate() for one perturbation.  `loader` yields batches of V * frames GPU images, sequence-major, as
+        images, (images, labels) or ((images, mask), labels) (the device prefetcher's items over datasets.PerturbationSequences).  Per
+        batch: encoder eval forward, pool + norm, logits, ranks, per-sequence sums, written on the device at the running sequence
+        offset of one slab sized for the data set: `n_sequences`, by default len(loader.dataset) or len(loader.loader.dataset) (a
+        loader that says neither needs the argument; more sequences than that are an error).  One read after the last batch.  The
+        host divides by frames - 1 and takes the means in float64, in sequence order, over the sequences without a NaN logit;
+        `nan_sequences` counts the others.  Per-sequence values do not depend on how the sequences are batched: each is a function
+        of its own logits."""
+        F = self._frames(frames)
+        if n_sequences is None:
+            ds = getattr(getattr(loader, "loader", loader), "dataset", None)
+            if ds is None or not hasattr(ds, "__len__"):
+                raise native.UvitError("evaluate_stability sizes its slab for the data set: pass n_sequences (the loader has no dataset to count)")
+            n_sequences = len(ds)
+        slab, n = None, 0
+        for item in loader:
+            images = item
+            while isinstance(images, (tuple, list)):
+                images = images[0]
+            B = self._features(images)
+            if B % F:
+                raise native.UvitError(f"a batch of {B} images is not whole sequences of {F} frames")
+            V = B // F
+            if n + V > n_sequences:
+                raise native.UvitError(f"the loader holds more than the {n_sequences} sequences the slab was sized for")
+            self._logits_into(B)
+            self._stability_buffers_for(B, 0)
+            if slab is None:
+                slab = torch.zeros(int(n_sequences), 3, dtype=torch.float64, device=images.device)
+            self._stability_into(self._logits, V, F, noise, slab.data_ptr() + 24 * n)
+            n += V
+        out = {"flip_prob": float("nan"), "top5_dist": float("nan"), "zipf_dist": float("nan"), "n_sequences": n, "frames": F,
+               "nan_sequences": 0}
+        if not n:
+            return out
+        rows = slab[:n].cpu().tolist()                                                  # the one read
+        good = [r for r in rows if not any(math.isnan(v) for v in r)]
+        out["nan_sequences"] = n - len(good)
+        for col, key in enumerate(("flip_prob", "top5_dist", "zipf_dist")):
+            if good:
+                out[key] = sum(r[col] / (F - 1) for r in good) / len(good)
+        return out
 
     # ---- optimizer state beside head.* in a checkpoint ----
     def optimizer_state_dict(self):

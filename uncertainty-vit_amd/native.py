@@ -171,6 +171,8 @@ _PROTOTYPES = {
     "uvit_op_calib_confidence": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "uvit_op_calib_tace": (_i, [_vp, _vp, C.c_double, _i, _i, _vp, _vp, _i, _i, _vp]),
     "uvit_op_calib_auroc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "uvit_op_stability_ranks": (_i, [_vp, _vp, _i, _i, _vp]),
+    "uvit_op_stability_sequences": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
