@@ -303,6 +303,65 @@ int uvit_op_ln_fwd(const float* x, const float* w, const float* b, void* y_bf16,
                    float eps, uvit_stream stream);
 int uvit_op_ln_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* w,
                    const float* dres, float* dx, float* dw, float* db, int M, int C, uvit_stream stream);
+/* ---- the same row-wise kernels in every walk the engine launches them in (tests).  Each call fills the launcher's descriptor and
+ * launches: nothing is allocated.  UVIT_ERR_ARG for a NULL mandatory pointer, before the device is touched; otherwise the launcher's
+ * own codes (UVIT_ERR_SHAPE for a combination of fields it refuses).  Column sums (dw, db, dgamma, dbias, colsum) are ADDED into
+ * nrep replicas of the accumulator, rep_stride floats apart (workgroup g adds into replica g % nrep): the caller zeroes them. ---- */
+/* LayerNorm forward.  rows walk (pos == NULL): y / mean / rstd row r <- x row rowidx[r] (NULL: r); rows r >= *count (NULL: M) get a
+ * zero y row and leave mean / rstd alone; mean / rstd may both be NULL.  samples walk (pos, xcopy, tokens; M % tokens == 0; no row
+ * list): sample b's rows go to rows pos[b] * tokens + t of y / mean / rstd; a sample with pos[b] < 0 is copied to xcopy instead. */
+int uvit_op_ln_fwd_walk(const float* x, const float* w, const float* b, void* y_bf16, float* mean, float* rstd, int M, int C,
+                        float eps, const int32_t* rowidx, const int32_t* count, const int32_t* pos, float* xcopy, int tokens,
+                        uvit_stream stream);
+/* The LayerScale + DropPath backward of the branch behind a row-wise backward pass over the residual-stream gradient d
+ * (modeling_finetune.py:295-298): e = d * rowscale[sample], dy = bf16(e * gamma), dgamma += e * y, dbias += dy (the stored bf16).
+ * tokens = rows per sample.  LayerNorm backward only: pos (sample -> compact slot of dy, -1 = dropped: writes nothing, adds nothing;
+ * NULL = dense); cnt (samples walk: kept rows; the pad rows cnt .. roundup(pad_base + cnt, 64) - pad_base of dy are zero-filled, and the
+ * same rows of pad2 [rows][pad2_cols], pad2_cols % 4 == 0). */
+typedef struct uvit_ls_rider {
+    const void* y; const float* gamma; const float* rowscale; void* dy; float* dgamma; float* dbias;
+    int32_t tokens; const int32_t* pos; const int32_t* cnt; int32_t pad_base; void* pad2; int32_t pad2_cols;
+} uvit_ls_rider;
+/* LayerNorm backward with `next` (nullable) fused on dx.  rows walk: dy / mean / rstd row r belongs to residual-stream row rowidx[r]
+ * (NULL: r; a row list needs count), where x, dres (nullable), dx and next->y live; rows r >= *count are skipped.  samples walk (pos, or
+ * next->cnt, or next->pos without a row list; needs dres, next->tokens, M % tokens == 0): dy / mean / rstd compact by pos (NULL: all
+ * kept); a dropped sample's rows get dx = dres and add nothing to dw / db. */
+int uvit_op_ln_bwd_walk(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* w, const float* dres,
+                        float* dx, float* dw, float* db, int M, int C, int nrep, int64_t rep_stride, const int32_t* rowidx,
+                        const int32_t* count, const int32_t* pos, const uvit_ls_rider* next, uvit_stream stream);
+/* The rider on its own over d = dx [.., C] (pos / cnt / pad* unused).  Row list: rider->dy is compact, row r reads dx / y / rowscale at
+ * residual-stream row rowidx[r], rows r >= *count (up to M) get zeros. */
+int uvit_op_ls_bwd(const float* dx, const uvit_ls_rider* rider, int M, int C, int nrep, int64_t rep_stride, const int32_t* rowidx,
+                   const int32_t* count, uvit_stream stream);
+/* out[c] += sum over the M rows of y[m][col0 + c], c < ncols (ld, col0, ncols multiples of 8) */
+int uvit_op_colsum(const void* y_bf16, int ld, int col0, int ncols, int M, float* out, int nrep, int64_t rep_stride, uvit_stream stream);
+/* out[i] += sum_r rep[r * stride + i], i < n (n, stride multiples of 4) */
+int uvit_op_reduce_replicas(const float* rep, float* out, int64_t n, int nrep, int64_t stride, uvit_stream stream);
+/* Drop-path sample lists from the multipliers scales [nlists][B] (0 = dropped): per list pos [B] (slot or -1), bmap [B] (slot -> sample,
+ * 0 behind the kept ones), rows [rows_stride] (compact row -> residual-stream row, -1 on the pad rows up to the next multiple of 64,
+ * nothing behind them), cnt[l] = kept rows, cnt[nlists + l] = 1 when the kept samples differ from host_counts[l] (HOST array). */
+int uvit_op_droppath_lists(const float* scales, int32_t* pos, int32_t* bmap, int32_t* rows, int32_t* cnt, int nlists, int B, int tokens,
+                           int rows_stride, const int32_t* host_counts, uvit_stream stream);
+/* uvit_op_gemm_nt_tuned in mode UVIT_EPI_RESID (any other: UVIT_ERR_ARG) over a COMPACT row list: GEMM row m stands for residual-stream
+ * row rowmap[m] -- resid is read and out / out2 are written there, rowscale is taken at rowmap[m] / tokens; rows m >= *rowcount write
+ * nothing.  Such a launch never splits its rows. */
+int uvit_op_gemm_nt_rows(int mode, const void* A_bf16, const void* W_bf16, int M, int N, int K, int lda, int ldw,
+                         const uvit_gemm_epilogue* epi, const int32_t* rowmap, const int32_t* rowcount, const uvit_tuning* tune,
+                         uvit_stream stream);
+/* uvit_op_wgrad_group on stacked two-stream operands: split[i] (parallel to problems[i]; s1_row = 0: one stream) sends the column sums
+ * of the rows from s1_row on to bias_s1 / bias2_s1.  s1_row % 64 == 0, M >= 1024, s1_row / 64 == (M / 64 + 1) / 2, and bias, bias_s1
+ * (bias2_s1 with bias2) set; anything else returns UVIT_ERR_SHAPE. */
+typedef struct uvit_wgrad_split { float* bias_s1; float* bias2_s1; int32_t s1_row; } uvit_wgrad_split;
+int uvit_op_wgrad_group_split(const uvit_wgrad_problem* problems, const uvit_wgrad_split* split, int count, const uvit_tuning* tune,
+                              uvit_stream stream);
+/* token-assembly backward (modeling_cyclical.py:179-192) of dx (B, P + 1, C): dpatch (B, P, C) bf16 = dx[:, 1:] with the masked rows
+ * zero (mask: int64 (B, P)), dcls [C] += sum_b dx[b, 0], dmask_token [C] += the sum of the masked rows */
+int uvit_op_token_bwd(const float* dx, const int64_t* mask, void* dpatch_bf16, float* dcls, float* dmask_token, int B, int P, int C,
+                      uvit_stream stream);
+/* bf16 transposes in one launch: dst (cols, rows) = src (rows, cols)^T per descriptor; descs in DEVICE memory, tile0 = the first
+ * 64 x 64 tile of the descriptor in the launch (ascending; total_tiles = their sum) */
+typedef struct uvit_transpose_desc { const void* src; void* dst; int32_t rows, cols, tile0, pad; } uvit_transpose_desc;
+int uvit_op_transpose_batch(const uvit_transpose_desc* descs_dev, int ndesc, int total_tiles, uvit_stream stream);
 /* ModelEmaV2._update with the lambda of engine_for_cyclical.py:183 */
 int uvit_op_ema(float* ema, const float* params, void* ema_bf16, int64_t n, float decay, uvit_stream stream);
 int uvit_op_sumsq(const float* g, int64_t n, double* out, uvit_stream stream);

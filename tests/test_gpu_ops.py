@@ -498,7 +498,7 @@ def test_relpos_gather_scatter(L):
     torch.testing.assert_close(dt, ref, rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("M,Cd", [(30, 128), (10, 192), (1000, 768), (77, 1024)])
+@pytest.mark.parametrize("M,Cd", [(30, 128), (10, 192), (1000, 768), (77, 1024), (33, 260), (21, 1280), (13, 1536), (9, 2048)])
 def test_layernorm_fwd_bwd(L, M, Cd):
     x = rnd(M, Cd, seed=50) * 2 + 0.3
     w, b = rnd(Cd, seed=51) * 0.2 + 1, rnd(Cd, seed=52) * 0.1

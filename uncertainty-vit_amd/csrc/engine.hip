@@ -1307,6 +1307,89 @@ extern "C" int uvit_op_ln_bwd(const void* dy, const float* x, const float* mean,
     LnBwd p; p.dy = (const bf16*)dy; p.x = x; p.mean = mean; p.rstd = rstd; p.w = w; p.dres = dres; p.dx = dx; p.dw = dw; p.db = db; p.M = M; p.C = C;
     return uvit_ln_bwd_launch(p, S(st));
 }
+// the row-wise kernels in the walks the step launches them in: each wrapper fills the launcher's descriptor, nothing else
+static LsNext ls_from_abi(const uvit_ls_rider* r) {
+    LsNext n;
+    if (!r) return n;
+    n.y = (const bf16*)r->y; n.gamma = r->gamma; n.rowscale = r->rowscale; n.dy = (bf16*)r->dy; n.dgamma = r->dgamma; n.dbias = r->dbias;
+    n.tokens = r->tokens; n.pos = r->pos; n.cnt = r->cnt; n.pad_base = r->pad_base; n.pad2 = (bf16*)r->pad2; n.pad2_cols = r->pad2_cols;
+    return n;
+}
+extern "C" int uvit_op_ln_fwd_walk(const float* x, const float* w, const float* b, void* y, float* mean, float* rstd, int M, int C, float eps,
+                                   const int32_t* rowidx, const int32_t* count, const int32_t* pos, float* xcopy, int tokens, uvit_stream st) {
+    if (!x || !w || !b || !y || (!mean != !rstd)) return UVIT_ERR_ARG;
+    LnFwd p; p.x = x; p.w = w; p.b = b; p.y = (bf16*)y; p.mean = mean; p.rstd = rstd; p.M = M; p.C = C; p.eps = eps;
+    p.rowidx = rowidx; p.count = count; p.pos = pos; p.xcopy = xcopy; p.tokens = tokens;
+    return uvit_ln_fwd_launch(p, S(st));
+}
+extern "C" int uvit_op_ln_bwd_walk(const void* dy, const float* x, const float* mean, const float* rstd, const float* w, const float* dres,
+                                   float* dx, float* dw, float* db, int M, int C, int nrep, int64_t rep_stride, const int32_t* rowidx,
+                                   const int32_t* count, const int32_t* pos, const uvit_ls_rider* next, uvit_stream st) {
+    if (!dy || !x || !mean || !rstd || !w || !dx || !dw || !db || nrep < 1 || rep_stride < 0) return UVIT_ERR_ARG;
+    if (next && next->dy && (!next->y || !next->gamma || !next->dgamma || !next->dbias)) return UVIT_ERR_ARG;
+    LnBwd p; p.dy = (const bf16*)dy; p.x = x; p.mean = mean; p.rstd = rstd; p.w = w; p.dres = dres; p.dx = dx; p.dw = dw; p.db = db;
+    p.M = M; p.C = C; p.nrep = nrep; p.rep_stride = (size_t)rep_stride; p.rowidx = rowidx; p.count = count; p.pos = pos;
+    p.next = ls_from_abi(next);
+    return uvit_ln_bwd_launch(p, S(st));
+}
+extern "C" int uvit_op_ls_bwd(const float* dx, const uvit_ls_rider* r, int M, int C, int nrep, int64_t rep_stride, const int32_t* rowidx,
+                              const int32_t* count, uvit_stream st) {
+    if (!dx || !r || !r->y || !r->gamma || !r->dy || !r->dgamma || !r->dbias || nrep < 1 || rep_stride < 0) return UVIT_ERR_ARG;
+    if (M <= 0 || C <= 0 || r->tokens <= 0) return UVIT_ERR_SHAPE;
+    return uvit_ls_bwd_launch(dx, ls_from_abi(r), M, C, nrep, (size_t)rep_stride, S(st), rowidx, count);
+}
+extern "C" int uvit_op_colsum(const void* y, int ld, int col0, int ncols, int M, float* out, int nrep, int64_t rep_stride, uvit_stream st) {
+    if (!y || !out || nrep < 1 || rep_stride < 0) return UVIT_ERR_ARG;
+    if (M <= 0 || ncols <= 0 || col0 < 0 || col0 + ncols > ld) return UVIT_ERR_SHAPE;
+    return uvit_colsum_launch(y, ld, col0, ncols, M, out, nrep, (size_t)rep_stride, S(st));
+}
+extern "C" int uvit_op_reduce_replicas(const float* rep, float* out, int64_t n, int nrep, int64_t stride, uvit_stream st) {
+    if (!rep || !out || n < 0 || nrep < 0 || stride < 0) return UVIT_ERR_ARG;
+    return uvit_reduce_replicas_launch(rep, out, (size_t)n, nrep, (size_t)stride, S(st));
+}
+extern "C" int uvit_op_droppath_lists(const float* scales, int32_t* pos, int32_t* bmap, int32_t* rows, int32_t* cnt, int nlists, int B,
+                                      int tokens, int rows_stride, const int32_t* host_counts, uvit_stream st) {
+    if (!scales || !pos || !bmap || !rows || !cnt || !host_counts || B < 1 || tokens < 1) return UVIT_ERR_ARG;
+    return uvit_droppath_lists_launch(scales, pos, bmap, rows, cnt, nlists, B, tokens, rows_stride, host_counts, S(st));
+}
+extern "C" int uvit_op_gemm_nt_rows(int mode, const void* A, const void* W, int M, int N, int K, int lda, int ldw, const uvit_gemm_epilogue* ep,
+                                    const int32_t* rowmap, const int32_t* rowcount, const uvit_tuning* tune, uvit_stream st) {
+    if (!A || !W || !ep || !ep->out || !ep->resid || !rowmap || !rowcount || mode != UVIT_EPI_RESID) return UVIT_ERR_ARG;
+    GemmTune tu;
+    const int trc = tune_from_abi(tune, tu);
+    if (trc) return trc;
+    GemmEpi g = epi_from_abi(ep);
+    g.rowmap = rowmap; g.rowcount = rowcount;
+    return uvit_gemm_nt_launch(mode, A, W, M, N, K, lda, ldw, &g, S(st), &tu, nullptr);
+}
+extern "C" int uvit_op_wgrad_group_split(const uvit_wgrad_problem* problems, const uvit_wgrad_split* split, int count, const uvit_tuning* tune,
+                                         uvit_stream st) {
+    if (!problems || !split || count < 1 || count > UVIT_TN_GROUP_MAX) return UVIT_ERR_ARG;
+    GemmTune tu;
+    const int trc = tune_from_abi(tune, tu);
+    if (trc) return trc;
+    TnProb pr[UVIT_TN_GROUP_MAX];
+    for (int i = 0; i < count; ++i) {
+        const uvit_wgrad_problem& q = problems[i];
+        if (!q.Y_bf16 || !q.X_bf16 || !q.C) return UVIT_ERR_ARG;
+        pr[i].Y = q.Y_bf16; pr[i].X = q.X_bf16; pr[i].C = q.C; pr[i].bias = q.bias; pr[i].bias2 = q.bias2;
+        pr[i].bias_end = q.bias_end; pr[i].bias2_begin = q.bias2_begin;
+        pr[i].M = q.M; pr[i].Nn = q.N; pr[i].Kk = q.K; pr[i].ldy = q.ldy; pr[i].ldx = q.ldx; pr[i].ldc = q.ldc;
+        pr[i].bias_s1 = split[i].bias_s1; pr[i].bias2_s1 = split[i].bias2_s1; pr[i].s1_row = split[i].s1_row;
+    }
+    return uvit_gemm_tn_group_launch(pr, count, S(st), &tu);
+}
+extern "C" int uvit_op_token_bwd(const float* dx, const int64_t* mask, void* dpatch, float* dcls, float* dmask_token, int B, int P, int C,
+                                 uvit_stream st) {
+    if (!dx || !mask || !dpatch || !dcls || !dmask_token) return UVIT_ERR_ARG;
+    if (B < 1 || P < 1 || C < 1) return UVIT_ERR_SHAPE;
+    return uvit_token_bwd_launch(dx, mask, dpatch, dcls, dmask_token, B, P, C, S(st));
+}
+static_assert(sizeof(uvit_transpose_desc) == sizeof(TransposeDesc), "uvit_transpose_desc mirrors TransposeDesc");
+extern "C" int uvit_op_transpose_batch(const uvit_transpose_desc* descs_dev, int ndesc, int total_tiles, uvit_stream st) {
+    if (!descs_dev || ndesc < 1 || total_tiles < 1) return UVIT_ERR_ARG;
+    return uvit_transpose_batch_launch(descs_dev, ndesc, total_tiles, S(st));
+}
 extern "C" int uvit_op_ema(float* ema, const float* p, void* eb, int64_t n, float d, uvit_stream st) {
     return uvit_ema_launch(ema, p, eb, (size_t)n, d, S(st));
 }

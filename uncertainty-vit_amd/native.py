@@ -89,6 +89,24 @@ class GemmNtPlanInfo(C.Structure):
     _fields_ = [("kernel", C.c_int32), ("rows", C.c_int32), ("grid", C.c_int32), ("tail_rows", C.c_int32)]
 
 
+class LsRider(C.Structure):
+    """uvit_ls_rider (include/uvit.h): the LayerScale + DropPath backward that rides along in a row-wise backward pass."""
+    _fields_ = [(n, C.c_void_p) for n in ("y", "gamma", "rowscale", "dy", "dgamma", "dbias")] + \
+               [("tokens", C.c_int32), ("pos", C.c_void_p), ("cnt", C.c_void_p), ("pad_base", C.c_int32), ("pad2", C.c_void_p),
+                ("pad2_cols", C.c_int32)]
+
+
+class WgradSplit(C.Structure):
+    """uvit_wgrad_split (include/uvit.h): the second stream's bias sums of one uvit_wgrad_problem."""
+    _fields_ = [("bias_s1", C.c_void_p), ("bias2_s1", C.c_void_p), ("s1_row", C.c_int32)]
+
+
+class TransposeDesc(C.Structure):
+    """uvit_transpose_desc (include/uvit.h): one matrix of uvit_op_transpose_batch."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("tile0", C.c_int32),
+                ("pad", C.c_int32)]
+
+
 class AugmentDesc(C.Structure):
     """uvit_augment_desc (include/uvit.h): one sample of uvit_op_augment_batch."""
     _fields_ = [("offset", C.c_int64)] + \
@@ -148,6 +166,16 @@ _PROTOTYPES = {
     "uvit_op_relpos_scatter": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "uvit_op_ln_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "uvit_op_ln_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "uvit_op_ln_fwd_walk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _vp]),
+    "uvit_op_ln_bwd_walk": (_i, [_vp] * 9 + [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "uvit_op_ls_bwd": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp]),
+    "uvit_op_colsum": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i64, _vp]),
+    "uvit_op_reduce_replicas": (_i, [_vp, _vp, _i64, _i, _i64, _vp]),
+    "uvit_op_droppath_lists": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "uvit_op_gemm_nt_rows": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "uvit_op_wgrad_group_split": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "uvit_op_token_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "uvit_op_transpose_batch": (_i, [_vp, _i, _i, _vp]),
     "uvit_op_ema": (_i, [_vp, _vp, _vp, _i64, _f, _vp]),
     "uvit_op_sumsq": (_i, [_vp, _i64, _vp, _vp]),
     "uvit_op_adamw": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f, _f, _f, _f, _f, _i, _vp, _f, _f, _vp, _vp]),
