@@ -516,6 +516,36 @@ int uvit_op_stability_ranks(const float* logits, int32_t* ranks, int R, int K, u
  * rank. */
 int uvit_op_stability_sequences(const int32_t* ranks, double* seq, int V, int F, int K, int noise, uvit_stream stream);
 
+/* ---- random-feature Gaussian-process head on the frozen encoder: modeling_finetune.SNGP (:525-638), DESIGN.md section 9.3 ----
+ * 1 <= B <= 65535, C % 4 == 0, 4 <= C <= 2048, D % 4 == 0, 4 <= D <= 2048, K >= 1.  fp32 unless stated otherwise.  Every call checks
+ * its arguments before it touches the device (UVIT_ERR_ARG for a NULL pointer or a bad scalar, UVIT_ERR_SHAPE for a size outside these
+ * limits, outputs untouched) and is asynchronous on `stream`.  No float atomics; every sum has one owner and a fixed order that does
+ * not depend on the launch shape, so the same input gives the same bits on every run.  The output layer z = phi . W_out^T and its
+ * gradient dW_out = dz^T phi are uvit_op_probe_logits (with a zero bias) and uvit_op_probe_head_grad on phi with C := D. */
+/* ghat (B, C, nullable) = (feat - mean) * rstd per row (two-pass statistics, ln_eps >= 0 inside the root); g = ghat gamma + beta;
+ * u (B, D, nullable) = g . W_rf (D, C)^T + b_rf (D), summed in tiles of 16 along C in ascending order; phi (B, D) = scale * cos(u).
+ * The reference passes scale = gp_input_scale = 1 / sqrt(gp_kernel_scale) (:586-587); edward2 has sqrt(2 / D) there. */
+int uvit_op_gp_features(const float* feat, const float* gamma, const float* beta, const float* W_rf, const float* b_rf, float scale,
+                        float ln_eps, float* ghat, float* u, float* phi, int B, int C, int D, uvit_stream stream);
+/* P (D, D), in place (:599-616).  S_ij = sum_b phi_bi phi_bj, one fma chain over b in ascending order.  momentum > 0:
+ * P_ij <- fma(m, P_ij, om * (S_ij / B)) with m = (float)momentum and om = (float)(1 - momentum) (the reference's two Python
+ * doubles, each rounded to fp32 on its own); momentum <= 0: P_ij <- P_ij + S_ij.  A symmetric P stays symmetric bit for bit.
+ * momentum >= 1 or NaN: UVIT_ERR_ARG. */
+int uvit_op_gp_precision_update(const float* phi, float* P, int B, int D, double momentum, uvit_stream stream);
+/* Gradients of the LayerNorm's affine from dlogits (B, K), the gradient of the loss at z: du = -scale sin(u) * (dlogits . W_out (K, D)),
+ * dg = du . W_rf (D, C), dgamma[c] = sum_b dg[b, c] ghat[b, c], dbeta[c] = sum_b dg[b, c], b in ascending order.  Three launches;
+ * scratch holds du and dg: uvit_op_gp_ln_grad_ws_bytes(B, C, D) bytes (< 0: the UVIT_ERR_* of the call).  dgamma and dbeta (C) are
+ * overwritten. */
+int64_t uvit_op_gp_ln_grad_ws_bytes(int B, int C, int D);
+int uvit_op_gp_ln_grad(const float* dlogits, const float* W_out, const float* u, const float* W_rf, const float* ghat, float scale,
+                       float* dgamma, float* dbeta, float* scratch, int B, int K, int C, int D, uvit_stream stream);
+/* var[b] (B, double) = ridge * phi_b^T Sigma phi_b, the diagonal of compute_predictive_covariance (:618-626).  Sigma (D, D) is DOUBLE
+ * (the host's float64 inverse of P); phi is widened to double, products and sums are double in a fixed order.  ridge >= 0. */
+int uvit_op_gp_variance(const float* phi, const double* Sigma, double ridge, double* var, int B, int D, uvit_stream stream);
+/* out[b, k] = (float)(logits[b, k] / sqrt(1 + factor var[b])) formed in double: edward2's mean_field_logits, not part of the
+ * reference.  factor >= 0; factor = 0 returns the logits bit for bit.  out may alias logits.  One wave per row. */
+int uvit_op_gp_mean_field(const float* logits, const double* var, double factor, float* out, int B, int K, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,15 @@ metrics to every evaluation: a second line `* ECE ... TACE ... NLL ... AUROC ...
 layout).  Per perturbation the flipping probability, the top-5 distance and the Zipf distance are printed in the reference's format
 and, with --output_dir, appended to log.txt as `test_flip_NAME`, `test_top5_NAME`, `test_zipf_NAME`; `Mean Flipping Prob` closes
 the list.  A perturbation with `noise` in its name compares every frame with frame 0, any other with the frame before it.
+
+`--gp_layer` (the reference's flag) replaces the nn.Linear by the reference's random-feature Gaussian-process head
+(modeling_finetune.SNGP; uncertainty-vit_amd/gp_probe.py): LayerNorm, frozen random Fourier features with a cosine, a trainable
+output layer and a Laplace precision matrix accumulated over the training steps.  `--gp_num_inducing D` (default: the embed dim),
+`--gp_cov_momentum` (0.999; at <= 0 the precision matrix is the exact sum and is reset at the start of every epoch, so that the
+data are counted once), `--gp_cov_ridge_penalty` (1e-3), `--gp_kernel_scale` (1.0).  Every evaluation then prints a line
+`* GP variance mean ...` after `* Acc@1` and log.txt gains `test_gp_var_mean`, the mean predictive variance over the evaluation set.
+`--gp_mean_field FACTOR` (default 0: off) evaluates on edward2's mean-field logits z / sqrt(1 + FACTOR * var), an addition to the
+reference.  `--calibration` and `--perturbation_path` work with the head unchanged.
 """
 import argparse
 import json
@@ -69,14 +78,28 @@ def get_args(argv=None):
       help="with --eval: directory of perturbation sequences, NAME.npy of shape (N, F, H, W, 3) uint8 (the reference's p_evaluate())")
     a("--perturbations", type=str, nargs="+", default=argparse.SUPPRESS, metavar="NAME",
       help="the perturbations to evaluate (default: every *.npy of --perturbation_path, sorted)")
+    a("--gp_layer", action="store_true", default=argparse.SUPPRESS,
+      help="probe with the reference's random-feature Gaussian-process head (modeling_finetune.SNGP) instead of the nn.Linear")
+    a("--gp_num_inducing", type=int, default=argparse.SUPPRESS, metavar="D", help="random features of the GP head (default: the embed dim)")
+    a("--gp_cov_momentum", type=float, default=argparse.SUPPRESS,
+      help="momentum of the precision matrix (default 0.999); <= 0: the exact sum, reset at the start of every epoch")
+    a("--gp_cov_ridge_penalty", type=float, default=argparse.SUPPRESS, help="ridge penalty of the precision matrix (default 1e-3)")
+    a("--gp_kernel_scale", type=float, default=argparse.SUPPRESS, help="the cosine is multiplied by 1 / sqrt(this) (default 1.0)")
+    a("--gp_mean_field", type=float, default=argparse.SUPPRESS, metavar="FACTOR",
+      help="evaluate on the mean-field logits z / sqrt(1 + FACTOR * var) (edward2's mean_field_logits; default 0: off)")
     return p.parse_args(argv)
 
 
 CALIB_KEYS = ("ECE", "TACE", "NLL", "AUROC")
+GP_FLAGS = ("gp_num_inducing", "gp_cov_momentum", "gp_cov_ridge_penalty", "gp_kernel_scale", "gp_mean_field")
 
 
 def calibration_line(stats):
     return "* ECE {ECE:.5f} TACE {TACE:.5f} NLL {NLL:.5f} AUROC {AUROC:.5f}".format(**stats)
+
+
+def gp_variance_line(stats):
+    return "* GP variance mean {gp_var_mean:.6f}".format(**stats)
 
 
 def perturbation_files(args):
@@ -103,7 +126,8 @@ def evaluate_perturbations(args, probe, device):
         ds = PerturbationSequences(path, aug)
         loader = torch.utils.data.DataLoader(ds, batch_size=max(1, args.batch_size // ds.frames), shuffle=False, drop_last=False,
                                              num_workers=args.num_workers, pin_memory=True, collate_fn=collate_sequences)
-        r = probe.evaluate_stability(DevicePrefetcher(loader, device), ds.frames, "noise" in name, n_sequences=len(ds))
+        gp = {"mean_field": args.gp_mean_field} if getattr(args, "gp_layer", False) and hasattr(args, "gp_mean_field") else {}
+        r = probe.evaluate_stability(DevicePrefetcher(loader, device), ds.frames, "noise" in name, n_sequences=len(ds), **gp)
         results[name] = r
         flip_list.append(r["flip_prob"])
         print("\n" + name, "Flipping Prob")
@@ -158,6 +182,9 @@ def main(args):
         raise ValueError("--finetune <pre-training checkpoint> is required")
     if (hasattr(args, "perturbation_path") or hasattr(args, "perturbations")) and not (args.eval and hasattr(args, "perturbation_path")):
         raise ValueError("--perturbation_path / --perturbations belong to an evaluation: give --eval and --perturbation_path DIR")
+    gp_layer = getattr(args, "gp_layer", False)
+    if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
+        raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
     device = torch.device("cuda")
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
@@ -168,8 +195,14 @@ def main(args):
     unused = load_encoder_checkpoint(encoder, ckpt, args.model_key, args.model_prefix)
     print(f"encoder: {encoder.depth} blocks, {len(unused)} checkpoint entries not part of it")
     encoder.to(device)
-    probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
-    print("Trainable weights: %s" % [n for n, _ in probe.named_parameters()])
+    if gp_layer:
+        from uncertainty_vit_amd.gp_probe import GPProbe
+        probe = GPProbe(encoder, args.nb_classes, smoothing=args.smoothing, num_inducing=getattr(args, "gp_num_inducing", None),
+                        kernel_scale=getattr(args, "gp_kernel_scale", 1.0), cov_momentum=getattr(args, "gp_cov_momentum", 0.999),
+                        cov_ridge_penalty=getattr(args, "gp_cov_ridge_penalty", 1e-3))
+    else:
+        probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
+    print("Trainable weights: %s" % [n for n, p in probe.named_parameters() if p.requires_grad])
     start_epoch = 0
     if args.resume:
         st = torch.load(args.resume, map_location="cpu", weights_only=False)
@@ -181,16 +214,19 @@ def main(args):
     eval_root = args.eval_data_path or args.data_path
     loader_val, _ = build_loader(args, encoder, eval_root, 1, train=False)
     calibration = getattr(args, "calibration", False)
-    evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration)      # noqa: E731
+    gp_eval = {"variance": True, "mean_field": getattr(args, "gp_mean_field", 0.0)} if gp_layer else {}
+    evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration, **gp_eval)      # noqa: E731
+    extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ())
     if args.eval:
         stats = evaluate()
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
+        if gp_layer:
+            print(gp_variance_line(stats))
         if calibration:
             print(calibration_line(stats))
-            if args.output_dir:
-                with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
-                    f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5")},
-                                        **{f"test_{k}": stats[k] for k in CALIB_KEYS}}) + "\n")
+        if extra_keys and args.output_dir:
+            with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
+                f.write(json.dumps({f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)
         return stats
@@ -214,6 +250,8 @@ def main(args):
     for epoch in range(start_epoch, args.epochs):
         log = utils.MetricLogger(delimiter="  ")
         seen = []
+        if gp_layer and probe.cov_momentum <= 0:
+            probe.reset_cov()                     # the exact sum counts the data once: it starts again with every epoch
         for i, ((images, _), labels) in enumerate(log.log_every(DevicePrefetcher(loader_train, device), 10, f"Epoch: [{epoch}]")):
             lr = float(lr_values[epoch * steps_per_epoch + i])
             loss, gnorm = probe.train_step(images, labels.to(device, non_blocking=True), lr, args.weight_decay, args.clip_grad)
@@ -225,6 +263,8 @@ def main(args):
             publish(log, l0, g0)
         stats = evaluate()
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f}")
+        if gp_layer:
+            print(gp_variance_line(stats))
         if calibration:
             print(calibration_line(stats))
         print(f"Epoch {epoch}: loss: {log.loss.global_avg:.4f}  lr: {log.lr.value:.8f}  acc1: {stats['acc1']:.3f}  acc5: {stats['acc5']:.3f}")
@@ -232,7 +272,7 @@ def main(args):
             save_probe(args, probe, epoch)
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({"epoch": epoch, "train_loss": log.loss.global_avg, "train_lr": log.lr.value,
-                                    **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + (CALIB_KEYS if calibration else ())}})
+                                    **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys}})
                         + "\n")
     print("Training time %.0f s" % (time.time() - t0))
     return stats

@@ -28,6 +28,10 @@ pids+=($!)
 # stability.hip finds NaN rows with z != z, compares in IEEE and fixes the order of every sum (bit-identical runs): no fast-math
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c stability.hip -o obj/stability.o ) &
 pids+=($!)
+# gp.hip fixes the order of every sum (bit-identical runs, a bit-symmetric precision matrix) and needs the accurate cosf / sinf:
+# no fast-math
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c gp.hip -o obj/gp.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

@@ -57,9 +57,16 @@ class LinearProbe(nn.Module):
             raise ValueError(f"smoothing must be in [0, 1), got {smoothing}")
         object.__setattr__(self, "encoder", encoder)
         self.num_classes, self.embed_dim, self.smoothing = K, Cd, float(smoothing)
+        self._setup_head(init_scale)
+        self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
+
+    # ---- arena plumbing (as the encoder's) ----
+    def _setup_head(self, init_scale):
+        """The head's flat arenas, its parameters as views of them, and their initial values (a subclass lays out another head)."""
+        K, Cd = self.num_classes, self.embed_dim
         self._n_decay = K * Cd
         n = K * Cd + (K + 3) // 4 * 4
-        dev = encoder._arena.device
+        dev = self.encoder._arena.device
         self._arena = torch.zeros(n, dtype=torch.float32, device=dev)
         self._grad_arena = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -71,9 +78,7 @@ class LinearProbe(nn.Module):
         self._rebind()
         _timm_trunc_normal_(self.head.weight.data, std=0.02).mul_(init_scale)     # modeling_finetune.py:439-441
         self.head.bias.data.zero_()                                               # constant 0 times init_scale
-        self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
 
-    # ---- arena plumbing (as the encoder's) ----
     def _rebind(self):
         K, Cd = self.num_classes, self.embed_dim
         for p, lo, hi, shape in ((self.head.weight, 0, K * Cd, (K, Cd)), (self.head.bias, K * Cd, K * Cd + K, (K,))):
@@ -178,7 +183,11 @@ class LinearProbe(nn.Module):
                                  ptr(self._stats), None, B, K, s), "uvit_op_probe_ce")
         check(L.uvit_op_probe_head_grad(ptr(self._dlogits), ptr(self._feat), ptr(self._grad_arena),
                                         C.c_void_p(self._grad_arena.data_ptr() + 4 * K * Cd), B, K, Cd, s), "uvit_op_probe_head_grad")
-        n = self._arena.numel()
+        return self._clip_and_update(lr, weight_decay, max_norm)
+
+    def _clip_and_update(self, lr, weight_decay, max_norm):
+        """Global-norm clip + AdamW of the head arena from the gradient arena; returns (loss, grad_norm) of self._stats."""
+        L, s, n = lib(), cur_stream(), self._arena.numel()
         self._sumsq.zero_()
         check(L.uvit_op_sumsq(ptr(self._grad_arena), n, ptr(self._sumsq), s), "uvit_op_sumsq")
         self.step_count += 1

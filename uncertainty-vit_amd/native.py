@@ -201,6 +201,12 @@ _PROTOTYPES = {
     "uvit_op_calib_auroc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "uvit_op_stability_ranks": (_i, [_vp, _vp, _i, _i, _vp]),
     "uvit_op_stability_sequences": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "uvit_op_gp_features": (_i, [_vp] * 5 + [_f, _f] + [_vp] * 3 + [_i, _i, _i, _vp]),
+    "uvit_op_gp_precision_update": (_i, [_vp, _vp, _i, _i, C.c_double, _vp]),
+    "uvit_op_gp_ln_grad_ws_bytes": (_i64, [_i, _i, _i]),
+    "uvit_op_gp_ln_grad": (_i, [_vp] * 5 + [_f] + [_vp] * 3 + [_i, _i, _i, _i, _vp]),
+    "uvit_op_gp_variance": (_i, [_vp, _vp, C.c_double, _vp, _i, _i, _vp]),
+    "uvit_op_gp_mean_field": (_i, [_vp, _vp, C.c_double, _vp, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
