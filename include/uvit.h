@@ -546,6 +546,41 @@ int uvit_op_gp_variance(const float* phi, const double* Sigma, double ridge, dou
  * reference.  factor >= 0; factor = 0 returns the logits bit for bit.  out may alias logits.  One wave per row. */
 int uvit_op_gp_mean_field(const float* logits, const double* var, double factor, float* out, int B, int K, uvit_stream stream);
 
+/* ---- heteroscedastic probe head on the frozen encoder: Monte-Carlo softmax with low-rank-plus-diagonal logit noise, the layer
+ * modeling_finetune.MCSoftmaxDenseFA (:904-1217) describes (edward2's MCSoftmaxDenseFA, non-parameter-efficient form); DESIGN.md
+ * section 9.4 ----
+ * 1 <= B <= 65535, 1 <= S <= 65535 Monte-Carlo samples, 3 <= K <= 4096 classes, 1 <= R <= min(32, K) factors.  fp32.
+ *   lin[b] (K (R + 2)) = [ loc (K) | draw (K) | V (K, R) row-major ], one uvit_op_probe_logits call with K := K (R + 2); d = draw + 1e-3
+ *   u_s = loc + V . epsR_s + d * epsK_s;   y_s = softmax(u_s / T);   p = (1 / S) sum_s y_s,   s = 0 .. S-1
+ * Noise: counter-based on the hash of common.h (uvit_hash32, written h below), regenerated by every kernel, never stored.  With
+ * row = share ? 0 : b and stream t in {0: factors epsR, 1: diagonal epsK}: key_t = h(seed ^ ((t + 1) * 0x9E3779B9u)),
+ * key = h((uint32_t)(row * S + s) ^ key_t); pair q: h1 = h((2 q) ^ key), h2 = h((2 q + 1) ^ key), u_i = ((h_i >> 9) + 0.5) * 2^-23 (exact
+ * in fp32, inside (0, 1)), r = sqrt(-2 ln u1), n[2 q] = r cos(2 pi u2), n[2 q + 1] = r sin(2 pi u2); both values are used, |n| <= 5.8.
+ * share = 1: the draws do not depend on the row (the reference's share_samples_across_batch), so a row's result does not depend on
+ * its place in the batch.
+ * Every call checks its arguments before it touches the device (UVIT_ERR_ARG for a NULL required pointer, a temperature that is
+ * not a positive finite number, an eps outside [0, 1) or a share outside {0, 1}; UVIT_ERR_SHAPE for a size outside the limits; outputs
+ * untouched) and is asynchronous on `stream`.  No float atomics: one wave handles one sample at a time, the samples of a row are split
+ * into ceil(S / cs) <= 8 chunks of cs = 64 ceil(S / 512) samples (a function of S alone, not of the launch), each chunk is summed in
+ * sample order and the chunk sums are added in chunk order by a second kernel, so the same input gives the same bits on every run. */
+/* The draws themselves: epsR (B, S, R) and epsK (B, S, K); either may be NULL and is then left alone.  For tests and debugging: the
+ * step never calls it. */
+int uvit_op_het_noise(float* epsR, float* epsK, int B, int S, int K, int R, uint32_t seed, int share, uvit_stream stream);
+/* scratch of both calls below: ceil(S / cs) * B * K * (R + 2) * 4 bytes, i.e. up to 8 x the size of lin (the backward's chunk sums of
+ * dlin; the forward uses the first ceil(S / cs) * B * 2 K floats of it).  49 MB at B = 128, S = 1000, K = 1000, R = 10.  < 0: the
+ * UVIT_ERR_* of the call. */
+int64_t uvit_op_het_mc_ws_bytes(int B, int S, int K, int R);
+/* p (B, K, required: the backward reads it) = the Monte-Carlo mean of the softmax; z (B, K, nullable) = log(clamp(p, eps, 1)), the
+ * head's "logits"; pvar (B, K, nullable) = max((1 / S) sum_s y_s^2 - p^2, 0).  p holds the same bits whether or not z and pvar are asked for. */
+int uvit_op_het_mc_forward(const float* lin, float* z, float* p, float* pvar, float* scratch, int B, int S, int K, int R,
+                           float temperature, float eps, uint32_t seed, int share, uvit_stream stream);
+/* dlin (B, K (R + 2)), overwritten, in the layout of lin, from dz (B, K), the gradient of the loss at z, and the forward's p:
+ *   dp[k] = eps <= p[k] <= 1 ? dz[k] / p[k] : 0;   a_s = <y_s, dp>;   du_s = y_s * (dp - a_s) / (S T)
+ *   dloc = sum_s du_s;   ddraw[k] = sum_s du_s[k] epsK_s[k];   dV[k, r] = sum_s du_s[k] epsR_s[r]
+ * with the draws of the same (seed, share).  One uvit_op_probe_head_grad call on dlin then gives the gradients of the three layers. */
+int uvit_op_het_mc_backward(const float* lin, const float* p, const float* dz, float* dlin, float* scratch, int B, int S, int K, int R,
+                            float temperature, float eps, uint32_t seed, int share, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,14 @@ data are counted once), `--gp_cov_ridge_penalty` (1e-3), `--gp_kernel_scale` (1.
 `* GP variance mean ...` after `* Acc@1` and log.txt gains `test_gp_var_mean`, the mean predictive variance over the evaluation set.
 `--gp_mean_field FACTOR` (default 0: off) evaluates on edward2's mean-field logits z / sqrt(1 + FACTOR * var), an addition to the
 reference.  `--calibration` and `--perturbation_path` work with the head unchanged.
+
+`--het_layer` (the reference's flag; exclusive with --gp_layer) replaces the nn.Linear by the heteroscedastic head the reference's
+modeling_finetune.MCSoftmaxDenseFA describes (uncertainty-vit_amd/het_probe.py): the logits get a Gaussian noise with an
+input-dependent low-rank-plus-diagonal covariance and the prediction is the Monte-Carlo mean of the softmax over that noise.
+`--het_num_factors R` (10), `--het_temperature` (1.0), `--het_train_mc_samples` (1000), `--het_test_mc_samples` (1000), `--het_seed`
+(42).  Every evaluation then prints a line `* Het variance mean ...` after `* Acc@1` and log.txt gains `test_het_var_mean`, the mean
+over the evaluation set of the Monte-Carlo variance of the predicted class's probability.  `--calibration` and `--perturbation_path`
+work with the head unchanged.
 """
 import argparse
 import json
@@ -87,11 +95,19 @@ def get_args(argv=None):
     a("--gp_kernel_scale", type=float, default=argparse.SUPPRESS, help="the cosine is multiplied by 1 / sqrt(this) (default 1.0)")
     a("--gp_mean_field", type=float, default=argparse.SUPPRESS, metavar="FACTOR",
       help="evaluate on the mean-field logits z / sqrt(1 + FACTOR * var) (edward2's mean_field_logits; default 0: off)")
+    a("--het_layer", action="store_true", default=argparse.SUPPRESS,
+      help="probe with the heteroscedastic head (modeling_finetune.MCSoftmaxDenseFA: Monte-Carlo softmax, low-rank logit noise)")
+    a("--het_num_factors", type=int, default=argparse.SUPPRESS, metavar="R", help="rank of the noise covariance's low-rank part (default 10)")
+    a("--het_temperature", type=float, default=argparse.SUPPRESS, help="softmax temperature of the Monte-Carlo samples (default 1.0)")
+    a("--het_train_mc_samples", type=int, default=argparse.SUPPRESS, help="Monte-Carlo samples of a training step (default 1000)")
+    a("--het_test_mc_samples", type=int, default=argparse.SUPPRESS, help="Monte-Carlo samples of an evaluation (default 1000)")
+    a("--het_seed", type=int, default=argparse.SUPPRESS, help="seed of the noise (default 42, what the reference re-seeds with)")
     return p.parse_args(argv)
 
 
 CALIB_KEYS = ("ECE", "TACE", "NLL", "AUROC")
 GP_FLAGS = ("gp_num_inducing", "gp_cov_momentum", "gp_cov_ridge_penalty", "gp_kernel_scale", "gp_mean_field")
+HET_FLAGS = ("het_num_factors", "het_temperature", "het_train_mc_samples", "het_test_mc_samples", "het_seed")
 
 
 def calibration_line(stats):
@@ -100,6 +116,10 @@ def calibration_line(stats):
 
 def gp_variance_line(stats):
     return "* GP variance mean {gp_var_mean:.6f}".format(**stats)
+
+
+def het_variance_line(stats):
+    return "* Het variance mean {het_var_mean:.6f}".format(**stats)
 
 
 def perturbation_files(args):
@@ -185,6 +205,11 @@ def main(args):
     gp_layer = getattr(args, "gp_layer", False)
     if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
         raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
+    het_layer = getattr(args, "het_layer", False)
+    if not het_layer and any(hasattr(args, k) for k in HET_FLAGS):
+        raise ValueError("--het_* options belong to the heteroscedastic head: give --het_layer")
+    if het_layer and gp_layer:
+        raise ValueError("--het_layer and --gp_layer are two heads: give one")
     device = torch.device("cuda")
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
@@ -200,6 +225,11 @@ def main(args):
         probe = GPProbe(encoder, args.nb_classes, smoothing=args.smoothing, num_inducing=getattr(args, "gp_num_inducing", None),
                         kernel_scale=getattr(args, "gp_kernel_scale", 1.0), cov_momentum=getattr(args, "gp_cov_momentum", 0.999),
                         cov_ridge_penalty=getattr(args, "gp_cov_ridge_penalty", 1e-3))
+    elif het_layer:
+        from uncertainty_vit_amd.het_probe import HetProbe
+        probe = HetProbe(encoder, args.nb_classes, smoothing=args.smoothing, num_factors=getattr(args, "het_num_factors", 10),
+                         temperature=getattr(args, "het_temperature", 1.0), train_mc_samples=getattr(args, "het_train_mc_samples", 1000),
+                         test_mc_samples=getattr(args, "het_test_mc_samples", 1000), seed=getattr(args, "het_seed", 42))
     else:
         probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
     print("Trainable weights: %s" % [n for n, p in probe.named_parameters() if p.requires_grad])
@@ -214,14 +244,16 @@ def main(args):
     eval_root = args.eval_data_path or args.data_path
     loader_val, _ = build_loader(args, encoder, eval_root, 1, train=False)
     calibration = getattr(args, "calibration", False)
-    gp_eval = {"variance": True, "mean_field": getattr(args, "gp_mean_field", 0.0)} if gp_layer else {}
+    gp_eval = {"variance": True, "mean_field": getattr(args, "gp_mean_field", 0.0)} if gp_layer else {"variance": True} if het_layer else {}
     evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration, **gp_eval)      # noqa: E731
-    extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ())
+    extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ()) + (("het_var_mean",) if het_layer else ())
     if args.eval:
         stats = evaluate()
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
         if gp_layer:
             print(gp_variance_line(stats))
+        if het_layer:
+            print(het_variance_line(stats))
         if calibration:
             print(calibration_line(stats))
         if extra_keys and args.output_dir:
@@ -265,6 +297,8 @@ def main(args):
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f}")
         if gp_layer:
             print(gp_variance_line(stats))
+        if het_layer:
+            print(het_variance_line(stats))
         if calibration:
             print(calibration_line(stats))
         print(f"Epoch {epoch}: loss: {log.loss.global_avg:.4f}  lr: {log.lr.value:.8f}  acc1: {stats['acc1']:.3f}  acc5: {stats['acc5']:.3f}")

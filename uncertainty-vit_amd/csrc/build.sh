@@ -32,6 +32,10 @@ pids+=($!)
 # no fast-math
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c gp.hip -o obj/gp.o ) &
 pids+=($!)
+# het.hip fixes the order of every sum (bit-identical runs) and needs the accurate logf / sincosf / expf of its Gaussian draws and
+# its softmax: no fast-math
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c het.hip -o obj/het.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

@@ -207,6 +207,10 @@ _PROTOTYPES = {
     "uvit_op_gp_ln_grad": (_i, [_vp] * 5 + [_f] + [_vp] * 3 + [_i, _i, _i, _i, _vp]),
     "uvit_op_gp_variance": (_i, [_vp, _vp, C.c_double, _vp, _i, _i, _vp]),
     "uvit_op_gp_mean_field": (_i, [_vp, _vp, C.c_double, _vp, _i, _i, _vp]),
+    "uvit_op_het_noise": (_i, [_vp, _vp, _i, _i, _i, _i, _u32, _i, _vp]),
+    "uvit_op_het_mc_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "uvit_op_het_mc_forward": (_i, [_vp] * 5 + [_i, _i, _i, _i, _f, _f, _u32, _i, _vp]),
+    "uvit_op_het_mc_backward": (_i, [_vp] * 5 + [_i, _i, _i, _i, _f, _f, _u32, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
