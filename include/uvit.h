@@ -581,6 +581,51 @@ int uvit_op_het_mc_forward(const float* lin, float* z, float* p, float* pvar, fl
 int uvit_op_het_mc_backward(const float* lin, const float* p, const float* dz, float* dlin, float* scratch, int B, int S, int K, int R,
                             float temperature, float eps, uint32_t seed, int share, uvit_stream stream);
 
+/* ---- ensemble probe head on the frozen encoder: M linear heads behind one pooled feature vector, the deep ensemble the reference
+ * evaluates with --ensembles (engine_for_finetuning.ensembles_evaluate, :225-343); DESIGN.md section 9.5 ----
+ * B >= 1, K >= 1 classes, 1 <= M <= 16 members.  fp32 unless stated otherwise.  The head arena is [W (M K, C) | bias (M K) | pad to 4]
+ * with n_decay = M K C, member m owning rows m K .. (m + 1) K - 1, so lin (B, M K) is one uvit_op_probe_logits call and the head
+ * gradient one uvit_op_probe_head_grad call, both with K := M K.
+ * Every call checks its arguments before it touches the device (UVIT_ERR_ARG for a NULL required pointer, a smoothing outside [0, 1)
+ * or a mode outside {0, 1}; UVIT_ERR_SHAPE for B < 1, K < 1, M outside [1, 16] or C % 4 != 0; outputs untouched) and is asynchronous
+ * on `stream`.  No float atomics; every floating sum has one owner and a fixed order that depends neither on the launch shape nor on
+ * M, so the same input gives the same bits on every run and member m's outputs are those of an M = 1 call on its slice. */
+/* w (B, M): the online-bagging weights (Oza & Russell), Poisson(1) per (row, member), counter-based on the hash of common.h (uvit_hash32, written h):
+ * key = h(seed ^ 0x9E3779B9u), hh = h((uint32_t)(b M + m) ^ key), w[b, m] = #{n in 0..7 : (hh >> 9) >= T[n]} as a float in 0..8,
+ * T = {3085997, 6171993, 7714992, 8229324, 8357907, 8383624, 8387910, 8388523} = ceil(2^23 e^-1 sum_{i <= n} 1 / i!): integer
+ * comparisons, so a host restatement agrees exactly.  uvit_op_ens_ce takes the weights as an input; nothing is stored between steps. */
+int uvit_op_ens_bag_weights(float* w, int B, int M, uint32_t seed, uvit_stream stream);
+/* The members' smoothed cross-entropies, one wave per (row, member) with uvit_op_probe_ce's formulas on z = lin[b, m K : (m + 1) K]
+ * (lse - v is formed as log(sum_k exp(z_k - max)) - (v - max), so the row maximum cancels exactly):
+ *   row_loss[b, m] (B, M) = (1 - s)(lse - z_y) + s (lse - mean_k z_k), unweighted;
+ *   loss_out (M + 1): loss_out[m] = (1 / B) sum_b w[b, m] row_loss[b, m], each member summed by one wave in row order, then
+ *   loss_out[M] = their mean, added in member order;  weights (B, M, nullable): w = 1;
+ *   dlin (B, M K, nullable) = w[b, m] (softmax(z)_k - (1 - s)[k == y] - s / K) / B, the gradient of sum_m loss_out[m]: every member
+ *   receives exactly its own gradient;
+ *   top1_top5 (nullable, ACCUMULATED int32 (M, 2)): uvit_op_probe_ce's two rules per member.
+ * A label outside [0, K) makes that row's losses and gradients NaN for every member (and so every entry of loss_out); nothing is
+ * read at that label and no counter moves. */
+int uvit_op_ens_ce(const float* lin, const int64_t* labels, const float* weights, float smoothing, float* dlin, float* row_loss,
+                   float* loss_out, int32_t* top1_top5, int B, int M, int K, uvit_stream stream);
+/* Per-member gradient clip on the gradient arena [dW (M K, C) | dbias (M K) | pad]: member m's segments start at m K C and at
+ * M K C + m K floats (the second is not 16-byte aligned in general; C % 4 == 0, C >= 4).  One workgroup per member sums the squares
+ * of its K C weights and K biases in double (per-thread strided partial sums over quads of four adjacent elements, a fixed tree; the
+ * same order whether or not grad is 16-byte aligned), norms[m] (M) = (float)sqrt of it, and
+ * with max_norm > 0 multiplies the member's entries in place by fminf(max_norm / (norms[m] + 1e-6f), 1.0f) (uvit_op_adamw's
+ * expression).  max_norm <= 0 only writes the norms.  A member whose sum is not finite is left as it is: uvit_op_adamw's guard then
+ * skips the whole update. */
+int uvit_op_ens_clip(float* grad, float* norms, int M, int K, int C, float max_norm, uvit_stream stream);
+/* z (B, K) from lin (B, M K), one wave per row; lse_m = log-sum-exp of member m's logits, p_m[k] = expf(lin[b, m, k] - lse_m), the
+ * difference formed as (lin[b, m, k] - max_m) - log(sum_k exp(lin[b, m, k] - max_m)):
+ *   mode 0: z[k] = (sum_m lin[b, m, k]) / M, added in member order: torch.mean(torch.stack(outputs), 0), engine_for_finetuning.py:288-290;
+ *   mode 1: z[k] = log((1 / M) sum_m p_m[k]) as a max-shifted log-sum-exp over m of lin[b, m, k] - lse_m, no clamp.
+ * unc (B, 5, double, nullable), with pbar = (1 / M) sum_m p_m, k* = argmax z and k_m = argmax lin[b, m, :] (lowest index on ties):
+ *   {total = -sum_k pbar log pbar, aleatoric = -(1 / M) sum_m sum_k p_m log p_m, mi = max(total - aleatoric, 0),
+ *    var_pred = (1 / M) sum_m (p_m[k*] - pbar[k*])^2, disagreement = #{m : k_m != k*} / M}.
+ * p_m is formed in fp32 and widened; every sum and logarithm of unc is double, 0 log 0 = 0.  A row that holds a NaN logit gives five
+ * NaNs; z follows IEEE arithmetic.  z holds the same bits whether or not unc is asked for. */
+int uvit_op_ens_combine(const float* lin, int mode, float* z, double* unc, int B, int M, int K, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,18 @@ input-dependent low-rank-plus-diagonal covariance and the prediction is the Mont
 (42).  Every evaluation then prints a line `* Het variance mean ...` after `* Acc@1` and log.txt gains `test_het_var_mean`, the mean
 over the evaluation set of the Monte-Carlo variance of the predicted class's probability.  `--calibration` and `--perturbation_path`
 work with the head unchanged.
+
+`--ensembles` (the reference's flag; exclusive with --gp_layer and --het_layer) trains and evaluates an ensemble of linear heads on
+the one frozen encoder (uncertainty-vit_amd/ens_probe.py): the members share the encoder forward of every batch, each receives its own
+gradient and its own gradient clip, and the evaluation is on their combination.  `--ens_members M` (5, at most 16), `--ens_combine
+logits|probs` (`logits`: the mean of the members' logits, the reference's; `probs`: the logarithm of the mean of their softmaxes),
+`--ens_bagging` (online bagging: a Poisson(1) weight per member and sample presentation; off by default, an addition to the
+reference), `--ens_seed` (0).  `--eval --ens_heads A.pth B.pth ...` assembles the ensemble from the `model` entries of separately
+trained linear-probe checkpoints (probe-N.pth), the reference's workflow; the member count is the number of files.  Every evaluation
+then prints, after the ensemble's `* Acc@1` line, one `* Member m Acc@1 ... Acc@5 ... loss ...` line per member and
+`* Ens entropy ... expected ... MI ... variance ... disagreement ...`; log.txt gains `test_member{m}_acc1`, `test_ens_total`,
+`test_ens_aleatoric`, `test_ens_mi`, `test_ens_var`, `test_ens_disagreement`.  `--calibration` and `--perturbation_path` work on the
+combined logits unchanged.
 """
 import argparse
 import json
@@ -102,12 +114,24 @@ def get_args(argv=None):
     a("--het_train_mc_samples", type=int, default=argparse.SUPPRESS, help="Monte-Carlo samples of a training step (default 1000)")
     a("--het_test_mc_samples", type=int, default=argparse.SUPPRESS, help="Monte-Carlo samples of an evaluation (default 1000)")
     a("--het_seed", type=int, default=argparse.SUPPRESS, help="seed of the noise (default 42, what the reference re-seeds with)")
+    a("--ensembles", action="store_true", default=argparse.SUPPRESS,
+      help="probe with an ensemble of linear heads on the one frozen encoder and evaluate their combination (the reference's flag)")
+    a("--ens_members", type=int, default=argparse.SUPPRESS, metavar="M", help="members of the ensemble (default 5, at most 16)")
+    a("--ens_combine", type=str, choices=["logits", "probs"], default=argparse.SUPPRESS,
+      help="logits: the mean of the members' logits (default, the reference's); probs: the logarithm of the mean of their softmaxes")
+    a("--ens_bagging", action="store_true", default=argparse.SUPPRESS,
+      help="online bagging: a Poisson(1) weight per member and sample presentation (default: every member sees every sample once)")
+    a("--ens_seed", type=int, default=argparse.SUPPRESS, help="seed of the bagging weights (default 0)")
+    a("--ens_heads", type=str, nargs="+", default=argparse.SUPPRESS, metavar="PTH",
+      help="with --eval: assemble the ensemble from separately trained linear-probe checkpoints (probe-N.pth); sets the member count")
     return p.parse_args(argv)
 
 
 CALIB_KEYS = ("ECE", "TACE", "NLL", "AUROC")
 GP_FLAGS = ("gp_num_inducing", "gp_cov_momentum", "gp_cov_ridge_penalty", "gp_kernel_scale", "gp_mean_field")
 HET_FLAGS = ("het_num_factors", "het_temperature", "het_train_mc_samples", "het_test_mc_samples", "het_seed")
+ENS_FLAGS = ("ens_members", "ens_combine", "ens_bagging", "ens_seed", "ens_heads")
+ENS_KEYS = ("ens_total", "ens_aleatoric", "ens_mi", "ens_var", "ens_disagreement")
 
 
 def calibration_line(stats):
@@ -120,6 +144,28 @@ def gp_variance_line(stats):
 
 def het_variance_line(stats):
     return "* Het variance mean {het_var_mean:.6f}".format(**stats)
+
+
+def ens_member_count(args):
+    """Members of the ensemble: the number of --ens_heads files when given, else --ens_members (5)."""
+    heads = getattr(args, "ens_heads", None)
+    return len(heads) if heads is not None else getattr(args, "ens_members", 5)
+
+
+def ens_lines(stats):
+    """One line per member, then the entropy split of the ensemble."""
+    rows = zip(stats["member_acc1"], stats["member_acc5"], stats["member_loss"])
+    lines = [f"* Member {m} Acc@1 {a1:.3f} Acc@5 {a5:.3f} loss {loss:.3f}" for m, (a1, a5, loss) in enumerate(rows)]
+    lines.append("* Ens entropy {ens_total:.5f} expected {ens_aleatoric:.5f} MI {ens_mi:.5f} variance {ens_var:.6f} "
+                 "disagreement {ens_disagreement:.5f}".format(**stats))
+    return lines
+
+
+def ens_log_entries(stats):
+    """What log.txt gains for an ensemble: every member's top-1 accuracy and the five means."""
+    out = {f"test_member{m}_acc1": v for m, v in enumerate(stats["member_acc1"])}
+    out.update({f"test_{k}": stats[k] for k in ENS_KEYS})
+    return out
 
 
 def perturbation_files(args):
@@ -210,6 +256,19 @@ def main(args):
         raise ValueError("--het_* options belong to the heteroscedastic head: give --het_layer")
     if het_layer and gp_layer:
         raise ValueError("--het_layer and --gp_layer are two heads: give one")
+    ensembles = getattr(args, "ensembles", False)
+    if not ensembles and any(hasattr(args, k) for k in ENS_FLAGS):
+        raise ValueError("--ens_* options belong to the ensemble: give --ensembles")
+    if ensembles and (gp_layer or het_layer):
+        raise ValueError("--ensembles is an ensemble of linear heads: give it without --gp_layer / --het_layer")
+    ens_heads = getattr(args, "ens_heads", None)
+    if ens_heads is not None:
+        if not args.eval:
+            raise ValueError("--ens_heads assembles an ensemble for an evaluation: give --eval")
+        if args.resume:
+            raise ValueError("--ens_heads and --resume both name the heads: give one")
+        if hasattr(args, "ens_members") and args.ens_members != len(ens_heads):
+            raise ValueError(f"--ens_members {args.ens_members} but --ens_heads names {len(ens_heads)} files")
     device = torch.device("cuda")
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
@@ -230,6 +289,18 @@ def main(args):
         probe = HetProbe(encoder, args.nb_classes, smoothing=args.smoothing, num_factors=getattr(args, "het_num_factors", 10),
                          temperature=getattr(args, "het_temperature", 1.0), train_mc_samples=getattr(args, "het_train_mc_samples", 1000),
                          test_mc_samples=getattr(args, "het_test_mc_samples", 1000), seed=getattr(args, "het_seed", 42))
+    elif ensembles:
+        from uncertainty_vit_amd.ens_probe import EnsembleProbe
+        ens_kw = dict(smoothing=args.smoothing, combine=getattr(args, "ens_combine", "logits"), bagging=getattr(args, "ens_bagging", False),
+                      seed=getattr(args, "ens_seed", 0))
+        if ens_heads is not None:
+            heads = [torch.load(path, map_location="cpu", weights_only=False)["model"] for path in ens_heads]
+            probe = EnsembleProbe.from_heads(encoder, heads, **ens_kw)
+            if probe.num_classes != args.nb_classes:
+                raise ValueError(f"--ens_heads hold {probe.num_classes} classes, --nb_classes is {args.nb_classes}")
+            print("Ensemble of %d heads: %s" % (probe.members, list(ens_heads)))
+        else:
+            probe = EnsembleProbe(encoder, args.nb_classes, members=ens_member_count(args), **ens_kw)
     else:
         probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
     print("Trainable weights: %s" % [n for n, p in probe.named_parameters() if p.requires_grad])
@@ -245,6 +316,8 @@ def main(args):
     loader_val, _ = build_loader(args, encoder, eval_root, 1, train=False)
     calibration = getattr(args, "calibration", False)
     gp_eval = {"variance": True, "mean_field": getattr(args, "gp_mean_field", 0.0)} if gp_layer else {"variance": True} if het_layer else {}
+    if ensembles:
+        gp_eval = {"members": True, "uncertainty": True}
     evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration, **gp_eval)      # noqa: E731
     extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ()) + (("het_var_mean",) if het_layer else ())
     if args.eval:
@@ -254,11 +327,14 @@ def main(args):
             print(gp_variance_line(stats))
         if het_layer:
             print(het_variance_line(stats))
+        if ensembles:
+            print("\n".join(ens_lines(stats)))
         if calibration:
             print(calibration_line(stats))
-        if extra_keys and args.output_dir:
+        if (extra_keys or ensembles) and args.output_dir:
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
-                f.write(json.dumps({f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys}) + "\n")
+                f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
+                                    **(ens_log_entries(stats) if ensembles else {})}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)
         return stats
@@ -299,6 +375,8 @@ def main(args):
             print(gp_variance_line(stats))
         if het_layer:
             print(het_variance_line(stats))
+        if ensembles:
+            print("\n".join(ens_lines(stats)))
         if calibration:
             print(calibration_line(stats))
         print(f"Epoch {epoch}: loss: {log.loss.global_avg:.4f}  lr: {log.lr.value:.8f}  acc1: {stats['acc1']:.3f}  acc5: {stats['acc5']:.3f}")
@@ -306,7 +384,8 @@ def main(args):
             save_probe(args, probe, epoch)
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({"epoch": epoch, "train_loss": log.loss.global_avg, "train_lr": log.lr.value,
-                                    **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys}})
+                                    **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
+                                    **(ens_log_entries(stats) if ensembles else {})})
                         + "\n")
     print("Training time %.0f s" % (time.time() - t0))
     return stats

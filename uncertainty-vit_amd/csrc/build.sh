@@ -36,6 +36,10 @@ pids+=($!)
 # its softmax: no fast-math
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c het.hip -o obj/het.o ) &
 pids+=($!)
+# ens.hip fixes the order of every sum (bit-identical runs, a member's outputs independent of the member count), finds NaN rows with
+# v != v and needs the accurate expf / logf of its softmax and entropies: no fast-math
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c ens.hip -o obj/ens.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

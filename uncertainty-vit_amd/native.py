@@ -211,6 +211,10 @@ _PROTOTYPES = {
     "uvit_op_het_mc_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "uvit_op_het_mc_forward": (_i, [_vp] * 5 + [_i, _i, _i, _i, _f, _f, _u32, _i, _vp]),
     "uvit_op_het_mc_backward": (_i, [_vp] * 5 + [_i, _i, _i, _i, _f, _f, _u32, _i, _vp]),
+    "uvit_op_ens_bag_weights": (_i, [_vp, _i, _i, _u32, _vp]),
+    "uvit_op_ens_ce": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "uvit_op_ens_clip": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
+    "uvit_op_ens_combine": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
