@@ -626,6 +626,44 @@ int uvit_op_ens_clip(float* grad, float* norms, int M, int K, int C, float max_n
  * NaNs; z follows IEEE arithmetic.  z holds the same bits whether or not unc is asked for. */
 int uvit_op_ens_combine(const float* lin, int mode, float* z, double* unc, int B, int M, int K, uvit_stream stream);
 
+/* ---- set-level detection metrics of per-sample uncertainty scores: misclassification and out-of-distribution detection, DESIGN.md
+ * section 9.6 ----
+ * The store of an evaluation is S fp32 columns of ld elements each (column s starts at scores + s ld) and one uint8 flag per sample;
+ * every column is oriented so that larger means more uncertain.  Every call checks its arguments before it touches the device
+ * (UVIT_ERR_ARG for a NULL required pointer, UVIT_ERR_SHAPE for a size outside the stated limits, UVIT_ERR_WORKSPACE, outputs
+ * untouched) and is asynchronous on `stream`.  No atomics; every sum has one owner and a fixed order, so the same input gives the
+ * same bits on every run, and no workgroup waits for another. */
+/* Per batch, one wave per row of logits z (B, K) fp32, B >= 1, K >= 1, 0 <= n0, n0 + B <= ld.  Writes at position n0 + b of columns
+ * 0, 1, 2:  msp = 1 - max_k softmax(z)_k,  entropy = -sum_k p_k log p_k (0 log 0 = 0),  energy = -logsumexp(z); expf in fp32, the row
+ * sums and everything behind them in double, rounded once to fp32.  flags[n0 + b] = 1 when the lowest index attaining max z differs
+ * from labels[b], else 0; 2 for a label outside [0, K), and nothing is read at that label.  labels == NULL (images without labels):
+ * no flag is written and flags may be NULL. */
+int uvit_op_detect_rows(const float* logits, const int64_t* labels, float* scores, int64_t ld, int64_t n0, uint8_t* flags, int B, int K,
+                        uvit_stream stream);
+/* dst[b] = (float) src[b stride] for b < B: a head's own per-sample column (float, or double with src_is_double = 1; stride >= 1 in
+ * elements) into a column of the store; the caller offsets both pointers. */
+int uvit_op_detect_column(const void* src, int src_is_double, int64_t stride, float* dst, int B, uvit_stream stream);
+/* Set level, 1 <= N <= 2^20 samples, 1 <= S <= 16 columns, ld >= N; ws: uvit_op_detect_ws_bytes(N, S) bytes (< 0: the UVIT_ERR_* of the
+ * call), 16-byte aligned.  positive = flag 1.  Per column, a 64-bit key per sample: order-preserving image of the fp32 score << 32 |
+ * sample index << 2 | [flag >= 2] << 1 | [flag == 1].  -0 ranks as +0.  A NaN score gets the image 0xFFFFFFFF: NaN rows sort behind
+ * every number by index, are counted and take no part in the metrics.  The keys are sorted ascending by a bitonic network over N
+ * padded to a power of two (all-ones padding): 4096-key chunks in LDS, one launch per compare-exchange distance >= 4096; the keys
+ * are all different, so the sorted order (ties in score by ascending index) does not depend on the network.  An inclusive prefix
+ * count of the positives in sorted order follows (three launches), then the metrics.  Tie groups are runs of equal image; walking
+ * from the most uncertain end with TP_i, FP_i the cumulative positives and negatives at the end of group i, P and Nn the totals
+ * over the n ranked samples:
+ *   AUROC = sum_i (FP_i - FP_{i-1}) (TP_i + TP_{i-1}) / (2 P Nn)           int64 numerator, exact
+ *   AUPR  = sum_i ((TP_i - TP_{i-1}) / P) TP_i / (TP_i + FP_i)             average precision, double
+ *   FPR95 = FP_i / Nn at the first group with TP_i >= ceil(19 P / 20)       exact integers
+ *   AURC  = (1 / n) sum_{k = 1..n} (positives among the k least uncertain) / k, in the ascending order of the keys, double
+ * The double sums are formed per 4096 sorted positions (16 consecutive positions per thread in ascending order, a fixed tree over
+ * the threads) and the segments are added in order by one thread.  out (S, 8) double = {AUROC, AUPR, FPR95, AURC, n, P, N - n, 0};
+ * AUROC and FPR95 are NaN when P = 0 or Nn = 0, AUPR when P = 0, AURC when n = 0; a flag >= 2 anywhere among the N makes all four
+ * NaN in every column.  order (S, N) int32, nullable: the sample indices in sorted order, the NaN rows last by index. */
+int64_t uvit_op_detect_ws_bytes(int N, int S);
+int uvit_op_detect_metrics(const float* scores, int64_t ld, const uint8_t* flags, int N, int S, int32_t* order, double* out, void* ws,
+                           int64_t ws_bytes, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

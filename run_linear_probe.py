@@ -49,6 +49,14 @@ then prints, after the ensemble's `* Acc@1` line, one `* Member m Acc@1 ... Acc@
 `* Ens entropy ... expected ... MI ... variance ... disagreement ...`; log.txt gains `test_member{m}_acc1`, `test_ens_total`,
 `test_ens_aleatoric`, `test_ens_mi`, `test_ens_var`, `test_ens_disagreement`.  `--calibration` and `--perturbation_path` work on the
 combined logits unchanged.
+
+`--eval --detection` asks whether each per-sample uncertainty ranks the wrong predictions above the right ones: the columns `msp`
+(1 - max softmax), `entropy` and `energy` (-logsumexp) of the evaluated logits, plus `gp_var`, `het_var` or the five `ens_*` columns of
+the head in use, are sorted over the whole evaluation set on the device and the run prints, per column,
+`* Detect misclassification <column> AUROC ... AUPR ... FPR95 ... AURC ...`.  `--ood_data_path DIR` (implies --detection) sends the
+images of another data set, an image folder whose class folders are ignored, through the same forward and adds
+`* Detect OOD <column> AUROC ... AUPR ... FPR95 ...` (positive = OOD image).  log.txt gains `test_mis_<column>_<metric>` and
+`test_ood_<column>_<metric>`.
 """
 import argparse
 import json
@@ -124,6 +132,10 @@ def get_args(argv=None):
     a("--ens_seed", type=int, default=argparse.SUPPRESS, help="seed of the bagging weights (default 0)")
     a("--ens_heads", type=str, nargs="+", default=argparse.SUPPRESS, metavar="PTH",
       help="with --eval: assemble the ensemble from separately trained linear-probe checkpoints (probe-N.pth); sets the member count")
+    a("--detection", action="store_true", default=argparse.SUPPRESS,
+      help="with --eval: does each uncertainty column rank the wrong predictions above the right ones (AUROC, AUPR, FPR95, AURC over the set)")
+    a("--ood_data_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
+      help="with --eval: image folder of another data set (its class folders are ignored); adds the OOD detection metrics, implies --detection")
     return p.parse_args(argv)
 
 
@@ -165,6 +177,31 @@ def ens_log_entries(stats):
     """What log.txt gains for an ensemble: every member's top-1 accuracy and the five means."""
     out = {f"test_member{m}_acc1": v for m, v in enumerate(stats["member_acc1"])}
     out.update({f"test_{k}": stats[k] for k in ENS_KEYS})
+    return out
+
+
+def check_detection_flags(args):
+    """Whether the run computes the detection metrics: --detection or --ood_data_path (which implies it); both belong to --eval."""
+    want = getattr(args, "detection", False) or hasattr(args, "ood_data_path")
+    if want and not args.eval:
+        raise ValueError("--detection / --ood_data_path belong to an evaluation: give --eval")
+    return bool(want)
+
+
+def detection_lines(det):
+    """One line per column and question, from stats["detection"]."""
+    lines = ["* Detect misclassification {} AUROC {AUROC:.5f} AUPR {AUPR:.5f} FPR95 {FPR95:.5f} AURC {AURC:.5f}".format(c, **det["misclassification"][c])
+             for c in det["columns"]]
+    if "ood" in det:
+        lines += ["* Detect OOD {} AUROC {AUROC:.5f} AUPR {AUPR:.5f} FPR95 {FPR95:.5f}".format(c, **det["ood"][c]) for c in det["columns"]]
+    return lines
+
+
+def detection_log_entries(det):
+    """What log.txt gains: test_mis_<column>_<metric> and, with OOD images, test_ood_<column>_<metric>."""
+    out = {f"test_mis_{c}_{k}": v for c in det["columns"] for k, v in det["misclassification"][c].items()}
+    if "ood" in det:
+        out.update({f"test_ood_{c}_{k}": v for c in det["columns"] for k, v in det["ood"][c].items()})
     return out
 
 
@@ -248,6 +285,7 @@ def main(args):
         raise ValueError("--finetune <pre-training checkpoint> is required")
     if (hasattr(args, "perturbation_path") or hasattr(args, "perturbations")) and not (args.eval and hasattr(args, "perturbation_path")):
         raise ValueError("--perturbation_path / --perturbations belong to an evaluation: give --eval and --perturbation_path DIR")
+    detection = check_detection_flags(args)
     gp_layer = getattr(args, "gp_layer", False)
     if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
         raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
@@ -318,6 +356,11 @@ def main(args):
     gp_eval = {"variance": True, "mean_field": getattr(args, "gp_mean_field", 0.0)} if gp_layer else {"variance": True} if het_layer else {}
     if ensembles:
         gp_eval = {"members": True, "uncertainty": True}
+    if detection:
+        gp_eval["detection"] = True
+        if hasattr(args, "ood_data_path"):
+            loader_ood, _ = build_loader(args, encoder, args.ood_data_path, 1, train=False)
+            gp_eval["ood_loader"] = DevicePrefetcher(loader_ood, device)
     evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration, **gp_eval)      # noqa: E731
     extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ()) + (("het_var_mean",) if het_layer else ())
     if args.eval:
@@ -331,10 +374,13 @@ def main(args):
             print("\n".join(ens_lines(stats)))
         if calibration:
             print(calibration_line(stats))
-        if (extra_keys or ensembles) and args.output_dir:
+        if detection:
+            print("\n".join(detection_lines(stats["detection"])))
+        if (extra_keys or ensembles or detection) and args.output_dir:
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
-                                    **(ens_log_entries(stats) if ensembles else {})}) + "\n")
+                                    **(ens_log_entries(stats) if ensembles else {}),
+                                    **(detection_log_entries(stats["detection"]) if detection else {})}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)
         return stats

@@ -40,6 +40,10 @@ pids+=($!)
 # v != v and needs the accurate expf / logf of its softmax and entropies: no fast-math
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c ens.hip -o obj/ens.o ) &
 pids+=($!)
+# detect.hip finds NaN scores with v != v, needs the accurate expf of its row scores and fixes the order of every sum (bit-identical
+# runs, a sorted order that is a function of the input alone): no fast-math
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c detect.hip -o obj/detect.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

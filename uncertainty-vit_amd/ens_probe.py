@@ -124,12 +124,16 @@ class EnsembleProbe(LinearProbe):
         """The members' logits, then the combination z into self._logits.  Inside evaluate(members=, uncertainty=) the members'
         criterion and the uncertainty columns of the batch go to device slabs that are read after the last batch."""
         self._lin_into(B)
-        ev = self._eval
+        ev, det = self._eval, self._det is not None
         slab = None
-        if ev is not None and ev["unc"] is not None:
+        if det or (ev is not None and ev["unc"] is not None):
             slab = torch.zeros(B, 5, dtype=torch.float64, device=self._arena.device)
-            ev["unc"].append(slab)
+            if ev is not None and ev["unc"] is not None and not self._in_ood:
+                ev["unc"].append(slab)
         self._combine_into(B, slab)
+        if det:      # evaluate(detection=True): the five columns of the batch go to the set-level store
+            for col, name in enumerate(UNC_KEYS):
+                self._det_column(name, slab[:, col], B)
         if ev is not None and ev["losses"] is not None and ev.get("labels") is not None:
             M, dev = self.members, self._arena.device
             if ev["counters"] is None:
@@ -181,15 +185,18 @@ class EnsembleProbe(LinearProbe):
         return self._member_loss[M], gnorm
 
     # ---- evaluation ----
-    def evaluate(self, loader, calibration=False, members=False, uncertainty=False):
+    DETECT_COLUMNS = LinearProbe.DETECT_COLUMNS + UNC_KEYS
+
+    def evaluate(self, loader, calibration=False, members=False, uncertainty=False, detection=False, ood_loader=None):
         """LinearProbe.evaluate on z.  `members`: the result gains the lists `member_loss`, `member_acc1`, `member_acc5` (plain
         cross-entropy and accuracies in percent of every member, one uvit_op_ens_ce call per batch) and `member_correct1`,
         `member_correct5`.  `uncertainty`: the means over the set of the five columns of uncertainty() as `ens_total`, `ens_aleatoric`,
         `ens_mi`, `ens_var`, `ens_disagreement`, over the rows without a NaN; `ens_nan_rows` counts the others.  Everything comes
-        from per-batch device slabs that are read once, after the last batch."""
+        from per-batch device slabs that are read once, after the last batch.  `detection`, `ood_loader`: as LinearProbe.evaluate on
+        z, with the five columns of uncertainty() beside the three of the logits, whatever `uncertainty` says."""
         self._eval = {"losses": [] if members else None, "unc": [] if uncertainty else None, "counters": None, "labels": None}
         try:
-            stats = super().evaluate(loader, calibration=calibration)
+            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader)
             ev, M, n = self._eval, self.members, stats["n"]
             if members:
                 nan = [float("nan")] * M

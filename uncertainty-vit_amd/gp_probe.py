@@ -153,13 +153,15 @@ class GPProbe(LinearProbe):
               "uvit_op_probe_logits")
         if keep:
             return
-        var = None
-        if self._var_slabs is not None:          # evaluate(variance=True): the batch's variances stay on the device until the last batch
+        var, det = None, self._det is not None
+        if self._var_slabs is not None and not self._in_ood:     # evaluate(variance=True): the batch's variances stay on the device until the last batch
             var = torch.empty(B, dtype=torch.float64, device=self._arena.device)
             self._var_slabs.append(var)
-        if var is not None or self._mf > 0.0:
+        if var is not None or self._mf > 0.0 or det:
             var = self._var if var is None else var
             self._variance_into(B, var)
+        if det:                                  # evaluate(detection=True): the variance is a column of the set-level store
+            self._det_column("gp_var", var, B)
         if self._mf > 0.0:
             check(lib().uvit_op_gp_mean_field(ptr(self._logits), ptr(var), C.c_double(self._mf), ptr(self._logits), B, K, cur_stream()),
                   "uvit_op_gp_mean_field")
@@ -207,14 +209,17 @@ class GPProbe(LinearProbe):
             raise native.UvitError(f"mean_field must be >= 0, got {mean_field}")
         return mf
 
-    def evaluate(self, loader, calibration=False, variance=False, mean_field=0.0):
+    DETECT_COLUMNS = LinearProbe.DETECT_COLUMNS + ("gp_var",)
+
+    def evaluate(self, loader, calibration=False, variance=False, mean_field=0.0, detection=False, ood_loader=None):
         """LinearProbe.evaluate on the GP logits; the precision matrix is not touched.  `variance`: the result gains `gp_var_mean`, the
         mean predictive variance over the set, from per-batch device slabs read after the last batch.  `mean_field` > 0: loss,
-        accuracy and calibration are computed from edward2's mean-field logits z / sqrt(1 + mean_field * var) (an addition: the
-        reference has no such step); 0 leaves the logits as they are."""
+        accuracy, calibration and the detection scores are computed from edward2's mean-field logits z / sqrt(1 + mean_field * var)
+        (an addition: the reference has no such step); 0 leaves the logits as they are.  `detection`, `ood_loader`: as
+        LinearProbe.evaluate, with the predictive variance as the column `gp_var` whatever `variance` says."""
         self._mf, self._var_slabs = self._factor(mean_field), [] if variance else None
         try:
-            stats = super().evaluate(loader, calibration=calibration)
+            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader)
             if variance:
                 host = torch.cat(self._var_slabs).cpu().tolist() if self._var_slabs else []
                 stats["gp_var_mean"] = math.fsum(host) / len(host) if host else float("nan")

@@ -130,11 +130,15 @@ class HetProbe(LinearProbe):
 
     def _logits_into(self, B):
         """Evaluation: the draws are shared across the batch under the fixed seed, so a row's logits do not depend on its place."""
-        want = self._var_slabs is not None
-        self._mc_into(B, self.test_mc_samples, self.seed, 1, pvar=want)
-        if want:     # evaluate(variance=True): the variance at the predicted class stays on the device until the last batch
+        want, det = self._var_slabs is not None and not self._in_ood, self._det is not None
+        self._mc_into(B, self.test_mc_samples, self.seed, 1, pvar=want or det)
+        if want or det:
             pred = self._logits[:B].argmax(1, keepdim=True)
-            self._var_slabs.append(self._pvar[:B].gather(1, pred).squeeze(1))
+            var = self._pvar[:B].gather(1, pred).squeeze(1)
+            if want:     # evaluate(variance=True): the variance at the predicted class stays on the device until the last batch
+                self._var_slabs.append(var)
+            if det:      # evaluate(detection=True): it is a column of the set-level store
+                self._det_column("het_var", var, B)
 
     def predictive_variance(self, images):
         """(B, K) fp32: the variance over the Monte-Carlo samples of each class's softmax probability (compute_pred_variance)."""
@@ -164,12 +168,15 @@ class HetProbe(LinearProbe):
         return self._clip_and_update(lr, weight_decay, max_norm)
 
     # ---- evaluation ----
-    def evaluate(self, loader, calibration=False, variance=False):
+    DETECT_COLUMNS = LinearProbe.DETECT_COLUMNS + ("het_var",)
+
+    def evaluate(self, loader, calibration=False, variance=False, detection=False, ood_loader=None):
         """LinearProbe.evaluate on z.  `variance`: the result gains `het_var_mean`, the mean over the set of the predictive variance at
-        each sample's predicted class, from per-batch device slabs read once after the last batch."""
+        each sample's predicted class, from per-batch device slabs read once after the last batch.  `detection`, `ood_loader`: as
+        LinearProbe.evaluate, with that variance as the column `het_var` whatever `variance` says."""
         self._var_slabs = [] if variance else None
         try:
-            stats = super().evaluate(loader, calibration=calibration)
+            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader)
             if variance:
                 host = torch.cat(self._var_slabs).cpu().tolist() if self._var_slabs else []
                 stats["het_var_mean"] = math.fsum(host) / len(host) if host else float("nan")

@@ -25,6 +25,8 @@ __all__ = ["LinearProbe", "build_probe_encoder", "load_encoder_checkpoint"]
 CALIB_MAX_BINS = 64          # csrc/calib.hip: 1 <= n_bins <= 64, 1 <= B <= 1024
 ECE_BINS, TACE_BINS, TACE_THRESHOLD = 15, 30, 0.01      # the reference's defaults (uncertainty_evaluations.py:200,243)
 STABILITY_MAX_FRAMES = 256   # csrc/stability.hip: 2 <= F <= 256, 1 <= V <= 65535, 1 <= K <= 4096
+DETECT_MAX_N, DETECT_MAX_S = 1 << 20, 16     # csrc/detect.hip: 1 <= N <= 2^20 samples, 1 <= S <= 16 columns
+DETECT_KEYS = ("AUROC", "AUPR", "FPR95", "AURC")        # the first four entries of a row of uvit_op_detect_metrics' table
 
 
 def _timm_trunc_normal_(t, std):
@@ -41,6 +43,9 @@ class LinearProbe(nn.Module):
     (K, C) and `head.bias` (K,), the reference's keys).  Owns the head, gradient and Adam moment arenas."""
 
     BETAS, EPS = (0.9, 0.999), 1e-8          # create_optimizer's adamw defaults (optim_factory.py:133-134)
+    # per-sample uncertainty columns of evaluate(detection=True), larger = more uncertain: the three of uvit_op_detect_rows on the
+    # logits; a head with an uncertainty of its own appends its columns
+    DETECT_COLUMNS = ("msp", "entropy", "energy")
 
     def __init__(self, encoder, num_classes, smoothing=0.1, init_scale=0.001):
         super().__init__()
@@ -57,6 +62,7 @@ class LinearProbe(nn.Module):
             raise ValueError(f"smoothing must be in [0, 1), got {smoothing}")
         object.__setattr__(self, "encoder", encoder)
         self.num_classes, self.embed_dim, self.smoothing = K, Cd, float(smoothing)
+        self._det, self._det_ws, self._in_ood = None, None, False
         self._setup_head(init_scale)
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
 
@@ -92,6 +98,7 @@ class LinearProbe(nn.Module):
         self._arena = new.contiguous()
         self._grad_arena, self.exp_avg, self.exp_avg_sq = (fn(t).contiguous() for t in (self._grad_arena, self.exp_avg, self.exp_avg_sq))
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
+        self._det_ws = None
         self._rebind()
         return self
 
@@ -237,8 +244,109 @@ class LinearProbe(nn.Module):
         o = self._calib_out
         return o[0], o[2], o[1], o[3] / o[4]
 
+    # ---- detection: does an uncertainty column rank the wrong predictions, or another data set's images, above the rest? ----
+    def _det_reserve(self, B):
+        """Room for B more samples in the evaluation's store: S fp32 columns of `cap` elements and one uint8 flag per sample, grown
+        geometrically (what is there is copied on the device)."""
+        d = self._det
+        need = d["n"] + B
+        if need > DETECT_MAX_N:
+            raise native.UvitError(f"detection ranks at most {DETECT_MAX_N} samples, the loaders hold more")
+        if need > d["cap"]:
+            cap, dev = min(DETECT_MAX_N, max(need, 2 * d["cap"], 1024)), self._arena.device
+            scores = torch.zeros(len(self.DETECT_COLUMNS), cap, dtype=torch.float32, device=dev)
+            flags = torch.zeros(cap, dtype=torch.uint8, device=dev)
+            if d["n"]:
+                scores[:, :d["n"]].copy_(d["scores"][:, :d["n"]])
+                flags[:d["n"]].copy_(d["flags"][:d["n"]])
+            d.update(scores=scores, flags=flags, cap=cap)
+
+    def _det_column(self, name, src, B):
+        """A head's own column of the current batch -- `src` holds one float or double per row, any row stride -- into the store as
+        fp32, behind the samples stored so far."""
+        d = self._det
+        at = d["scores"].data_ptr() + 4 * (self.DETECT_COLUMNS.index(name) * d["cap"] + d["n"])
+        check(lib().uvit_op_detect_column(ptr(src), int(src.dtype == torch.float64), src.stride(0) if B > 1 else 1, C.c_void_p(at), B,
+                                          cur_stream()), "uvit_op_detect_column")
+
+    def _det_rows(self, B, labels):
+        """The three scores of self._logits[:B] and, with labels, the wrong-prediction flags into the store; the batch is then stored."""
+        d = self._det
+        check(lib().uvit_op_detect_rows(ptr(self._logits), ptr(labels), ptr(d["scores"]), d["cap"], d["n"], ptr(d["flags"]), B,
+                                        self.num_classes, cur_stream()), "uvit_op_detect_rows")
+        d["n"] += B
+
+    def _det_metrics(self, scores, ld, flags, N, S, order=None):
+        """uvit_op_detect_metrics on the current stream: the (S, 8) float64 device table."""
+        ws = lib().uvit_op_detect_ws_bytes(N, S)
+        if ws < 0:
+            check(int(ws), "uvit_op_detect_ws_bytes")
+        if self._det_ws is None or self._det_ws.numel() < ws:
+            self._det_ws = torch.empty(int(ws), dtype=torch.uint8, device=scores.device)
+        out = torch.zeros(S, 8, dtype=torch.float64, device=scores.device)
+        check(lib().uvit_op_detect_metrics(ptr(scores), int(ld), ptr(flags), N, S, ptr(order), ptr(out), ptr(self._det_ws),
+                                           self._det_ws.numel(), cur_stream()), "uvit_op_detect_metrics")
+        return out
+
+    def detection_batch(self, scores, flags, order=False):
+        """The set-level metrics of caller-supplied GPU columns: `scores` (S, N) or (N,) fp32 with larger = more uncertain, `flags` (N,)
+        uint8 with 1 = positive (2: a bad label).  Returns the (S, 8) float64 device table {AUROC, AUPR (average precision), FPR at
+        95 % TPR, AURC, samples ranked, positives among them, NaN scores left out, 0} (include/uvit.h has the definitions); nothing
+        synchronises with the host.  With `order`, also the (S, N) int32 sample indices in ascending (score, index) order, NaN rows
+        last."""
+        if not torch.is_tensor(scores) or not scores.is_cuda or not torch.is_tensor(flags) or not flags.is_cuda:
+            raise native.UvitError("scores and flags must be GPU tensors: the HIP path has no CPU fallback")
+        if scores.ndim == 1:
+            scores = scores.unsqueeze(0)
+        if scores.dtype != torch.float32 or scores.ndim != 2 or not scores.is_contiguous():
+            raise native.UvitError("scores must be a contiguous float32 tensor of shape (S, N)")
+        S, N = scores.shape
+        if not (1 <= S <= DETECT_MAX_S and 1 <= N <= DETECT_MAX_N):
+            raise native.UvitError(f"detection ranks 1 .. {DETECT_MAX_N} samples in 1 .. {DETECT_MAX_S} columns, got {N} in {S}")
+        if flags.dtype != torch.uint8 or flags.shape != (N,) or not flags.is_contiguous():
+            raise native.UvitError(f"flags must be a contiguous uint8 tensor of shape ({N},)")
+        perm = torch.zeros(S, N, dtype=torch.int32, device=scores.device) if order else None
+        out = self._det_metrics(scores, N, flags, N, S, perm)
+        return (out, perm) if order else out
+
+    def _det_launch(self, n_eval, ood_loader):
+        """Behind the last evaluation batch: the out-of-distribution images through the same forward and columns, then one metrics
+        call per question.  Returns the device tables (misclassification, OOD or None) and the number of OOD images."""
+        d, S, n_ood = self._det, len(self.DETECT_COLUMNS), 0
+        mis = self._det_metrics(d["scores"], d["cap"], d["flags"], n_eval, S) if n_eval else None
+        if ood_loader is not None:
+            self._in_ood = True
+            for item in ood_loader:
+                images = item
+                while isinstance(images, (tuple, list)):
+                    images = images[0]
+                B = self._features(images)
+                self._det_reserve(B)
+                self._logits_into(B)
+                self._det_rows(B, None)
+            n_ood = d["n"] - n_eval
+        ood = None
+        if n_eval + n_ood and ood_loader is not None:
+            is_ood = torch.zeros(d["cap"], dtype=torch.uint8, device=d["flags"].device)
+            is_ood[n_eval:n_eval + n_ood] = 1
+            ood = self._det_metrics(d["scores"], d["cap"], is_ood, n_eval + n_ood, S)
+        return mis, ood, n_ood
+
+    def _det_stats(self, mis, ood, n, n_wrong, n_ood, with_ood):
+        """stats["detection"] from the two tables (read here: the evaluation's one synchronisation has happened with the losses)."""
+        cols = list(self.DETECT_COLUMNS)
+        nan = [float("nan")] * 4
+        rows = mis.cpu().tolist() if mis is not None else [nan] * len(cols)
+        out = {"columns": cols, "n": n, "n_wrong": n_wrong,
+               "misclassification": {c: dict(zip(DETECT_KEYS, r[:4])) for c, r in zip(cols, rows)}}
+        if with_ood:
+            rows = ood.cpu().tolist() if ood is not None else [nan] * len(cols)
+            out["ood"] = {c: dict(zip(DETECT_KEYS[:3], r[:3])) for c, r in zip(cols, rows)}
+            out["n_ood"] = n_ood
+        return out
+
     # ---- evaluation ----
-    def evaluate(self, loader, calibration=False):
+    def evaluate(self, loader, calibration=False, detection=False, ood_loader=None):
         """`loader` yields (images, labels) or ((images, mask), labels) on the GPU (the device prefetcher's items).  Plain cross-entropy
         (the reference's evaluate() uses nn.CrossEntropyLoss) and top-1 / top-5 accuracy in percent, from device-side per-batch
         losses and integer counters that are read once, after the last batch.  With `calibration`, every batch (at most 1024 samples)
@@ -246,7 +354,23 @@ class LinearProbe(nn.Module):
         per-batch values, the reference's meters (engine_for_finetuning.py:207-213), ECE and TACE with the reference's bin accuracy
         (calibration_batch's reference_bin_accuracy=True).  A batch in which no class has both a positive
         and a negative row has no AUROC and is left out of that mean only; AUROC_zero_absent is the weighted mean of
-        (sum of the per-class values) / K, i.e. with every class absent from a batch scored 0."""
+        (sum of the per-class values) / K, i.e. with every class absent from a batch scored 0.
+        With `detection` (implied by `ood_loader`), every batch also writes its per-sample uncertainty columns (DETECT_COLUMNS) and
+        wrong-prediction flags into a device store, and one set-level call behind the last batch ranks all samples per column:
+        stats["detection"] = {"columns", "n", "n_wrong", "misclassification": {column: {AUROC, AUPR, FPR95, AURC}}} with positive =
+        wrong prediction.  `ood_loader` yields images of another data set (labels, if any, are ignored): they go through the same
+        forward and columns behind the evaluation set, take no part in loss, accuracy, calibration or any mean, and a second call
+        with positive = OOD image adds "ood": {column: {AUROC, AUPR, FPR95}} and "n_ood".  The two small tables are read with the
+        losses.  Without the two arguments nothing else is launched or returned."""
+        detection = bool(detection) or ood_loader is not None
+        self._det = {"scores": None, "flags": None, "cap": 0, "n": 0} if detection else None
+        try:
+            return self._evaluate(loader, calibration, ood_loader)
+        finally:
+            self._det, self._in_ood = None, False
+
+    def _evaluate(self, loader, calibration, ood_loader):
+        detection = self._det is not None
         losses, sizes, counters = [], [], None
         calib = []
         for item in loader:
@@ -261,6 +385,8 @@ class LinearProbe(nn.Module):
                 counters = torch.zeros(2, dtype=torch.int32, device=images.device)
             if len(losses) % 256 == 0:
                 slab = torch.zeros(256, dtype=torch.float32, device=images.device)
+            if detection:
+                self._det_reserve(B)
             self._logits_into(B)
             slot = C.c_void_p(slab.data_ptr() + 4 * (len(losses) % 256))
             check(lib().uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(0.0), None, ptr(self._row_loss), slot, ptr(counters), B,
@@ -271,12 +397,18 @@ class LinearProbe(nn.Module):
                     cslab = torch.zeros(256, 5, dtype=torch.float64, device=images.device)
                 self._calibration_into(self._logits, labels, B, cslab.data_ptr() + 40 * (len(calib) % 256))
                 calib.append((cslab, len(calib) % 256))
+            if detection:
+                self._det_rows(B, labels)
             losses.append((slab, len(losses) % 256))
             sizes.append(B)
+        if detection:
+            mis, ood, n_ood = self._det_launch(sum(sizes), ood_loader)
         if not sizes:
             empty = {"loss": float("nan"), "acc1": float("nan"), "acc5": float("nan"), "n": 0}
             if calibration:
                 empty.update({k: float("nan") for k in ("ECE", "TACE", "NLL", "AUROC", "AUROC_zero_absent")})
+            if detection:
+                empty["detection"] = self._det_stats(mis, ood, 0, 0, n_ood, ood_loader is not None)
             return empty
         slabs = {id(s): s for s, _ in losses}
         host = {k: v.cpu() for k, v in slabs.items()}                       # the one read
@@ -292,6 +424,8 @@ class LinearProbe(nn.Module):
             have = [(r[3] / r[4], b) for r, b in zip(rows, sizes) if r[4] > 0]
             stats["AUROC"] = sum(a * b for a, b in have) / sum(b for _, b in have) if have else float("nan")
             stats["AUROC_zero_absent"] = sum(r[3] / self.num_classes * b for r, b in zip(rows, sizes)) / n
+        if detection:
+            stats["detection"] = self._det_stats(mis, ood, n, n - c1, n_ood, ood_loader is not None)
         return stats
 
     # ---- stability under perturbation sequences ----

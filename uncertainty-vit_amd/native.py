@@ -215,6 +215,10 @@ _PROTOTYPES = {
     "uvit_op_ens_ce": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "uvit_op_ens_clip": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
     "uvit_op_ens_combine": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "uvit_op_detect_rows": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _i, _i, _vp]),
+    "uvit_op_detect_column": (_i, [_vp, _i, _i64, _vp, _i, _vp]),
+    "uvit_op_detect_ws_bytes": (_i64, [_i, _i]),
+    "uvit_op_detect_metrics": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
