@@ -664,6 +664,35 @@ int64_t uvit_op_detect_ws_bytes(int N, int S);
 int uvit_op_detect_metrics(const float* scores, int64_t ld, const uint8_t* flags, int N, int S, int32_t* order, double* out, void* ws,
                            int64_t ws_bytes, uvit_stream stream);
 
+/* ---- post-hoc temperature scaling, fitted and applied on the device, DESIGN.md section 9.7 ----
+ * s = 1 / T minimises f(s) = (1 / n) sum_i [ log sum_k exp(s z_ik) - s z_i,y_i ], the mean NLL of softmax(z / T), over
+ * [1 / t_max, 1 / t_min]; g = f' = (1 / n) sum_i [ sum_k p_ik z_ik - z_i,y_i ] is non-decreasing and h = f'' = (1 / n) sum_i Var_p_i[z_i].
+ * Every call checks its arguments before it touches the device (UVIT_ERR_ARG for a NULL required pointer or a misaligned workspace,
+ * UVIT_ERR_SHAPE for a size or a setting outside the stated limits, UVIT_ERR_WORKSPACE, outputs untouched) and is asynchronous on
+ * `stream`.  No atomics; every sum has one owner and a fixed order that depends on N and K alone, so the same input gives the same
+ * bits on every run and for every ld; no workgroup waits for another and nothing is read back to the host. */
+/* Workspace of uvit_op_ts_fit in bytes; UVIT_ERR_SHAPE unless 1 <= N <= 2^20 and K >= 2. */
+int64_t uvit_op_ts_ws_bytes(int N, int K);
+/* logits (N, ld >= K) fp32, labels (N) int64, out: 8 doubles on the device, ws: uvit_op_ts_ws_bytes(N, K) bytes, 16-byte aligned.
+ * UVIT_ERR_SHAPE also for t_min <= 0, t_max <= t_min or not finite, tol <= 0, max_iter outside [1, 64].
+ * A row pass: one wave per row, 16 rows per workgroup; m = max_k z_k, d_k = z_k - m in fp32, e_k = expf((float)(s (double) d_k)), then
+ * double: S = sum e_k, T1 = sum e_k d_k, T2 = sum e_k d_k^2 (lane partial sums over ascending k, the xor tree), row values
+ * log S - s d_y, T1 / S - d_y, T2 / S - (T1 / S)^2 with d_y = z_y - m formed in fp32; a workgroup adds its rows in ascending order and
+ * writes one partial per quantity, one workgroup adds the partials in a fixed order and takes the step.
+ * Pass 1 evaluates s_max = 1 / t_min, s_min = 1 / t_max, s_0 = 1 clamped to [s_min, s_max], and 1 in one read.  g(s_max) <= 0: the
+ * result is s_max, status 2; g(s_min) >= 0: s_min, status 1.  Otherwise a bracketed Newton from s_0: the pass at s moves the bracket
+ * [lo, hi] by the sign of g(s); the candidate s - g / h is replaced by sqrt(lo hi) when h is not positive and finite or the candidate
+ * is not inside (lo, hi); status 0 when |candidate - s| <= tol s or g == 0, status 3 after max_iter passes.  The result is the last
+ * point evaluated.  2 max_iter launches are enqueued up front; those behind the end read the device state and return at once.
+ * out = {T = 1 / s clamped to [max(t_min, 1 / s_max), min(t_max, 1 / s_min)], s, NLL at s = 1, NLL at the result, g at the result,
+ * passes used, status, rows left out}.  A label outside [0, K) makes all eight NaN and nothing is read at that label.  A row with a
+ * non-finite logit is left out and counted; when no row remains T, s, the NLLs and g are NaN (passes 1, status 0). */
+int uvit_op_ts_fit(const float* logits, int64_t ld, const int64_t* labels, int N, int K, double t_min, double t_max, double tol,
+                   int max_iter, double* out, void* ws, int64_t ws_bytes, uvit_stream stream);
+/* dst[b, k] = (float)((double) src[b, k] * s) for b < B, k < K, with s = table[1] read on the device (the table of uvit_op_ts_fit, or
+ * any 8 doubles); ld_src, ld_dst >= K; dst == src is allowed.  A NaN s gives NaN logits; s > 0 is a monotone map, ranks are kept. */
+int uvit_op_ts_scale(const float* src, float* dst, int64_t ld_src, int64_t ld_dst, const double* table, int B, int K, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,15 @@ the head in use, are sorted over the whole evaluation set on the device and the 
 images of another data set, an image folder whose class folders are ignored, through the same forward and adds
 `* Detect OOD <column> AUROC ... AUPR ... FPR95 ...` (positive = OOD image).  log.txt gains `test_mis_<column>_<metric>` and
 `test_ood_<column>_<metric>`.
+
+`--eval --ts_data_path DIR` repairs the head's calibration by post-hoc temperature scaling (Guo et al., 2017; an addition to the
+reference): DIR is a labelled image folder with the evaluation's classes, read with the evaluation pipeline; one scalar T is fitted
+on it on the device by minimising the NLL of softmax(z / T) (`--ts_tol`, default 1e-7, and `--ts_max_iter`, default 16, are the stopping
+rule), and `--eval_data_path` is then evaluated on z / T.  The accuracy does not change; loss, the calibration metrics and the msp,
+entropy and energy columns do.  Before `* Acc@1` the run prints
+`* Temperature <T> NLL <before> -> <after> on <n> calibration images (<iterations> passes, <status>)` and log.txt gains
+`test_ts_temperature`, `test_ts_nll_before`, `test_ts_nll_after`, `test_ts_n`, `test_ts_iterations`, `test_ts_status`.
+`--ts_temperature T` applies a given T without a fit (log.txt: `test_ts_temperature` alone); the two are exclusive.
 """
 import argparse
 import json
@@ -136,6 +145,12 @@ def get_args(argv=None):
       help="with --eval: does each uncertainty column rank the wrong predictions above the right ones (AUROC, AUPR, FPR95, AURC over the set)")
     a("--ood_data_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
       help="with --eval: image folder of another data set (its class folders are ignored); adds the OOD detection metrics, implies --detection")
+    a("--ts_data_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
+      help="with --eval: labelled image folder (the evaluation's classes) on which a post-hoc temperature is fitted before the evaluation")
+    a("--ts_temperature", type=float, default=argparse.SUPPRESS, metavar="T",
+      help="with --eval: evaluate on logits / T for this T, without a fit (exclusive with --ts_data_path)")
+    a("--ts_tol", type=float, default=argparse.SUPPRESS, help="relative step at which the temperature fit stops (default 1e-7)")
+    a("--ts_max_iter", type=int, default=argparse.SUPPRESS, help="passes over the calibration set the fit may take (default 16, at most 64)")
     return p.parse_args(argv)
 
 
@@ -186,6 +201,42 @@ def check_detection_flags(args):
     if want and not args.eval:
         raise ValueError("--detection / --ood_data_path belong to an evaluation: give --eval")
     return bool(want)
+
+
+TS_FLAGS = ("ts_data_path", "ts_temperature", "ts_tol", "ts_max_iter")
+
+
+def check_ts_flags(args):
+    """Whether the run scales its logits by a post-hoc temperature: "fit" (--ts_data_path), "given" (--ts_temperature) or None.  All
+    four --ts_* flags belong to --eval; the two sources of T are exclusive and the stopping rule belongs to the fit."""
+    given = [k for k in TS_FLAGS if hasattr(args, k)]
+    if not given:
+        return None
+    if not args.eval:
+        raise ValueError("--ts_data_path / --ts_temperature / --ts_tol / --ts_max_iter belong to an evaluation: give --eval")
+    if hasattr(args, "ts_data_path") and hasattr(args, "ts_temperature"):
+        raise ValueError("--ts_data_path fits the temperature and --ts_temperature names it: give one (with --eval)")
+    if hasattr(args, "ts_data_path"):
+        return "fit"
+    if hasattr(args, "ts_temperature"):
+        return "given"
+    raise ValueError("--ts_tol / --ts_max_iter steer the fit of --eval --ts_data_path DIR: give it")
+
+
+def temperature_line(fit):
+    """The line in front of `* Acc@1`, from fit_temperature's result."""
+    from uncertainty_vit_amd.linear_probe import TS_STATUS
+    word = TS_STATUS[fit["status"]] if 0 <= fit["status"] < len(TS_STATUS) else "failed"
+    return "* Temperature {T:.5f} NLL {nll_before:.5f} -> {nll_after:.5f} on {n} calibration images ({iterations} passes, {0})".format(word, **fit)
+
+
+def temperature_log_entries(stats, fit=None):
+    """What log.txt gains: the temperature applied and, when it was fitted, the fit's figures."""
+    out = {"test_ts_temperature": stats["temperature"]}
+    if fit is not None:
+        out.update(test_ts_nll_before=fit["nll_before"], test_ts_nll_after=fit["nll_after"], test_ts_n=fit["n"],
+                   test_ts_iterations=fit["iterations"], test_ts_status=fit["status"])
+    return out
 
 
 def detection_lines(det):
@@ -286,6 +337,7 @@ def main(args):
     if (hasattr(args, "perturbation_path") or hasattr(args, "perturbations")) and not (args.eval and hasattr(args, "perturbation_path")):
         raise ValueError("--perturbation_path / --perturbations belong to an evaluation: give --eval and --perturbation_path DIR")
     detection = check_detection_flags(args)
+    ts_mode = check_ts_flags(args)
     gp_layer = getattr(args, "gp_layer", False)
     if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
         raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
@@ -361,10 +413,22 @@ def main(args):
         if hasattr(args, "ood_data_path"):
             loader_ood, _ = build_loader(args, encoder, args.ood_data_path, 1, train=False)
             gp_eval["ood_loader"] = DevicePrefetcher(loader_ood, device)
+    ts_fit = None
+    if ts_mode == "fit":
+        loader_ts, _ = build_loader(args, encoder, args.ts_data_path, 1, train=False)
+        ts_kw = {"mean_field": args.gp_mean_field} if gp_layer and hasattr(args, "gp_mean_field") else {}
+        ts_fit = probe.fit_temperature(DevicePrefetcher(loader_ts, device), tol=getattr(args, "ts_tol", 1e-7),
+                                       max_iter=getattr(args, "ts_max_iter", 16), **ts_kw)
+        gp_eval["temperature"] = True
+    elif ts_mode == "given":
+        gp_eval["temperature"] = args.ts_temperature
     evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration, **gp_eval)      # noqa: E731
     extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ()) + (("het_var_mean",) if het_layer else ())
     if args.eval:
         stats = evaluate()
+        if ts_fit is not None:
+            stats["temperature_fit"] = ts_fit
+            print(temperature_line(ts_fit))
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
         if gp_layer:
             print(gp_variance_line(stats))
@@ -376,11 +440,12 @@ def main(args):
             print(calibration_line(stats))
         if detection:
             print("\n".join(detection_lines(stats["detection"])))
-        if (extra_keys or ensembles or detection) and args.output_dir:
+        if (extra_keys or ensembles or detection or ts_mode) and args.output_dir:
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
                                     **(ens_log_entries(stats) if ensembles else {}),
-                                    **(detection_log_entries(stats["detection"]) if detection else {})}) + "\n")
+                                    **(detection_log_entries(stats["detection"]) if detection else {}),
+                                    **(temperature_log_entries(stats, ts_fit) if ts_mode else {})}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)
         return stats

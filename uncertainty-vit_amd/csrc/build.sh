@@ -44,6 +44,10 @@ pids+=($!)
 # runs, a sorted order that is a function of the input alone): no fast-math
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c detect.hip -o obj/detect.o ) &
 pids+=($!)
+# tscale.hip finds non-finite logits by comparison, needs the accurate expf / log of its row pass (the test bounds are derived from
+# them) and fixes the order of every sum (bit-identical fits, independent of the row stride): no fast-math
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c tscale.hip -o obj/tscale.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

@@ -187,16 +187,18 @@ class EnsembleProbe(LinearProbe):
     # ---- evaluation ----
     DETECT_COLUMNS = LinearProbe.DETECT_COLUMNS + UNC_KEYS
 
-    def evaluate(self, loader, calibration=False, members=False, uncertainty=False, detection=False, ood_loader=None):
+    def evaluate(self, loader, calibration=False, members=False, uncertainty=False, detection=False, ood_loader=None, temperature=None):
         """LinearProbe.evaluate on z.  `members`: the result gains the lists `member_loss`, `member_acc1`, `member_acc5` (plain
         cross-entropy and accuracies in percent of every member, one uvit_op_ens_ce call per batch) and `member_correct1`,
         `member_correct5`.  `uncertainty`: the means over the set of the five columns of uncertainty() as `ens_total`, `ens_aleatoric`,
         `ens_mi`, `ens_var`, `ens_disagreement`, over the rows without a NaN; `ens_nan_rows` counts the others.  Everything comes
         from per-batch device slabs that are read once, after the last batch.  `detection`, `ood_loader`: as LinearProbe.evaluate on
-        z, with the five columns of uncertainty() beside the three of the logits, whatever `uncertainty` says."""
+        z, with the five columns of uncertainty() beside the three of the logits, whatever `uncertainty` says.  `temperature`: as
+        LinearProbe.evaluate, on the combined z; the members' own lines and the five ens_* columns come from the members' logits
+        before the combination and are not scaled."""
         self._eval = {"losses": [] if members else None, "unc": [] if uncertainty else None, "counters": None, "labels": None}
         try:
-            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader)
+            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader, temperature=temperature)
             ev, M, n = self._eval, self.members, stats["n"]
             if members:
                 nan = [float("nan")] * M

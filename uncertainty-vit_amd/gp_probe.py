@@ -211,15 +211,25 @@ class GPProbe(LinearProbe):
 
     DETECT_COLUMNS = LinearProbe.DETECT_COLUMNS + ("gp_var",)
 
-    def evaluate(self, loader, calibration=False, variance=False, mean_field=0.0, detection=False, ood_loader=None):
+    def fit_temperature(self, loader, mean_field=0.0, **kw):
+        """LinearProbe.fit_temperature on the GP logits, on the mean-field logits with `mean_field` > 0: give the factor of the
+        evaluation the temperature is meant for, so that the fit sees the logits that evaluation sees."""
+        self._mf = self._factor(mean_field)
+        try:
+            return super().fit_temperature(loader, **kw)
+        finally:
+            self._mf = 0.0
+
+    def evaluate(self, loader, calibration=False, variance=False, mean_field=0.0, detection=False, ood_loader=None, temperature=None):
         """LinearProbe.evaluate on the GP logits; the precision matrix is not touched.  `variance`: the result gains `gp_var_mean`, the
         mean predictive variance over the set, from per-batch device slabs read after the last batch.  `mean_field` > 0: loss,
         accuracy, calibration and the detection scores are computed from edward2's mean-field logits z / sqrt(1 + mean_field * var)
         (an addition: the reference has no such step); 0 leaves the logits as they are.  `detection`, `ood_loader`: as
-        LinearProbe.evaluate, with the predictive variance as the column `gp_var` whatever `variance` says."""
+        LinearProbe.evaluate, with the predictive variance as the column `gp_var` whatever `variance` says.  `temperature`: as
+        LinearProbe.evaluate, applied behind the mean-field step; `gp_var` and `gp_var_mean` do not depend on it."""
         self._mf, self._var_slabs = self._factor(mean_field), [] if variance else None
         try:
-            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader)
+            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader, temperature=temperature)
             if variance:
                 host = torch.cat(self._var_slabs).cpu().tolist() if self._var_slabs else []
                 stats["gp_var_mean"] = math.fsum(host) / len(host) if host else float("nan")

@@ -43,6 +43,10 @@ class HetProbe(LinearProbe):
     bias (K)}, head._scale_layer.{weight (K R, C), bias (K R)}.  `num_factors` R is the rank of the noise covariance's low-rank part;
     the reference re-seeds with 42 on every forward, `seed` has that default."""
 
+    # the softmax temperature of the Monte-Carlo samples, a constructor argument: it keeps the name, so on this head the post-hoc
+    # temperature of LinearProbe is read as `post_hoc_temperature`
+    temperature = 1.0
+
     def __init__(self, encoder, num_classes, smoothing=0.1, num_factors=10, temperature=1.0, train_mc_samples=1000, test_mc_samples=1000,
                  seed=42):
         K, R = int(num_classes), int(num_factors)
@@ -170,13 +174,15 @@ class HetProbe(LinearProbe):
     # ---- evaluation ----
     DETECT_COLUMNS = LinearProbe.DETECT_COLUMNS + ("het_var",)
 
-    def evaluate(self, loader, calibration=False, variance=False, detection=False, ood_loader=None):
+    def evaluate(self, loader, calibration=False, variance=False, detection=False, ood_loader=None, temperature=None):
         """LinearProbe.evaluate on z.  `variance`: the result gains `het_var_mean`, the mean over the set of the predictive variance at
         each sample's predicted class, from per-batch device slabs read once after the last batch.  `detection`, `ood_loader`: as
-        LinearProbe.evaluate, with that variance as the column `het_var` whatever `variance` says."""
+        LinearProbe.evaluate, with that variance as the column `het_var` whatever `variance` says.  `temperature`: as
+        LinearProbe.evaluate, the post-hoc temperature on z (not the softmax temperature of the samples); `het_var` and `het_var_mean`
+        are variances of probabilities formed before it and do not change."""
         self._var_slabs = [] if variance else None
         try:
-            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader)
+            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader, temperature=temperature)
             if variance:
                 host = torch.cat(self._var_slabs).cpu().tolist() if self._var_slabs else []
                 stats["het_var_mean"] = math.fsum(host) / len(host) if host else float("nan")

@@ -27,6 +27,9 @@ ECE_BINS, TACE_BINS, TACE_THRESHOLD = 15, 30, 0.01      # the reference's defaul
 STABILITY_MAX_FRAMES = 256   # csrc/stability.hip: 2 <= F <= 256, 1 <= V <= 65535, 1 <= K <= 4096
 DETECT_MAX_N, DETECT_MAX_S = 1 << 20, 16     # csrc/detect.hip: 1 <= N <= 2^20 samples, 1 <= S <= 16 columns
 DETECT_KEYS = ("AUROC", "AUPR", "FPR95", "AURC")        # the first four entries of a row of uvit_op_detect_metrics' table
+TS_MAX_N = 1 << 20           # csrc/tscale.hip: 1 <= N <= 2^20 calibration samples, K >= 2
+TS_T_MIN, TS_T_MAX, TS_TOL, TS_MAX_ITER = 0.01, 100.0, 1e-7, 16
+TS_STATUS = ("converged", "clamped at T_max", "clamped at T_min", "iteration limit")     # status 0 .. 3 of uvit_op_ts_fit
 
 
 def _timm_trunc_normal_(t, std):
@@ -63,6 +66,9 @@ class LinearProbe(nn.Module):
         object.__setattr__(self, "encoder", encoder)
         self.num_classes, self.embed_dim, self.smoothing = K, Cd, float(smoothing)
         self._det, self._det_ws, self._in_ood = None, None, False
+        # post-hoc temperature: host (T, s) of the fitted or set value, its device table, the table of the running evaluation, the
+        # fit's workspace.  Plain attributes: state_dict() does not see them
+        self._ts, self._ts_table, self._ts_on, self._ts_ws = None, None, None, None
         self._setup_head(init_scale)
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
 
@@ -98,7 +104,7 @@ class LinearProbe(nn.Module):
         self._arena = new.contiguous()
         self._grad_arena, self.exp_avg, self.exp_avg_sq = (fn(t).contiguous() for t in (self._grad_arena, self.exp_avg, self.exp_avg_sq))
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
-        self._det_ws = None
+        self._det_ws = self._ts_table = self._ts_ws = None
         self._rebind()
         return self
 
@@ -323,6 +329,7 @@ class LinearProbe(nn.Module):
                 B = self._features(images)
                 self._det_reserve(B)
                 self._logits_into(B)
+                self._ts_apply(B)
                 self._det_rows(B, None)
             n_ood = d["n"] - n_eval
         ood = None
@@ -345,8 +352,124 @@ class LinearProbe(nn.Module):
             out["n_ood"] = n_ood
         return out
 
+    # ---- post-hoc temperature scaling (csrc/tscale.hip) ----
+    def _ts_fit(self, logits, ld, labels, N, t_min, t_max, tol, max_iter):
+        """uvit_op_ts_fit on the current stream: the (8,) float64 device table."""
+        K = self.num_classes
+        ws = lib().uvit_op_ts_ws_bytes(N, K)
+        if ws < 0:
+            check(int(ws), "uvit_op_ts_ws_bytes")
+        if self._ts_ws is None or self._ts_ws.numel() < ws or self._ts_ws.device != logits.device:
+            self._ts_ws = torch.empty(int(ws), dtype=torch.uint8, device=logits.device)
+        out = torch.zeros(8, dtype=torch.float64, device=logits.device)
+        check(lib().uvit_op_ts_fit(ptr(logits), int(ld), ptr(labels), N, K, float(t_min), float(t_max), float(tol), int(max_iter), ptr(out),
+                                   ptr(self._ts_ws), self._ts_ws.numel(), cur_stream()), "uvit_op_ts_fit")
+        return out
+
+    def temperature_batch(self, logits, labels, t_min=TS_T_MIN, t_max=TS_T_MAX, tol=TS_TOL, max_iter=TS_MAX_ITER):
+        """The temperature T that minimises the mean NLL of softmax(logits / T) over caller-supplied GPU logits (N, K) fp32, N <= 2^20,
+        with int64 labels (N,): the (8,) float64 device table {T, s = 1 / T, NLL at T = 1, NLL at T, dNLL/ds at s, passes used, status,
+        rows left out} of uvit_op_ts_fit (include/uvit.h; status 0 converged, 1 clamped at t_max, 2 clamped at t_min, 3 max_iter passes
+        used up).  Nothing synchronises with the host, and the probe's own temperature is not touched."""
+        if not torch.is_tensor(logits) or not logits.is_cuda:
+            raise native.UvitError("logits must be a GPU tensor: the HIP path has no CPU fallback")
+        if logits.dtype != torch.float32 or logits.ndim != 2 or logits.shape[1] != self.num_classes or not logits.is_contiguous():
+            raise native.UvitError(f"logits must be a contiguous float32 tensor of shape (N, {self.num_classes})")
+        N = logits.shape[0]
+        if not 1 <= N <= TS_MAX_N:
+            raise native.UvitError(f"the temperature fit takes 1 .. {TS_MAX_N} samples, got {N}")
+        return self._ts_fit(logits, self.num_classes, self._labels(labels, N), N, t_min, t_max, tol, max_iter)
+
+    def fit_temperature(self, loader, t_min=TS_T_MIN, t_max=TS_T_MAX, tol=TS_TOL, max_iter=TS_MAX_ITER):
+        """Fit the temperature on a calibration loader (items as evaluate()'s): every batch goes through the forward and the
+        _logits_into of evaluate(), its logits and labels into a device store grown geometrically (at most 2^20 samples), then one
+        uvit_op_ts_fit over the store.  The table stays on the device for evaluate(temperature=True) and is read once:
+        {"T", "nll_before" (at T = 1), "nll_after", "grad" (dNLL/ds at the result), "iterations", "status", "n", "n_skipped" (rows with
+        a non-finite logit)}.  The fit sees the combined logits of an ensemble and the logits a GP or heteroscedastic evaluation sees."""
+        K, store, lab, n = self.num_classes, None, None, 0
+        for item in loader:
+            images, labels = item
+            if isinstance(images, (tuple, list)):
+                images = images[0]
+            B = self._features(images)
+            if torch.is_tensor(labels) and not labels.is_cuda:
+                labels = labels.to(images.device, non_blocking=True)
+            labels = self._labels(labels, B)
+            if n + B > TS_MAX_N:
+                raise native.UvitError(f"the temperature fit takes at most {TS_MAX_N} samples, the loader holds more")
+            if store is None or n + B > store.shape[0]:
+                cap = min(TS_MAX_N, max(n + B, 2 * (store.shape[0] if store is not None else 0), 1024))
+                grown, glab = torch.zeros(cap, K, dtype=torch.float32, device=images.device), torch.zeros(cap, dtype=torch.int64, device=images.device)
+                if n:
+                    grown[:n].copy_(store[:n])
+                    glab[:n].copy_(lab[:n])
+                store, lab = grown, glab
+            self._logits_into(B)
+            store[n:n + B].copy_(self._logits[:B])
+            lab[n:n + B].copy_(labels)
+            n += B
+        if not n:
+            raise native.UvitError("the temperature fit needs at least one calibration sample")
+        table = self._ts_fit(store, K, lab, n, t_min, t_max, tol, max_iter)
+        t = table.cpu().tolist()                                                         # the one read
+        self._ts, self._ts_table = (t[0], t[1]), table
+        nan = math.isnan(t[6])
+        return {"T": t[0], "nll_before": t[2], "nll_after": t[3], "grad": t[4], "iterations": -1 if nan else int(t[5]),
+                "status": -1 if nan else int(t[6]), "n": n, "n_skipped": -1 if nan else int(t[7])}
+
+    def set_temperature(self, T):
+        """Use the temperature T (a positive finite number) in evaluate(temperature=True); None forgets it.  Not a parameter and not
+        a buffer: state_dict() and the checkpoints keep their keys."""
+        if T is None:
+            self._ts = self._ts_table = None
+            return
+        T = float(T)
+        if not 0.0 < T < math.inf:
+            raise ValueError(f"the temperature must be positive and finite, got {T}")
+        self._ts, self._ts_table = (T, 1.0 / T), None
+
+    @property
+    def post_hoc_temperature(self):
+        """The fitted or set post-hoc temperature, None when there is none."""
+        return self._ts[0] if self._ts is not None else None
+
+    @property
+    def temperature(self):
+        """post_hoc_temperature (HetProbe keeps its own `temperature`, the softmax temperature of the Monte-Carlo samples: read
+        `post_hoc_temperature` there)."""
+        return self.post_hoc_temperature
+
+    @staticmethod
+    def _ts_make_table(T, s, device):
+        nan = float("nan")
+        return torch.tensor([T, s, nan, nan, nan, 0.0, 0.0, 0.0], dtype=torch.float64).to(device)
+
+    def _ts_begin(self, temperature):
+        """(device table, host T) of evaluate(temperature=...): None leaves the evaluation as it is."""
+        if temperature is None or temperature is False:
+            return None, None
+        dev = self._arena.device
+        if dev.type != "cuda":
+            raise native.UvitError("the linear probe runs as HIP kernels: move the encoder and the probe to a GPU (no CPU fallback)")
+        if temperature is True:
+            if self._ts is None:
+                raise native.UvitError("evaluate(temperature=True) needs fit_temperature() or set_temperature() first")
+            if self._ts_table is None or self._ts_table.device != dev:
+                self._ts_table = self._ts_make_table(self._ts[0], self._ts[1], dev)
+            return self._ts_table, self._ts[0]
+        T = float(temperature)
+        if not 0.0 < T < math.inf:
+            raise ValueError(f"the temperature must be positive and finite, got {temperature}")
+        return self._ts_make_table(T, 1.0 / T, dev), T
+
+    def _ts_apply(self, B):
+        """Inside evaluate(temperature=...): self._logits[:B] <- (float)((double) z * s), in place, directly behind _logits_into."""
+        if self._ts_on is not None:
+            K = self.num_classes
+            check(lib().uvit_op_ts_scale(ptr(self._logits), ptr(self._logits), K, K, ptr(self._ts_on), B, K, cur_stream()), "uvit_op_ts_scale")
+
     # ---- evaluation ----
-    def evaluate(self, loader, calibration=False, detection=False, ood_loader=None):
+    def evaluate(self, loader, calibration=False, detection=False, ood_loader=None, temperature=None):
         """`loader` yields (images, labels) or ((images, mask), labels) on the GPU (the device prefetcher's items).  Plain cross-entropy
         (the reference's evaluate() uses nn.CrossEntropyLoss) and top-1 / top-5 accuracy in percent, from device-side per-batch
         losses and integer counters that are read once, after the last batch.  With `calibration`, every batch (at most 1024 samples)
@@ -361,13 +484,24 @@ class LinearProbe(nn.Module):
         wrong prediction.  `ood_loader` yields images of another data set (labels, if any, are ignored): they go through the same
         forward and columns behind the evaluation set, take no part in loss, accuracy, calibration or any mean, and a second call
         with positive = OOD image adds "ood": {column: {AUROC, AUPR, FPR95}} and "n_ood".  The two small tables are read with the
-        losses.  Without the two arguments nothing else is launched or returned."""
+        losses.  Without the two arguments nothing else is launched or returned.
+        `temperature`: None launches and returns exactly the above.  True applies the fitted or set post-hoc temperature
+        (fit_temperature, set_temperature; an error when there is none), a number applies that T: uvit_op_ts_scale then runs in place
+        on the logits directly behind every _logits_into of the evaluation, the OOD images included, with 1 / T read from a device
+        table, so loss, accuracy counters, the calibration ops and the three detection columns of the logits (msp, entropy, energy)
+        see z / T, and stats gains "temperature".  Not scaled, because they are formed before the combination or do not depend on the
+        scale of the logits: the members' own lines and the ens_* columns of an ensemble, gp_var, het_var, and everything
+        evaluate_stability reports (ranks do not depend on T)."""
         detection = bool(detection) or ood_loader is not None
+        self._ts_on, ts_value = self._ts_begin(temperature)
         self._det = {"scores": None, "flags": None, "cap": 0, "n": 0} if detection else None
         try:
-            return self._evaluate(loader, calibration, ood_loader)
+            stats = self._evaluate(loader, calibration, ood_loader)
+            if ts_value is not None:
+                stats["temperature"] = ts_value
+            return stats
         finally:
-            self._det, self._in_ood = None, False
+            self._det, self._in_ood, self._ts_on = None, False, None
 
     def _evaluate(self, loader, calibration, ood_loader):
         detection = self._det is not None
@@ -388,6 +522,7 @@ class LinearProbe(nn.Module):
             if detection:
                 self._det_reserve(B)
             self._logits_into(B)
+            self._ts_apply(B)
             slot = C.c_void_p(slab.data_ptr() + 4 * (len(losses) % 256))
             check(lib().uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(0.0), None, ptr(self._row_loss), slot, ptr(counters), B,
                                          self.num_classes, cur_stream()), "uvit_op_probe_ce")
