@@ -693,6 +693,46 @@ int uvit_op_ts_fit(const float* logits, int64_t ld, const int64_t* labels, int N
  * any 8 doubles); ld_src, ld_dst >= K; dst == src is allowed.  A NaN s gives NaN logits; s > 0 is a monotone map, ranks are kept. */
 int uvit_op_ts_scale(const float* src, float* dst, int64_t ld_src, int64_t ld_dst, const double* table, int B, int K, uvit_stream stream);
 
+/* ---- split conformal prediction sets, calibrated and evaluated on the device, DESIGN.md section 9.8 ----
+ * Per row: m = max_k z_k, e_k = expf(z_k - m) in fp32, S = sum_k e_k in double, o_j = 1 + #{i : z_i > z_j} + #{i < j : z_i == z_j} (the
+ * ordinal rank by descending softmax, ties to the smaller index), and with a per-row u in [0, 1] (u == NULL: 1)
+ *   kind 0 (lac):  s_j = 1 - e_j / S
+ *   kind 1 (aps):  s_j = (sum_{i : o_i < o_j} e_i + u e_j) / S        kind 2 (raps): the same + lam * max(0, o_j - kreg)
+ * lam and kreg are read for kind 2 only.  Limits: 1 <= N, B <= 2^20 rows, 2 <= K <= 4096 classes, 1 <= A <= 8 levels, ld >= K.  Every
+ * call checks its arguments before it touches the device (UVIT_ERR_ARG for a NULL required pointer or a misaligned workspace,
+ * UVIT_ERR_SHAPE for a size, a kind, a negative or non-finite lam, a negative kreg or an alpha outside (0, 1), UVIT_ERR_WORKSPACE;
+ * outputs untouched) and is asynchronous on `stream`; nothing is read back to the host.  Every double sum has a fixed order that
+ * depends on K alone; the only atomics add integers, which is exact: the same input gives the same bits on every run. */
+/* scores (N) double = s_y of each row, one wave per row.  A row with a non-finite logit gets a NaN; a label outside [0, K) gets the
+ * NaN 0x7FF8000000000BAD, nothing is read at it, and uvit_op_cp_quantile turns its table to NaN. */
+int uvit_op_cp_scores(const float* logits, int64_t ld, const int64_t* labels, const float* u, int N, int K, int kind, double lam, int kreg,
+                      double* scores, uvit_stream stream);
+/* Workspace of uvit_op_cp_quantile in bytes; UVIT_ERR_SHAPE outside the limits. */
+int64_t uvit_op_cp_ws_bytes(int N, int A);
+/* scores (N) double on the device, non-negative or NaN; alphas: A doubles ON THE HOST, each in (0, 1); table (A, 16) double on the
+ * device; ws 16-byte aligned.  With n the number of non-NaN scores and k_a = ceil((n + 1) (1 - alpha_a)) (the product and the ceiling
+ * in double), q_a is the k_a-th smallest score, found by a radix select on the bit patterns, eight bits per pass: q_a is one of the
+ * input scores bit for bit.  k_a > n: q_a = +inf, status 1.  Row a of the table = {alpha, q, k, n, N - n, status (0 finite, 1 +inf),
+ * then ten slots that uvit_op_cp_finish fills (0 here)}.  A bad-label score anywhere makes all 16 slots of every row NaN. */
+int uvit_op_cp_quantile(const double* scores, int N, const double* alphas, int A, double* table, void* ws, int64_t ws_bytes,
+                        uvit_stream stream);
+/* Number of int64 counters of uvit_op_cp_sets: 4 + 20 A + K (A + 1); UVIT_ERR_SHAPE outside the limits.  Layout: rows used | rows
+ * skipped (a non-finite logit) | bad labels | 0; per level {covered, size sum, empty sets, singletons, largest set, rows of the 7
+ * size bins [0,1] [2,3] [4,6] [7,10] [11,100] [101,1000] [1001,inf), covered rows of the 7 bins, 0}; rows per class (K); covered rows
+ * per level and class (A, K).  The caller zeroes them once; calls over consecutive batches add up to the call over their concatenation. */
+int64_t uvit_op_cp_counter_count(int K, int A);
+/* One evaluation batch against the q of `table` (A, 16): per row and level size = #{j : s_j <= q_a} and covered = [s_y <= q_a], s_y
+ * by the very function uvit_op_cp_scores uses.  One workgroup per row; kinds 1 and 2 sort the row in LDS as 64-bit keys (image of
+ * -z, class index) by a bitonic network over K padded to a power of two and take a double prefix sum in rank order.  sizes (A, ld_out)
+ * int32 and covered (A, ld_out) uint8 are optional (ld_out >= B); a skipped row gets size -1 and covered 0 there.  Rows with a
+ * non-finite logit or a bad label are counted and take part in nothing else. */
+int uvit_op_cp_sets(const float* logits, int64_t ld, const int64_t* labels, const float* u, int B, int K, int kind, double lam, int kreg,
+                    const double* table, int A, int64_t* counters, int32_t* sizes, uint8_t* covered, int64_t ld_out, uvit_stream stream);
+/* Slots 6 .. 15 of every table row from the counters: coverage, mean size, share of empty sets, share of singletons, largest set,
+ * SSCV = max over the non-empty size bins of |coverage in the bin - (1 - alpha)|, worst-class coverage = min over the classes with a
+ * row of covered_c / rows_c, rows used, rows skipped, 0.  The seven metrics are NaN when no row was used, a label was bad or q is NaN. */
+int uvit_op_cp_finish(const int64_t* counters, double* table, int K, int A, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

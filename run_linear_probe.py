@@ -66,6 +66,17 @@ entropy and energy columns do.  Before `* Acc@1` the run prints
 `* Temperature <T> NLL <before> -> <after> on <n> calibration images (<iterations> passes, <status>)` and log.txt gains
 `test_ts_temperature`, `test_ts_nll_before`, `test_ts_nll_after`, `test_ts_n`, `test_ts_iterations`, `test_ts_status`.
 `--ts_temperature T` applies a given T without a fit (log.txt: `test_ts_temperature` alone); the two are exclusive.
+
+`--eval --cp_data_path DIR` calibrates split-conformal prediction sets (an addition to the reference): DIR is a labelled image folder
+with the evaluation's classes (it may be the folder of --ts_data_path).  `--cp_score lac|aps|raps` (default aps; raps with
+`--cp_lambda`, default 0.01, and `--cp_kreg`, default 5) scores every calibration image's label on the device, `--cp_alpha A [A ...]`
+(default 0.1, up to 8 levels) takes the ceil((n + 1)(1 - A))-th smallest score as the threshold, and every evaluation image then
+gets the set of classes whose score does not exceed it: the true class is in the set with probability >= 1 - A, whatever the head.
+`--cp_randomized` (with `--cp_seed`, default 0) randomises the last class of an aps / raps set.  With --ts_data_path or
+--ts_temperature both the calibration and the evaluation see z / T (the temperature is fitted first).  Behind the other lines the run
+prints, per level, `* Conformal <score> alpha <A> qhat <q> coverage <c> size <mean> empty <e> singleton <s> SSCV <v> worst-class <w>
+on <n> calibration images`, and log.txt gains `test_cp_alpha`, `test_cp_qhat`, `test_cp_coverage`, `test_cp_size`, `test_cp_empty`,
+`test_cp_singleton`, `test_cp_sscv`, `test_cp_worst_class` (lists in --cp_alpha order) and `test_cp_n_cal`.
 """
 import argparse
 import json
@@ -151,6 +162,16 @@ def get_args(argv=None):
       help="with --eval: evaluate on logits / T for this T, without a fit (exclusive with --ts_data_path)")
     a("--ts_tol", type=float, default=argparse.SUPPRESS, help="relative step at which the temperature fit stops (default 1e-7)")
     a("--ts_max_iter", type=int, default=argparse.SUPPRESS, help="passes over the calibration set the fit may take (default 16, at most 64)")
+    a("--cp_data_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
+      help="with --eval: labelled image folder (the evaluation's classes) on which conformal prediction sets are calibrated")
+    a("--cp_alpha", type=float, nargs="+", default=argparse.SUPPRESS, metavar="A",
+      help="miscoverage levels of the conformal sets, up to 8 (default 0.1): a set holds the true class with probability >= 1 - A")
+    a("--cp_score", type=str, choices=["lac", "aps", "raps"], default=argparse.SUPPRESS, help="the conformal score (default aps)")
+    a("--cp_lambda", type=float, default=argparse.SUPPRESS, help="raps: the penalty per rank beyond --cp_kreg (default 0.01)")
+    a("--cp_kreg", type=int, default=argparse.SUPPRESS, help="raps: the ranks that carry no penalty (default 5)")
+    a("--cp_randomized", action="store_true", default=argparse.SUPPRESS,
+      help="aps / raps: randomise the last class of a set with a per-image u from a seeded device generator")
+    a("--cp_seed", type=int, default=argparse.SUPPRESS, help="seed of --cp_randomized (default 0)")
     return p.parse_args(argv)
 
 
@@ -236,6 +257,43 @@ def temperature_log_entries(stats, fit=None):
     if fit is not None:
         out.update(test_ts_nll_before=fit["nll_before"], test_ts_nll_after=fit["nll_after"], test_ts_n=fit["n"],
                    test_ts_iterations=fit["iterations"], test_ts_status=fit["status"])
+    return out
+
+
+CP_FLAGS = ("cp_data_path", "cp_alpha", "cp_score", "cp_lambda", "cp_kreg", "cp_randomized", "cp_seed")
+
+
+def check_cp_flags(args):
+    """Whether the run calibrates and reports conformal sets (--cp_data_path).  All --cp_* flags belong to --eval, every other one
+    needs --cp_data_path, and --cp_lambda / --cp_kreg belong to --cp_score raps."""
+    given = [k for k in CP_FLAGS if hasattr(args, k)]
+    if not given:
+        return False
+    if not args.eval:
+        raise ValueError("the --cp_* flags belong to an evaluation: give --eval")
+    if not hasattr(args, "cp_data_path"):
+        raise ValueError("--cp_alpha / --cp_score / --cp_lambda / --cp_kreg / --cp_randomized / --cp_seed steer the conformal calibration "
+                         "of --eval --cp_data_path DIR: give it")
+    if (hasattr(args, "cp_lambda") or hasattr(args, "cp_kreg")) and getattr(args, "cp_score", "aps") != "raps":
+        raise ValueError("--cp_lambda / --cp_kreg are the penalty of --cp_score raps: give it")
+    return True
+
+
+def conformal_lines(fit, conformal):
+    """One line per alpha, from fit_conformal's result and evaluate_conformal's stats["conformal"]."""
+    return ["* Conformal {} alpha {:g} qhat {:.5f} coverage {coverage:.5f} size {size:.3f} empty {empty:.5f} singleton {singleton:.5f} "
+            "SSCV {sscv:.5f} worst-class {worst_class:.5f} on {} calibration images".format(fit["score"], a, q, fit["n"], **conformal[a])
+            for a, q in zip(fit["alpha"], fit["qhat"])]
+
+
+def conformal_log_entries(fit, conformal):
+    """What log.txt gains: the per-alpha lists in --cp_alpha order and the number of calibration images used."""
+    rows = [conformal[a] for a in fit["alpha"]]
+    out = {"test_cp_alpha": list(fit["alpha"]), "test_cp_qhat": list(fit["qhat"])}
+    for key, col in (("coverage", "coverage"), ("size", "size"), ("empty", "empty"), ("singleton", "singleton"), ("sscv", "sscv"),
+                     ("worst_class", "worst_class")):
+        out[f"test_cp_{key}"] = [r[col] for r in rows]
+    out["test_cp_n_cal"] = fit["n"]
     return out
 
 
@@ -338,6 +396,7 @@ def main(args):
         raise ValueError("--perturbation_path / --perturbations belong to an evaluation: give --eval and --perturbation_path DIR")
     detection = check_detection_flags(args)
     ts_mode = check_ts_flags(args)
+    conformal = check_cp_flags(args)
     gp_layer = getattr(args, "gp_layer", False)
     if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
         raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
@@ -422,6 +481,16 @@ def main(args):
         gp_eval["temperature"] = True
     elif ts_mode == "given":
         gp_eval["temperature"] = args.ts_temperature
+    cp_fit = None
+    if conformal:
+        loader_cp, _ = build_loader(args, encoder, args.cp_data_path, 1, train=False)
+        cp_kw = {"mean_field": args.gp_mean_field} if gp_layer and hasattr(args, "gp_mean_field") else {}
+        cp_temp = {"temperature": gp_eval["temperature"]} if ts_mode else {}
+        raps = getattr(args, "cp_score", "aps") == "raps"
+        cp_fit = probe.fit_conformal(DevicePrefetcher(loader_cp, device), alpha=getattr(args, "cp_alpha", [0.1]),
+                                     score=getattr(args, "cp_score", "aps"), lam=getattr(args, "cp_lambda", 0.01) if raps else 0.0,
+                                     kreg=getattr(args, "cp_kreg", 5) if raps else 0, randomized=getattr(args, "cp_randomized", False),
+                                     seed=getattr(args, "cp_seed", 0), **cp_temp, **cp_kw)
     evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration, **gp_eval)      # noqa: E731
     extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ()) + (("het_var_mean",) if het_layer else ())
     if args.eval:
@@ -440,12 +509,17 @@ def main(args):
             print(calibration_line(stats))
         if detection:
             print("\n".join(detection_lines(stats["detection"])))
-        if (extra_keys or ensembles or detection or ts_mode) and args.output_dir:
+        if conformal:
+            stats["conformal_fit"] = cp_fit
+            stats["conformal"] = probe.evaluate_conformal(DevicePrefetcher(loader_val, device), **cp_temp, **cp_kw)["conformal"]
+            print("\n".join(conformal_lines(cp_fit, stats["conformal"])))
+        if (extra_keys or ensembles or detection or ts_mode or conformal) and args.output_dir:
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
                                     **(ens_log_entries(stats) if ensembles else {}),
                                     **(detection_log_entries(stats["detection"]) if detection else {}),
-                                    **(temperature_log_entries(stats, ts_fit) if ts_mode else {})}) + "\n")
+                                    **(temperature_log_entries(stats, ts_fit) if ts_mode else {}),
+                                    **(conformal_log_entries(cp_fit, stats["conformal"]) if conformal else {})}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)
         return stats

@@ -220,6 +220,22 @@ class GPProbe(LinearProbe):
         finally:
             self._mf = 0.0
 
+    def fit_conformal(self, loader, alpha=0.1, mean_field=0.0, **kw):
+        """LinearProbe.fit_conformal on the GP logits, on the mean-field logits with `mean_field` > 0 (as fit_temperature)."""
+        self._mf = self._factor(mean_field)
+        try:
+            return super().fit_conformal(loader, alpha, **kw)
+        finally:
+            self._mf = 0.0
+
+    def evaluate_conformal(self, loader, sizes=False, temperature=None, mean_field=0.0):
+        """LinearProbe.evaluate_conformal on the GP logits, on the mean-field logits with `mean_field` > 0."""
+        self._mf = self._factor(mean_field)
+        try:
+            return super().evaluate_conformal(loader, sizes=sizes, temperature=temperature)
+        finally:
+            self._mf = 0.0
+
     def evaluate(self, loader, calibration=False, variance=False, mean_field=0.0, detection=False, ood_loader=None, temperature=None):
         """LinearProbe.evaluate on the GP logits; the precision matrix is not touched.  `variance`: the result gains `gp_var_mean`, the
         mean predictive variance over the set, from per-batch device slabs read after the last batch.  `mean_field` > 0: loss,

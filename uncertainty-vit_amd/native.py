@@ -222,6 +222,12 @@ _PROTOTYPES = {
     "uvit_op_ts_ws_bytes": (_i64, [_i, _i]),
     "uvit_op_ts_fit": (_i, [_vp, _i64, _vp, _i, _i, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _i64, _vp]),
     "uvit_op_ts_scale": (_i, [_vp, _vp, _i64, _i64, _vp, _i, _i, _vp]),
+    "uvit_op_cp_scores": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp]),
+    "uvit_op_cp_ws_bytes": (_i64, [_i, _i]),
+    "uvit_op_cp_quantile": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i64, _vp]),
+    "uvit_op_cp_counter_count": (_i64, [_i, _i]),
+    "uvit_op_cp_sets": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    "uvit_op_cp_finish": (_i, [_vp, _vp, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
