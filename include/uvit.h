@@ -733,6 +733,43 @@ int uvit_op_cp_sets(const float* logits, int64_t ld, const int64_t* labels, cons
  * row of covered_c / rows_c, rows used, rows skipped, 0.  The seven metrics are NaN when no row was used, a label was bad or q is NaN. */
 int uvit_op_cp_finish(const int64_t* counters, double* table, int K, int A, uvit_stream stream);
 
+/* ---- post-hoc last-layer K-FAC Laplace approximation of the linear head, DESIGN.md section 9.9 ----
+ * f (B, C) is the probe's pooled, normalised feature, phi = [f, 1] has D = C + 1 entries, z = W f + b are the head's logits and
+ * p = softmax(z).  Over the rows of a labelled set: A = sum phi phi^T (D, D), G = (1 / n) sum (diag(p) - p p^T) (K, K), and the
+ * posterior precision of the head's K D parameters is G (x) A + tau I.  With the host's A = U_A diag(lam_A) U_A^T and
+ * G = U_G diag(lam_G) U_G^T the variance of logit k at phi is var_k = sum_i a_i^2 T[i, k], a = U_A^T phi,
+ * T[i, k] = sum_j U_G[k, j]^2 / (lam_A[i] lam_G[j] + tau).
+ * Limits: C % 4 == 0, 4 <= C <= 2048, 2 <= K <= 4096, 1 <= B <= 65535, ld >= K.  Every call checks its arguments before it touches
+ * the device (UVIT_ERR_ARG for a NULL required pointer, a pointer that is not aligned to its element -- a workspace: to 16 bytes --
+ * or a bad scalar, UVIT_ERR_SHAPE for a size outside these limits, UVIT_ERR_WORKSPACE; outputs untouched) and is asynchronous on
+ * `stream`.  All arithmetic is double on fp32 inputs widened.  No atomics; every sum has one owner and a fixed order, so the same
+ * input gives the same bits on every run. */
+/* Workspace of uvit_op_lap_factors in bytes: the softmax (B, K) double, a double and an int32 per row. */
+int64_t uvit_op_lap_factors_ws_bytes(int B, int C, int K);
+/* One batch added in place into A (D, D), G_sum (K, K) (NOT divided by n: the host divides) and sums = {nll = -sum log p[y], rows
+ * used, rows skipped}, all double and zeroed once by the caller.  feat (B, C) fp32, logits (B, ld) fp32, labels (B) int64.  A first
+ * launch writes the max-shifted softmax to ws (lane partial sums over ascending k, the xor tree); then every element of A is one fma
+ * chain over b in ascending order, every element of G_sum is delta_kl sum_b p_bk minus such a chain of p_bk p_bl, and both are added
+ * to the old value; (i, j) and (j, i) come from the same products in the same order: symmetric inputs stay symmetric bit for bit.
+ * A row with a non-finite logit or a label outside [0, K) is left out of everything and counted as skipped. */
+int uvit_op_lap_factors(const float* feat, const float* logits, int64_t ld, const int64_t* labels, double* A, double* G, double* sums,
+                        void* ws, int64_t ws_bytes, int B, int C, int K, uvit_stream stream);
+/* T (D, K) double from UG (K, K; column j the j-th eigenvector), lamA (D) and lamG (K), all double: j in ascending order, one owner
+ * per element.  Once per fit and tau; tau must be positive and finite (UVIT_ERR_ARG). */
+int uvit_op_lap_prepare(const double* UG, const double* lamA, const double* lamG, double tau, double* T, int C, int K, uvit_stream stream);
+/* Workspace of uvit_op_lap_variance in bytes: the squares a^2 (B, D) double. */
+int64_t uvit_op_lap_variance_ws_bytes(int B, int C, int K);
+/* var (B, K) double = (phi UA)^2 T with UA (D, D; column i the i-th eigenvector) and T (D, K) double: two launches of 16 x 32 output
+ * tiles, every element one fma chain over the reduction index in ascending order; a^2 is rounded once, into ws. */
+int uvit_op_lap_variance(const float* feat, const double* UA, const double* T, double* var, void* ws, int64_t ws_bytes, int B, int C, int K,
+                         uvit_stream stream);
+/* The probit link: out[b, k] = (float)((double) logits[b, k] / sqrt(1 + factor var[b, k])), rounded once; ld, ld_out >= K; out may
+ * alias logits; factor >= 0 and finite, factor = 0 returns the logits bit for bit (pi / 8 is the literature's value).  A NaN or
+ * negative var gives NaN in that entry alone.  lap_var (B) fp32, nullable: var[b, argmax_k logits[b, k]], the arg-max over the
+ * unscaled logits with the lowest index on ties (NaN logits never win; index 0 when all are NaN).  One wave per row. */
+int uvit_op_lap_probit(const float* logits, int64_t ld, const double* var, double factor, float* out, int64_t ld_out, float* lap_var,
+                       int B, int K, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

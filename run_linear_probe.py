@@ -77,6 +77,18 @@ gets the set of classes whose score does not exceed it: the true class is in the
 prints, per level, `* Conformal <score> alpha <A> qhat <q> coverage <c> size <mean> empty <e> singleton <s> SSCV <v> worst-class <w>
 on <n> calibration images`, and log.txt gains `test_cp_alpha`, `test_cp_qhat`, `test_cp_coverage`, `test_cp_size`, `test_cp_empty`,
 `test_cp_singleton`, `test_cp_sscv`, `test_cp_worst_class` (lists in --cp_alpha order) and `test_cp_n_cal`.
+
+`--laplace` (the reference's flag; exclusive with --gp_layer, --het_layer and --ensembles) gives a trained linear head an epistemic
+uncertainty after the fact (uncertainty-vit_amd/lap_probe.py): a last-layer K-FAC Laplace approximation whose two Kronecker factors
+are accumulated on the device over `--lap_data_path DIR`, a labelled image folder read with the evaluation pipeline (required with
+--eval unless `--lap_state FILE` loads a saved fit).  `--lap_prior_precision X|marglik` is the prior precision (default 1.0;
+`marglik` takes the arg-max of the marginal likelihood over 97 log-spaced points of [1e-4, 1e8]).  Every evaluation then runs on
+the probit-scaled logits z / sqrt(1 + pi / 8 var), in front of the temperature and the conformal calibration, which are fitted
+after the Laplace fit; `--detection` gains the column `lap_var`.  Before `* Acc@1` the run prints
+`* Laplace prior precision <tau> (<given|marglik[, grid edge]>) log-marglik <v> NLL <nll / n> on <n> images` and
+`* Laplace variance mean <v>`; log.txt gains `test_lap_prior_precision`, `test_lap_log_marglik`, `test_lap_var_mean`; with
+--output_dir the fit is saved as `laplace.pth`.  Without --eval the head trains as a linear probe and, with --lap_data_path, every
+epoch's evaluation uses the fit of that epoch's head.
 """
 import argparse
 import json
@@ -172,6 +184,14 @@ def get_args(argv=None):
     a("--cp_randomized", action="store_true", default=argparse.SUPPRESS,
       help="aps / raps: randomise the last class of a set with a per-image u from a seeded device generator")
     a("--cp_seed", type=int, default=argparse.SUPPRESS, help="seed of --cp_randomized (default 0)")
+    a("--laplace", action="store_true", default=argparse.SUPPRESS,
+      help="post-hoc last-layer K-FAC Laplace approximation of the linear head (the reference's flag): probit-scaled logits, lap_var")
+    a("--lap_data_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
+      help="labelled image folder (the evaluation's classes) the Laplace factors are accumulated on, read with the evaluation pipeline")
+    a("--lap_prior_precision", type=str, default=argparse.SUPPRESS, metavar="X|marglik",
+      help="prior precision tau: a positive number (default 1.0) or `marglik`, the arg-max of the marginal likelihood over a grid")
+    a("--lap_state", type=str, default=argparse.SUPPRESS, metavar="FILE",
+      help="with --eval: load a saved Laplace fit (laplace.pth) instead of fitting")
     return p.parse_args(argv)
 
 
@@ -277,6 +297,57 @@ def check_cp_flags(args):
     if (hasattr(args, "cp_lambda") or hasattr(args, "cp_kreg")) and getattr(args, "cp_score", "aps") != "raps":
         raise ValueError("--cp_lambda / --cp_kreg are the penalty of --cp_score raps: give it")
     return True
+
+
+LAP_FLAGS = ("lap_data_path", "lap_prior_precision", "lap_state")
+
+
+def lap_prior_precision(args):
+    """--lap_prior_precision as fit_laplace takes it: "marglik" or a positive number; None when the flag is absent."""
+    v = getattr(args, "lap_prior_precision", None)
+    if v is None or v == "marglik":
+        return v
+    try:
+        tau = float(v)
+    except ValueError:
+        tau = float("nan")
+    if not 0.0 < tau < math.inf:
+        raise ValueError(f"--lap_prior_precision takes a positive number or the word marglik, got {v!r}")
+    return tau
+
+
+def check_lap_flags(args):
+    """Whether the run is a Laplace probe (--laplace).  The --lap_* flags belong to it; it is a linear head, so --gp_layer,
+    --het_layer and --ensembles are refused; an evaluation needs the data to fit on or a saved fit, and not both; a saved fit
+    belongs to a head that no longer trains."""
+    if not getattr(args, "laplace", False):
+        if any(hasattr(args, k) for k in LAP_FLAGS):
+            raise ValueError("--lap_* options belong to the Laplace probe: give --laplace")
+        return False
+    if getattr(args, "gp_layer", False) or getattr(args, "het_layer", False) or getattr(args, "ensembles", False):
+        raise ValueError("--laplace is a post-hoc fit of the linear head: give it without --gp_layer / --het_layer / --ensembles")
+    lap_prior_precision(args)
+    if hasattr(args, "lap_data_path") and hasattr(args, "lap_state"):
+        raise ValueError("--lap_data_path fits the Laplace factors and --lap_state loads them: give one")
+    if args.eval and not (hasattr(args, "lap_data_path") or hasattr(args, "lap_state")):
+        raise ValueError("--eval --laplace needs --lap_data_path DIR (the labelled images to fit on) or --lap_state FILE (a saved fit)")
+    if hasattr(args, "lap_state") and not args.eval:
+        raise ValueError("--lap_state is the fit of a finished head: give --eval")
+    return True
+
+
+def laplace_lines(fit, stats):
+    """The two lines in front of `* Acc@1`, from fit_laplace's result (with its `source`) and the evaluation's stats."""
+    how = fit["source"] + (", grid edge" if fit["on_grid_edge"] else "")
+    return ["* Laplace prior precision {:g} ({}) log-marglik {:.5f} NLL {:.5f} on {} images".format(
+                fit["prior_precision"], how, fit["log_marglik"], fit["nll"] / max(fit["n"], 1), fit["n"]),
+            "* Laplace variance mean {:.6f}".format(stats["lap_var_mean"])]
+
+
+def laplace_log_entries(fit, stats):
+    """What log.txt gains: the prior precision in use, its log marginal likelihood and the mean lap_var of the evaluation."""
+    return {"test_lap_prior_precision": fit["prior_precision"], "test_lap_log_marglik": fit["log_marglik"],
+            "test_lap_var_mean": stats["lap_var_mean"]}
 
 
 def conformal_lines(fit, conformal):
@@ -397,6 +468,7 @@ def main(args):
     detection = check_detection_flags(args)
     ts_mode = check_ts_flags(args)
     conformal = check_cp_flags(args)
+    laplace = check_lap_flags(args)
     gp_layer = getattr(args, "gp_layer", False)
     if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
         raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
@@ -450,6 +522,9 @@ def main(args):
             print("Ensemble of %d heads: %s" % (probe.members, list(ens_heads)))
         else:
             probe = EnsembleProbe(encoder, args.nb_classes, members=ens_member_count(args), **ens_kw)
+    elif laplace:
+        from uncertainty_vit_amd.lap_probe import LaplaceProbe
+        probe = LaplaceProbe(encoder, args.nb_classes, smoothing=args.smoothing)
     else:
         probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
     print("Trainable weights: %s" % [n for n, p in probe.named_parameters() if p.requires_grad])
@@ -472,6 +547,32 @@ def main(args):
         if hasattr(args, "ood_data_path"):
             loader_ood, _ = build_loader(args, encoder, args.ood_data_path, 1, train=False)
             gp_eval["ood_loader"] = DevicePrefetcher(loader_ood, device)
+    lap_fit = None
+
+    def fit_laplace():
+        """Fit on --lap_data_path for the head as it stands; with --output_dir the fit is saved as laplace.pth."""
+        prior = lap_prior_precision(args)
+        loader_lap, _ = build_loader(args, encoder, args.lap_data_path, 1, train=False)
+        fit = probe.fit_laplace(DevicePrefetcher(loader_lap, device), prior_precision=1.0 if prior is None else prior)
+        fit["source"] = "marglik" if prior == "marglik" else "given"
+        if args.output_dir:
+            torch.save({**probe.laplace_state_dict(), "source": fit["source"], "on_grid_edge": fit["on_grid_edge"]},
+                       os.path.join(args.output_dir, "laplace.pth"))
+        return fit
+
+    if laplace and args.eval:
+        if hasattr(args, "lap_state"):
+            saved = torch.load(args.lap_state, map_location="cpu", weights_only=False)
+            lap_fit = probe.load_laplace_state(saved)
+            lap_fit["source"], lap_fit["on_grid_edge"] = saved.get("source", "given"), bool(saved.get("on_grid_edge", False))
+            prior = lap_prior_precision(args)
+            if prior is not None:
+                lap_fit = probe.set_prior_precision(prior)
+                lap_fit["source"] = "marglik" if prior == "marglik" else "given"
+            print("Load Laplace state %s" % args.lap_state)
+        else:
+            lap_fit = fit_laplace()
+        gp_eval["variance"] = True
     ts_fit = None
     if ts_mode == "fit":
         loader_ts, _ = build_loader(args, encoder, args.ts_data_path, 1, train=False)
@@ -498,6 +599,9 @@ def main(args):
         if ts_fit is not None:
             stats["temperature_fit"] = ts_fit
             print(temperature_line(ts_fit))
+        if lap_fit is not None:
+            stats["laplace_fit"] = lap_fit
+            print("\n".join(laplace_lines(lap_fit, stats)))
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
         if gp_layer:
             print(gp_variance_line(stats))
@@ -513,12 +617,13 @@ def main(args):
             stats["conformal_fit"] = cp_fit
             stats["conformal"] = probe.evaluate_conformal(DevicePrefetcher(loader_val, device), **cp_temp, **cp_kw)["conformal"]
             print("\n".join(conformal_lines(cp_fit, stats["conformal"])))
-        if (extra_keys or ensembles or detection or ts_mode or conformal) and args.output_dir:
+        if (extra_keys or ensembles or detection or ts_mode or conformal or laplace) and args.output_dir:
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
                                     **(ens_log_entries(stats) if ensembles else {}),
                                     **(detection_log_entries(stats["detection"]) if detection else {}),
                                     **(temperature_log_entries(stats, ts_fit) if ts_mode else {}),
+                                    **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {}),
                                     **(conformal_log_entries(cp_fit, stats["conformal"]) if conformal else {})}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)
@@ -554,7 +659,11 @@ def main(args):
             log.update(lr=lr)
         for l0, g0 in seen:
             publish(log, l0, g0)
+        if laplace and hasattr(args, "lap_data_path"):
+            lap_fit = fit_laplace()              # the fit of this epoch's head: train_step dropped the one before
         stats = evaluate()
+        if lap_fit is not None:
+            print("\n".join(laplace_lines(lap_fit, stats)))
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f}")
         if gp_layer:
             print(gp_variance_line(stats))
@@ -570,7 +679,8 @@ def main(args):
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({"epoch": epoch, "train_loss": log.loss.global_avg, "train_lr": log.lr.value,
                                     **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
-                                    **(ens_log_entries(stats) if ensembles else {})})
+                                    **(ens_log_entries(stats) if ensembles else {}),
+                                    **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {})})
                         + "\n")
     print("Training time %.0f s" % (time.time() - t0))
     return stats

@@ -52,6 +52,10 @@ pids+=($!)
 # forms a score by one expression in two kernels that must agree bit for bit: no fast-math, no FMA contraction
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c conformal.hip -o obj/conformal.o ) &
 pids+=($!)
+# laplace.hip fixes the order of every double sum (bit-identical runs, bit-symmetric Kronecker factors), screens rows with isfinite
+# and needs the accurate double exp / log of its softmax (the test bounds are derived from them): no fast-math
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c laplace.hip -o obj/laplace.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

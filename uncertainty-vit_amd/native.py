@@ -228,6 +228,12 @@ _PROTOTYPES = {
     "uvit_op_cp_counter_count": (_i64, [_i, _i]),
     "uvit_op_cp_sets": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     "uvit_op_cp_finish": (_i, [_vp, _vp, _i, _i, _vp]),
+    "uvit_op_lap_factors_ws_bytes": (_i64, [_i, _i, _i]),
+    "uvit_op_lap_factors": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "uvit_op_lap_prepare": (_i, [_vp, _vp, _vp, C.c_double, _vp, _i, _i, _vp]),
+    "uvit_op_lap_variance_ws_bytes": (_i64, [_i, _i, _i]),
+    "uvit_op_lap_variance": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "uvit_op_lap_probit": (_i, [_vp, _i64, _vp, C.c_double, _vp, _i64, _vp, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
