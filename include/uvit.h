@@ -770,6 +770,36 @@ int uvit_op_lap_variance(const float* feat, const double* UA, const double* T, d
 int uvit_op_lap_probit(const float* logits, int64_t ld, const double* var, double factor, float* out, int64_t ld_out, float* lap_var,
                        int B, int K, uvit_stream stream);
 
+/* ---- Mahalanobis and relative Mahalanobis out-of-distribution scores of the probe's feature, DESIGN.md section 9.10 ----
+ * f (B, C) is the probe's pooled, normalised feature.  Over the usable rows of a labelled set (every feature finite, the label inside
+ * [0, K)): S = sum f f^T (C, C), class_sum[k] = the sum of the rows of class k (K, C), total_sum (C), class_count (K).  From these the
+ * host forms the class means mu_k, the overall mean mu_0, the tied covariance Sigma = (S - sum_k n_k mu_k mu_k^T) / n and the
+ * background covariance Sigma_0 = S / n - mu_0 mu_0^T, shrinks both (+ rho tr / C I), factors them (L L^T, L_0 L_0^T) and uploads
+ * W = L^-1, W0 = L_0^-1, Wmu[k] = W mu_k and Wmu0 = W0 mu_0.  Then d_k(f) = |W f - Wmu[k]|^2, maha = min_k d_k over the classes with
+ * a row, pred = arg min (the lowest index on ties), d_0 = |W0 f - Wmu0|^2 and rmaha = maha - d_0; larger = more out of distribution.
+ * Limits, argument checks, double arithmetic and the fixed order of every sum are those of the Laplace ops above. */
+/* Workspace of uvit_op_maha_accumulate in bytes: an int32 per row, padded to 16 bytes. */
+int64_t uvit_op_maha_accumulate_ws_bytes(int B, int C, int K);
+/* One batch added in place into S (C, C), class_sum (K, C), total_sum (C), class_count (K) and sums = {rows used, rows skipped}, all
+ * double and zeroed once by the caller.  feat (B, C) fp32, labels (B) int64.  Every element of S is one fma chain over b in ascending
+ * order added to the old value, (i, j) and (j, i) from the same products in the same order: S stays symmetric bit for bit.  Every
+ * element of class_sum and total_sum has one owner that walks b in ascending order (K + 1 rows of workgroups read the B screened
+ * labels each).  A row with a non-finite feature or a label outside [0, K) is left out of everything and counted as skipped. */
+int uvit_op_maha_accumulate(const float* feat, const int64_t* labels, double* S, double* class_sum, double* total_sum, double* class_count,
+                            double* sums, void* ws, int64_t ws_bytes, int B, int C, int K, uvit_stream stream);
+/* Workspace of uvit_op_maha_scores in bytes: W f and W0 f (B, C) double each and the distances (B, K) double. */
+int64_t uvit_op_maha_scores_ws_bytes(int B, int C, int K);
+/* maha (B) fp32, rmaha (B) fp32 and pred (B) int32 of feat (B, C) fp32 from W, W0 (C, C) double, row-major and lower triangular with
+ * exact zeros above the diagonal, Wmu (K, C), Wmu0 (C) and class_count (K) double.  The whitened rows go to ws (16 x 32 output tiles,
+ * every element one fma chain over ascending column index); every d_k is the sum of the squared differences (g_c - Wmu[k, c])^2 in
+ * ascending c, never the expanded form; the minimum skips the classes with class_count <= 0 (none left: NaN, NaN, -1) and takes the
+ * lowest index on ties; the fp32 outputs are rounded once.  dist (B, ld) double, nullable, ld >= K: every d_k, the padding untouched;
+ * NULL gives the same maha, rmaha and pred bits.  A row with a non-finite feature gets NaN, NaN, -1 and NaN in its row of dist.
+ * labels (B) int64 and correct (1) int32, both nullable: *correct += the rows whose pred equals their label (an integer atomic). */
+int uvit_op_maha_scores(const float* feat, const double* W, const double* W0, const double* Wmu, const double* Wmu0,
+                        const double* class_count, float* maha, float* rmaha, int32_t* pred, double* dist, int64_t ld,
+                        const int64_t* labels, int32_t* correct, void* ws, int64_t ws_bytes, int B, int C, int K, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,16 @@ after the Laplace fit; `--detection` gains the column `lap_var`.  Before `* Acc@
 `* Laplace variance mean <v>`; log.txt gains `test_lap_prior_precision`, `test_lap_log_marglik`, `test_lap_var_mean`; with
 --output_dir the fit is saved as `laplace.pth`.  Without --eval the head trains as a linear probe and, with --lap_data_path, every
 epoch's evaluation uses the fit of that epoch's head.
+
+`--maha_data_path DIR` (with --eval; every head, also with --laplace; implies --detection) fits class-conditional Gaussians with one
+tied covariance, and one background Gaussian, on the frozen features of a labelled image folder read with the evaluation pipeline
+(LinearProbe.fit_density), and the detection gains the columns `maha` (the smallest squared Mahalanobis
+distance to a class mean) and `rmaha` (that minus the squared distance to the background Gaussian).  `--maha_shrinkage RHO` (default
+1e-3) is the shrinkage rho of Sigma + rho tr(Sigma) / C I; `--maha_state FILE` loads a saved fit instead (exclusive with
+--maha_data_path; with --maha_shrinkage the saved sums are factorised again).  Before `* Acc@1` the run prints
+`* Mahalanobis fit on <n> images (<skipped> skipped), <K> classes (<e> empty), shrinkage <rho>, log-det <v> background <v0>` and
+`* Mahalanobis Acc@1 <a> mean <m>` (the nearest-class-mean accuracy and the mean `maha` of the evaluation set); log.txt gains
+`test_maha_acc1`, `test_maha_mean`, `test_maha_shrinkage`; with --output_dir the fit is saved as `density.pth`.
 """
 import argparse
 import json
@@ -192,6 +202,13 @@ def get_args(argv=None):
       help="prior precision tau: a positive number (default 1.0) or `marglik`, the arg-max of the marginal likelihood over a grid")
     a("--lap_state", type=str, default=argparse.SUPPRESS, metavar="FILE",
       help="with --eval: load a saved Laplace fit (laplace.pth) instead of fitting")
+    a("--maha_data_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
+      help="with --eval: labelled image folder (the evaluation's classes) on whose features the Mahalanobis density is fitted; adds the "
+           "detection columns maha and rmaha, implies --detection")
+    a("--maha_shrinkage", type=float, default=argparse.SUPPRESS, metavar="RHO",
+      help="shrinkage of the two covariances, Sigma + RHO tr(Sigma) / C I (default 1e-3)")
+    a("--maha_state", type=str, default=argparse.SUPPRESS, metavar="FILE",
+      help="with --eval: load a saved Mahalanobis fit (density.pth) instead of fitting (exclusive with --maha_data_path)")
     return p.parse_args(argv)
 
 
@@ -350,6 +367,39 @@ def laplace_log_entries(fit, stats):
             "test_lap_var_mean": stats["lap_var_mean"]}
 
 
+MAHA_FLAGS = ("maha_data_path", "maha_shrinkage", "maha_state")
+
+
+def check_maha_flags(args):
+    """How the run gets its Mahalanobis density: "fit" (--maha_data_path), "state" (--maha_state) or None.  The three --maha_* flags
+    belong to --eval, the two sources are exclusive, --maha_shrinkage needs one of them and is positive and finite."""
+    if not any(hasattr(args, k) for k in MAHA_FLAGS):
+        return None
+    if not args.eval:
+        raise ValueError("--maha_data_path / --maha_shrinkage / --maha_state belong to an evaluation: give --eval")
+    if hasattr(args, "maha_data_path") and hasattr(args, "maha_state"):
+        raise ValueError("--maha_data_path fits the Mahalanobis density and --maha_state loads it: give one")
+    if hasattr(args, "maha_shrinkage") and not 0.0 < args.maha_shrinkage < math.inf:
+        raise ValueError(f"--maha_shrinkage must be positive and finite, got {args.maha_shrinkage}")
+    if hasattr(args, "maha_data_path"):
+        return "fit"
+    if hasattr(args, "maha_state"):
+        return "state"
+    raise ValueError("--maha_shrinkage steers the fit of --maha_data_path DIR or --maha_state FILE: give one")
+
+
+def maha_lines(fit, stats):
+    """The two lines in front of `* Acc@1`, from fit_density's result and the evaluation's stats."""
+    return ["* Mahalanobis fit on {n} images ({skipped} skipped), {classes} classes ({empty_classes} empty), shrinkage {shrinkage:g}, "
+            "log-det {logdet:.5f} background {logdet0:.5f}".format(**fit),
+            "* Mahalanobis Acc@1 {maha_acc1:.3f} mean {maha_mean:.5f}".format(**stats)]
+
+
+def maha_log_entries(fit, stats):
+    """What log.txt gains: the nearest-class-mean accuracy, the mean maha of the evaluation set and the shrinkage in use."""
+    return {"test_maha_acc1": stats["maha_acc1"], "test_maha_mean": stats["maha_mean"], "test_maha_shrinkage": fit["shrinkage"]}
+
+
 def conformal_lines(fit, conformal):
     """One line per alpha, from fit_conformal's result and evaluate_conformal's stats["conformal"]."""
     return ["* Conformal {} alpha {:g} qhat {:.5f} coverage {coverage:.5f} size {size:.3f} empty {empty:.5f} singleton {singleton:.5f} "
@@ -469,6 +519,8 @@ def main(args):
     ts_mode = check_ts_flags(args)
     conformal = check_cp_flags(args)
     laplace = check_lap_flags(args)
+    maha = check_maha_flags(args)
+    detection = detection or maha is not None
     gp_layer = getattr(args, "gp_layer", False)
     if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
         raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
@@ -573,6 +625,18 @@ def main(args):
         else:
             lap_fit = fit_laplace()
         gp_eval["variance"] = True
+    maha_fit = None
+    if maha == "fit":
+        loader_maha, _ = build_loader(args, encoder, args.maha_data_path, 1, train=False)
+        maha_fit = probe.fit_density(DevicePrefetcher(loader_maha, device), shrinkage=getattr(args, "maha_shrinkage", 1e-3))
+    elif maha == "state":
+        saved = torch.load(args.maha_state, map_location="cpu", weights_only=False)
+        if hasattr(args, "maha_shrinkage"):
+            saved = {**saved, "shrinkage": args.maha_shrinkage}
+        maha_fit = probe.load_density_state(saved)
+        print("Load Mahalanobis state %s" % args.maha_state)
+    if maha == "fit" and args.output_dir:
+        torch.save(probe.density_state_dict(), os.path.join(args.output_dir, "density.pth"))
     ts_fit = None
     if ts_mode == "fit":
         loader_ts, _ = build_loader(args, encoder, args.ts_data_path, 1, train=False)
@@ -602,6 +666,9 @@ def main(args):
         if lap_fit is not None:
             stats["laplace_fit"] = lap_fit
             print("\n".join(laplace_lines(lap_fit, stats)))
+        if maha_fit is not None:
+            stats["density_fit"] = maha_fit
+            print("\n".join(maha_lines(maha_fit, stats)))
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
         if gp_layer:
             print(gp_variance_line(stats))
@@ -624,6 +691,7 @@ def main(args):
                                     **(detection_log_entries(stats["detection"]) if detection else {}),
                                     **(temperature_log_entries(stats, ts_fit) if ts_mode else {}),
                                     **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {}),
+                                    **(maha_log_entries(maha_fit, stats) if maha_fit is not None else {}),
                                     **(conformal_log_entries(cp_fit, stats["conformal"]) if conformal else {})}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)

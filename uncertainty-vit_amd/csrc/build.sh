@@ -56,6 +56,10 @@ pids+=($!)
 # and needs the accurate double exp / log of its softmax (the test bounds are derived from them): no fast-math
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c laplace.hip -o obj/laplace.o ) &
 pids+=($!)
+# maha.hip fixes the order of every double sum (bit-identical runs, a bit-symmetric scatter matrix) and screens rows with isfinite:
+# no fast-math
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c maha.hip -o obj/maha.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).

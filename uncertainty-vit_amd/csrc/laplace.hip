@@ -16,6 +16,7 @@
 
 #include "../../include/uvit.h"
 #include "common.h"
+#include "gram.h"
 
 #define LAP_MAX_B 65535
 #define LAP_MAX_C 2048
@@ -72,8 +73,7 @@ void lap_softmax_kernel(const float* __restrict__ logits, int64_t ld, const int6
 // MODE 1: X = p (zero in the rows left out), N = K, out = G_sum:                             G_kl += delta_kl sum_b p_bk - S_kl
 // S_ij = one fma chain over b in ascending order.  (i, j) and (j, i) are formed from the same products (a * b == b * a) in the same
 // order and combined with the old value by the same expression, so a symmetric matrix stays symmetric bit for bit.
-#define FT 64                // output tile edge: 256 threads with a 4 x 4 micro-tile each
-#define FK 16                // batch rows per LDS tile
+#define FT GRAM_T            // output tile edge: 256 threads with a 4 x 4 micro-tile each (gram.h)
 template <int MODE>
 __device__ __forceinline__ double lap_x(const float* __restrict__ feat, const double* __restrict__ p, const int* __restrict__ used,
                                         int b, int col, int B, int C, int N) {
@@ -87,35 +87,10 @@ template <int MODE>
 __global__ __launch_bounds__(256)
 void lap_gram_kernel(const float* __restrict__ feat, const double* __restrict__ p, const int* __restrict__ used, double* __restrict__ out,
                      int B, int C, int N) {
-    __shared__ __attribute__((aligned(16))) double Is[FK][FT + 2], Js[FK][FT + 2];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int j0 = blockIdx.x * FT, i0 = blockIdx.y * FT;
-    const int fr = tid >> 4, fc = (tid & 15) * 4;         // staging: batch row, first of four columns
     double acc[4][4] = {}, si[4] = {};
-    for (int b0 = 0; b0 < B; b0 += FK) {
-        double vi[4], vj[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            vi[q] = lap_x<MODE>(feat, p, used, b0 + fr, i0 + fc + q, B, C, N);
-            vj[q] = lap_x<MODE>(feat, p, used, b0 + fr, j0 + fc + q, B, C, N);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { Is[fr][fc + q] = vi[q]; Js[fr][fc + q] = vj[q]; }
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < FK; ++b) {                    // rows past B hold zeros: fma(0, 0, acc) = acc
-            const double2 i01 = *(const double2*)&Is[b][ty * 4], i23 = *(const double2*)&Is[b][ty * 4 + 2];
-            const double2 j01 = *(const double2*)&Js[b][tx * 4], j23 = *(const double2*)&Js[b][tx * 4 + 2];
-            const double ii[4] = {i01.x, i01.y, i23.x, i23.y}, jj[4] = {j01.x, j01.y, j23.x, j23.y};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (MODE == 1) si[i] += ii[i];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fma(ii[i], jj[j], acc[i][j]);
-            }
-        }
-    }
+    gram_tile<MODE == 1>([&](int b, int col) { return lap_x<MODE>(feat, p, used, b, col, B, C, N); }, B, i0, j0, acc, si);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = i0 + ty * 4 + i;

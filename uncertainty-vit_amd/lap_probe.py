@@ -90,7 +90,10 @@ class LaplaceProbe(LinearProbe):
         if state is not None:
             return self.load_laplace_state(state)
         self._lap = None
-        self.DETECT_COLUMNS = LinearProbe.DETECT_COLUMNS       # unfitted: the columns, and so the launches, of a LinearProbe
+        self._det_refresh()                                    # unfitted: the columns, and so the launches, of a LinearProbe
+
+    def _det_class_columns(self):
+        return LinearProbe.DETECT_COLUMNS if self._lap is None else type(self).DETECT_COLUMNS
 
     @property
     def laplace(self):
@@ -152,7 +155,7 @@ class LaplaceProbe(LinearProbe):
                      "head_sha256": self._head_hash(head), "UA": up(UA), "UG": up(UG), "lam_a_dev": up(lam_a), "lam_g_dev": up(lam_g),
                      "T": torch.zeros(D, K, dtype=F64, device=dev),
                      "info": {"n": int(n), "n_skipped": int(skipped), "nll": nll}}
-        self.__dict__.pop("DETECT_COLUMNS", None)                       # fitted: the class's columns, lap_var among them
+        self._det_refresh()                                             # fitted: the class's columns, lap_var among them
         return self.set_prior_precision(prior)
 
     def set_prior_precision(self, prior_precision):

@@ -32,6 +32,9 @@ TS_T_MIN, TS_T_MAX, TS_TOL, TS_MAX_ITER = 0.01, 100.0, 1e-7, 16
 TS_STATUS = ("converged", "clamped at T_max", "clamped at T_min", "iteration limit")     # status 0 .. 3 of uvit_op_ts_fit
 CP_MAX_N, CP_MAX_K, CP_MAX_A, CP_TABLE = 1 << 20, 4096, 8, 16      # csrc/conformal.hip: rows, classes, levels, doubles per table row
 CP_KINDS = {"lac": 0, "aps": 1, "raps": 2}                         # the `kind` of uvit_op_cp_scores / uvit_op_cp_sets
+MAHA_MAX_C, MAHA_MAX_K = 2048, 4096          # csrc/maha.hip: C % 4 == 0, 4 <= C <= 2048, 2 <= K <= 4096, 1 <= B <= 65535
+MAHA_COLUMNS = ("maha", "rmaha")             # the detection columns a fitted density appends to the class's
+MAHA_SHRINKAGE = 1e-3                        # an option's default, not a measured optimum
 
 
 def _timm_trunc_normal_(t, std):
@@ -73,6 +76,8 @@ class LinearProbe(nn.Module):
         self._ts, self._ts_table, self._ts_on, self._ts_ws = None, None, None, None
         # conformal sets: the fitted or set state (settings and the device table of uvit_op_cp_quantile) and the quantile's workspace
         self._cp, self._cp_ws = None, None
+        # feature density (Mahalanobis scores): the fitted or loaded state and the largest batch its buffers hold
+        self._maha, self._maha_batch, self._maha_eval = None, 0, None
         self._setup_head(init_scale)
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
 
@@ -109,6 +114,10 @@ class LinearProbe(nn.Module):
         self._grad_arena, self.exp_avg, self.exp_avg_sq = (fn(t).contiguous() for t in (self._grad_arena, self.exp_avg, self.exp_avg_sq))
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
         self._det_ws = self._ts_table = self._ts_ws = self._cp = self._cp_ws = None
+        self._maha_batch = 0
+        if self._maha is not None:                   # the density moves with the module and stays float64; its sums stay on the host
+            for key in ("W", "W0", "Wmu", "Wmu0", "count_dev"):
+                self._maha[key] = self._maha[key].to(new.device)
         self._rebind()
         return self
 
@@ -332,6 +341,8 @@ class LinearProbe(nn.Module):
                     images = images[0]
                 B = self._features(images)
                 self._det_reserve(B)
+                if self._maha_eval is not None:
+                    self._maha_columns(B, None)
                 self._logits_into(B)
                 self._ts_apply(B)
                 self._det_rows(B, None)
@@ -355,6 +366,198 @@ class LinearProbe(nn.Module):
             out["ood"] = {c: dict(zip(DETECT_KEYS[:3], r[:3])) for c, r in zip(cols, rows)}
             out["n_ood"] = n_ood
         return out
+
+    # ---- feature density: Mahalanobis and relative Mahalanobis scores (csrc/maha.hip) ----
+    def _det_class_columns(self):
+        """The columns of the head itself (LaplaceProbe: a LinearProbe's while it has no fit)."""
+        return type(self).DETECT_COLUMNS
+
+    def _det_refresh(self):
+        """The instance's DETECT_COLUMNS: the head's own columns, followed by MAHA_COLUMNS while a density is set.  An instance
+        attribute only where that differs from the class's."""
+        cols = tuple(self._det_class_columns()) + (MAHA_COLUMNS if self._maha is not None else ())
+        if cols == type(self).DETECT_COLUMNS:
+            self.__dict__.pop("DETECT_COLUMNS", None)
+        else:
+            self.DETECT_COLUMNS = cols
+
+    @staticmethod
+    def _maha_shrinkage(shrinkage):
+        rho = float(shrinkage)
+        if not 0.0 < rho < math.inf:
+            raise native.UvitError(f"the shrinkage must be positive and finite, got {shrinkage}")
+        return rho
+
+    def _maha_install(self, S, class_sum, total_sum, class_count, sums, shrinkage):
+        """Host float64 sums -> the two shrunk covariances, their Cholesky factors, the whitened means and the uploads."""
+        rho = self._maha_shrinkage(shrinkage)
+        K, Cd, F64 = self.num_classes, self.embed_dim, torch.float64
+        if Cd < 4 or Cd % 4 or Cd > MAHA_MAX_C or not 2 <= K <= MAHA_MAX_K:
+            raise native.UvitError(f"the Mahalanobis ops take an embed dim that is a multiple of 4 in [4, {MAHA_MAX_C}] and 2 .. {MAHA_MAX_K} "
+                                   f"classes, got {Cd} and {K}")
+        S, class_sum, total_sum, class_count, sums = (torch.as_tensor(t, dtype=F64).cpu().contiguous()
+                                                      for t in (S, class_sum, total_sum, class_count, sums))
+        if (tuple(S.shape), tuple(class_sum.shape), tuple(total_sum.shape), tuple(class_count.shape), tuple(sums.shape)) != \
+                ((Cd, Cd), (K, Cd), (Cd,), (K,), (2,)):
+            raise native.UvitError(f"the density state belongs to another probe: its sums must have shapes ({Cd}, {Cd}), ({K}, {Cd}), "
+                                   f"({Cd},), ({K},) and (2,)")
+        n, skipped = float(sums[0]), float(sums[1])
+        if not n >= 2:
+            raise native.UvitError("the density fit needs at least two usable rows (finite features, a label inside [0, K))")
+        mu = class_sum / class_count.clamp_min(1.0)[:, None]                 # an empty class: a zero row, never chosen
+        mu0 = total_sum / n
+        sigma = (S - class_sum.T @ mu) / n                                   # sum_k n_k mu_k mu_k^T = class_sum^T mu
+        sigma = 0.5 * (sigma + sigma.T)
+        sigma0 = S / n - torch.outer(mu0, mu0)
+        eye = torch.eye(Cd, dtype=F64)
+        fac = []
+        for m in (sigma, sigma0):
+            reg = m + rho * (float(torch.trace(m)) / Cd) * eye
+            L, info = torch.linalg.cholesky_ex(reg)
+            if int(info) != 0 or not bool(torch.isfinite(L).all()):
+                raise native.UvitError("the density fit failed: a shrunk covariance is not positive definite (constant or non-finite "
+                                       "features?); try a larger shrinkage")
+            fac.append((torch.linalg.solve_triangular(L, eye, upper=False).tril(), 2.0 * float(torch.log(torch.diagonal(L)).sum())))
+        (W, logdet), (W0, logdet0) = fac
+        dev = self._arena.device
+        up = lambda t: t.contiguous().to(dev)                                # noqa: E731
+        self._maha = {"S": S, "class_sum": class_sum, "total_sum": total_sum, "class_count": class_count, "sums": sums,
+                      "W": up(W), "W0": up(W0), "Wmu": up(mu @ W.T), "Wmu0": up(W0 @ mu0), "count_dev": up(class_count),
+                      "info": {"n": int(n), "skipped": int(skipped), "classes": K, "empty_classes": int((class_count <= 0).sum()),
+                               "shrinkage": rho, "logdet": logdet, "logdet0": logdet0}}
+        self._det_refresh()
+        return dict(self._maha["info"])
+
+    def fit_density(self, loader, shrinkage=MAHA_SHRINKAGE):
+        """Class-conditional Gaussians with one tied covariance, and one background Gaussian, on the probe's features: one pass over a
+        labelled loader (items as evaluate()'s) of the encoder forward, pool + norm and uvit_op_maha_accumulate into device
+        accumulators, one read of the sums, then the host's two covariances, their shrinkage Sigma + shrinkage tr(Sigma) / C I and
+        Cholesky factors in float64 (torch.linalg on the CPU) and the upload of W = L^-1, W0 = L0^-1 and the whitened means.  The head
+        takes no part: any trained or untrained head gets the columns.  Returns {n, skipped (rows with a non-finite feature or a label
+        outside [0, K)), classes, empty_classes, shrinkage, logdet, logdet0 (log-determinants of the two shrunk covariances)}."""
+        rho = self._maha_shrinkage(shrinkage)
+        K, Cd, acc, ws = self.num_classes, self.embed_dim, None, None
+        o_cs, o_ts, o_cc, o_sums = Cd * Cd, Cd * Cd + K * Cd, Cd * Cd + K * Cd + Cd, Cd * Cd + K * Cd + Cd + K
+        for item in loader:
+            images, labels = item
+            if isinstance(images, (tuple, list)):
+                images = images[0]
+            B = self._features(images)
+            if torch.is_tensor(labels) and not labels.is_cuda:
+                labels = labels.to(images.device, non_blocking=True)
+            labels = self._labels(labels, B)
+            if acc is None:
+                acc = torch.zeros(o_sums + 2, dtype=torch.float64, device=images.device)     # S | class sums | total | counts | sums
+            need = lib().uvit_op_maha_accumulate_ws_bytes(B, Cd, K)
+            if need < 0:
+                check(int(need), "uvit_op_maha_accumulate_ws_bytes")
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(int(need), dtype=torch.uint8, device=images.device)
+            at = lambda off: C.c_void_p(acc.data_ptr() + 8 * off)                             # noqa: E731
+            check(lib().uvit_op_maha_accumulate(ptr(self._feat), ptr(labels), at(0), at(o_cs), at(o_ts), at(o_cc), at(o_sums), ptr(ws),
+                                                ws.numel(), B, Cd, K, cur_stream()), "uvit_op_maha_accumulate")
+        if acc is None:
+            raise native.UvitError("the density fit needs at least two labelled samples")
+        host = acc.cpu()                                                                      # the one read
+        return self._maha_install(host[:o_cs].view(Cd, Cd), host[o_cs:o_ts].view(K, Cd), host[o_ts:o_cc], host[o_cc:o_sums],
+                                  host[o_sums:o_sums + 2], rho)
+
+    def set_density(self, state):
+        """None forgets the density (the detection columns are the class's again); a dict of density_state_dict() is loaded."""
+        if state is not None:
+            return self.load_density_state(state)
+        self._maha = None
+        self._det_refresh()
+
+    @property
+    def density(self):
+        """{n, skipped, classes, empty_classes, shrinkage, logdet, logdet0} of the density in use, None when there is none."""
+        return dict(self._maha["info"]) if self._maha is not None else None
+
+    def set_density_shrinkage(self, shrinkage):
+        """Another shrinkage for the density in use: the host factorises again from the kept sums, the data are not read."""
+        st = self._maha
+        if st is None:
+            raise native.UvitError("set_density_shrinkage needs fit_density() or load_density_state() first")
+        return self._maha_install(st["S"], st["class_sum"], st["total_sum"], st["class_count"], st["sums"], shrinkage)
+
+    def density_state_dict(self):
+        """What a density is made of, on the host: the float64 sums S, class_sum, total_sum, class_count, sums = {rows used, rows
+        skipped} and the shrinkage.  Not part of state_dict(): neither a parameter nor a buffer."""
+        st = self._maha
+        if st is None:
+            raise native.UvitError("density_state_dict needs fit_density() or load_density_state() first")
+        return {**{k: st[k].clone() for k in ("S", "class_sum", "total_sum", "class_count", "sums")}, "shrinkage": st["info"]["shrinkage"]}
+
+    def load_density_state(self, sd):
+        """Install a saved density (density_state_dict()); one of another embed dim or class count is refused."""
+        keys = ("S", "class_sum", "total_sum", "class_count", "sums", "shrinkage")
+        if not (isinstance(sd, dict) and set(keys) <= set(sd)):
+            raise native.UvitError("load_density_state takes a dict of density_state_dict()")
+        return self._maha_install(*(sd[k] for k in keys))
+
+    def _maha_buffers_for(self, B):
+        if B > self._maha_batch:
+            dev = self._arena.device
+            ws = lib().uvit_op_maha_scores_ws_bytes(B, self.embed_dim, self.num_classes)
+            if ws < 0:
+                check(int(ws), "uvit_op_maha_scores_ws_bytes")
+            self._maha_ws = torch.empty(int(ws), dtype=torch.uint8, device=dev)
+            self._maha_col, self._rmaha_col = (torch.zeros(B, dtype=torch.float32, device=dev) for _ in range(2))
+            self._maha_pred = torch.zeros(B, dtype=torch.int32, device=dev)
+            self._maha_batch = B
+        if self._maha_ws.device != self._maha["W"].device:
+            raise native.UvitError("the density and the probe are on different devices")
+
+    def _maha_into(self, feat, B, dist=None, labels=None, correct=None):
+        """uvit_op_maha_scores of feat[:B] on the current stream into self._maha_col, self._rmaha_col and self._maha_pred."""
+        st = self._maha
+        if st is None:
+            raise native.UvitError("the Mahalanobis scores need fit_density() or load_density_state() first")
+        if self._arena.device.type != "cuda":
+            raise native.UvitError("the Mahalanobis scores run as HIP kernels: move the encoder and the probe to a GPU (no CPU fallback)")
+        self._maha_buffers_for(B)
+        K = self.num_classes
+        check(lib().uvit_op_maha_scores(ptr(feat), ptr(st["W"]), ptr(st["W0"]), ptr(st["Wmu"]), ptr(st["Wmu0"]), ptr(st["count_dev"]),
+                                        ptr(self._maha_col), ptr(self._rmaha_col), ptr(self._maha_pred), ptr(dist), K, ptr(labels),
+                                        ptr(correct), ptr(self._maha_ws), self._maha_ws.numel(), B, self.embed_dim, K, cur_stream()),
+              "uvit_op_maha_scores")
+
+    def _maha_result(self, feat, B, distances):
+        dist = torch.zeros(B, self.num_classes, dtype=torch.float64, device=feat.device) if distances else None
+        self._maha_into(feat, B, dist)
+        out = {"maha": self._maha_col[:B].clone(), "rmaha": self._rmaha_col[:B].clone(), "pred": self._maha_pred[:B].clone()}
+        if distances:
+            out["dist"] = dist
+        return out
+
+    def feature_scores(self, images, distances=False):
+        """{"maha", "rmaha" (B) fp32, "pred" (B) int32} of the images' features against the density in use, device tensors; with
+        `distances`, also "dist" (B, K) float64, the squared distance to every class mean.  maha = the smallest squared Mahalanobis
+        distance to a class mean under the tied covariance, pred = that class (the nearest class mean), rmaha = maha minus the squared
+        distance to the background Gaussian; larger = more out of distribution.  A row with a non-finite feature: NaN, NaN, -1."""
+        if self._maha is None:
+            raise native.UvitError("feature_scores needs fit_density() or load_density_state() first")
+        B = self._features(images)
+        return self._maha_result(self._feat, B, distances)
+
+    def density_batch(self, feat, distances=False):
+        """feature_scores() of caller-supplied GPU features (B, C) fp32; nothing synchronises with the host."""
+        if not torch.is_tensor(feat) or not feat.is_cuda:
+            raise native.UvitError("feat must be a GPU tensor: the HIP path has no CPU fallback")
+        if feat.dtype != torch.float32 or feat.ndim != 2 or feat.shape[1] != self.embed_dim or not feat.is_contiguous() or not feat.shape[0]:
+            raise native.UvitError(f"feat must be a contiguous float32 tensor of shape (B, {self.embed_dim})")
+        return self._maha_result(feat, feat.shape[0], distances)
+
+    def _maha_columns(self, B, labels):
+        """Inside evaluate(detection=True) with a density: the two columns of self._feat[:B] into the store (behind _det_reserve, in
+        front of _det_rows).  The evaluation set's rows (labels given) are also counted against their labels and kept for the mean."""
+        ev = self._maha_eval
+        self._maha_into(self._feat, B, None, labels, ev["correct"] if labels is not None else None)
+        self._det_column("maha", self._maha_col, B)
+        self._det_column("rmaha", self._rmaha_col, B)
+        if labels is not None:
+            ev["slabs"].append(self._maha_col[:B].clone())
 
     # ---- post-hoc temperature scaling (csrc/tscale.hip, DESIGN.md section 9.7) ----
     def _ts_fit(self, logits, ld, labels, N, t_min, t_max, tol, max_iter):
@@ -702,6 +905,9 @@ class LinearProbe(nn.Module):
         forward and columns behind the evaluation set, take no part in loss, accuracy, calibration or any mean, and a second call
         with positive = OOD image adds "ood": {column: {AUROC, AUPR, FPR95}} and "n_ood".  The two small tables are read with the
         losses.  Without the two arguments nothing else is launched or returned.
+        While a density is set (fit_density, load_density_state), detection also stores the columns `maha` and `rmaha` of every batch's
+        features, the OOD images' included, behind the head's own columns, and stats gains "maha_mean" (the mean of `maha` over the
+        evaluation rows that are not NaN) and "maha_acc1" (the nearest-class-mean accuracy in percent, counted on the device).
         `temperature`: None launches and returns exactly the above.  True applies the fitted or set post-hoc temperature
         (fit_temperature, set_temperature; an error when there is none), a number applies that T: uvit_op_ts_scale then runs in place
         on the logits directly behind every _logits_into of the evaluation, the OOD images included, with 1 / T read from a device
@@ -712,13 +918,14 @@ class LinearProbe(nn.Module):
         detection = bool(detection) or ood_loader is not None
         self._ts_on, ts_value = self._ts_begin(temperature)
         self._det = {"scores": None, "flags": None, "cap": 0, "n": 0} if detection else None
+        self._maha_eval = {"correct": None, "slabs": []} if detection and self._maha is not None else None
         try:
             stats = self._evaluate(loader, calibration, ood_loader)
             if ts_value is not None:
                 stats["temperature"] = ts_value
             return stats
         finally:
-            self._det, self._in_ood, self._ts_on = None, False, None
+            self._det, self._in_ood, self._ts_on, self._maha_eval = None, False, None, None
 
     def _evaluate(self, loader, calibration, ood_loader):
         detection = self._det is not None
@@ -738,6 +945,10 @@ class LinearProbe(nn.Module):
                 slab = torch.zeros(256, dtype=torch.float32, device=images.device)
             if detection:
                 self._det_reserve(B)
+                if self._maha_eval is not None:
+                    if self._maha_eval["correct"] is None:
+                        self._maha_eval["correct"] = torch.zeros(1, dtype=torch.int32, device=images.device)
+                    self._maha_columns(B, labels)
             self._logits_into(B)
             self._ts_apply(B)
             slot = C.c_void_p(slab.data_ptr() + 4 * (len(losses) % 256))
@@ -761,6 +972,8 @@ class LinearProbe(nn.Module):
                 empty.update({k: float("nan") for k in ("ECE", "TACE", "NLL", "AUROC", "AUROC_zero_absent")})
             if detection:
                 empty["detection"] = self._det_stats(mis, ood, 0, 0, n_ood, ood_loader is not None)
+            if self._maha_eval is not None:
+                empty.update(maha_mean=float("nan"), maha_acc1=float("nan"))
             return empty
         slabs = {id(s): s for s, _ in losses}
         host = {k: v.cpu() for k, v in slabs.items()}                       # the one read
@@ -778,6 +991,10 @@ class LinearProbe(nn.Module):
             stats["AUROC_zero_absent"] = sum(r[3] / self.num_classes * b for r, b in zip(rows, sizes)) / n
         if detection:
             stats["detection"] = self._det_stats(mis, ood, n, n - c1, n_ood, ood_loader is not None)
+        if self._maha_eval is not None:                                     # read with the counters, after the last batch
+            vals = [v for v in torch.cat(self._maha_eval["slabs"]).cpu().tolist() if not math.isnan(v)]
+            stats["maha_mean"] = math.fsum(vals) / len(vals) if vals else float("nan")
+            stats["maha_acc1"] = 100.0 * int(self._maha_eval["correct"].cpu()) / n
         return stats
 
     # ---- stability under perturbation sequences ----
