@@ -800,6 +800,39 @@ int uvit_op_maha_scores(const float* feat, const double* W, const double* W0, co
                         const double* class_count, float* maha, float* rmaha, int32_t* pred, double* dist, int64_t ld,
                         const int64_t* labels, int32_t* correct, void* ws, int64_t ws_bytes, int B, int C, int K, uvit_stream stream);
 
+/* ---- k-nearest-neighbour OOD score and k-NN classifier of the probe's feature (csrc/knn.hip) ----
+ * Deep nearest neighbours (Sun et al., ICML 2022): features are scaled to unit length, the score of a test feature is its distance to
+ * the k-th nearest training feature, knn = |q - b_(k)|^2 = 2 - 2 s_k with s the dot product; larger = more out of distribution.  The
+ * same neighbours give the weighted k-NN classifier of DINO / iBOT: votes_c = sum_j exp((s_j - s_1) / T) [label_j == c].
+ * Arguments are checked before anything touches the device, nothing synchronises with the host, a second run gives the same bits. */
+/* feat (B, C) fp32 -> out (B, C) bf16 unit rows, written at the pointer given (bank + row0 * C appends to a bank; 16-byte aligned) and
+ * out_labels (B) int32.  |f|^2 is summed in double; an element is (float)(f_c * (1 / sqrt(|f|^2))) rounded to bf16, nearest even.
+ * labels (B) int64, nullable: a usable row gets its label (0 without labels).  A row with a non-finite element, a zero norm or a label
+ * outside [0, K) becomes a zero row with out_labels = -1.  sums (2) double, nullable: {rows used, rows skipped} added in place.
+ * C % 32 == 0, 32 <= C <= 2048, 1 <= B <= 2^22; K (2 .. 4096) is read with labels only. */
+int uvit_op_knn_rows(const float* feat, const int64_t* labels, void* out, int32_t* out_labels, double* sums, int B, int C, int K,
+                     uvit_stream stream);
+/* Workspace of uvit_op_knn_search in bytes: the slabs' running lists, (B, slabs, k) 64-bit keys; O(B slabs k), never (B, N). */
+int64_t uvit_op_knn_search_ws_bytes(int B, int C, int N, int k, int slabs);
+/* query (B, C) bf16 and query_valid (B) int32 (both from uvit_op_knn_rows; valid = not negative), bank (N, C) bf16, bank_labels (N)
+ * int32 -> sim (B, ld) fp32 and idx (B, ld) int32, ld >= k, the padding untouched: per query row the k bank rows with the largest
+ * dot product among those with bank_labels >= 0, sorted by (similarity descending, index ascending); fewer than k such rows leave
+ * -inf and -1 behind them; an invalid query row gets NaN and -1 throughout.  The products are v_mfma_f32_16x16x32_bf16 with fp32
+ * accumulation, one chain over C in ascending 32-element steps for every output element; -0 is reported as +0.  The bank is split into
+ * `slabs` contiguous row ranges (0: chosen from N, B and the CU count; 1 .. 1024), a workgroup streams one slab for 64 query rows and
+ * keeps a running top-k per row, a second kernel merges.  The order is total (64-bit key: the similarity's bits, then the inverted
+ * index), so the result has the same bits for every `slabs` and on every run.  1 <= B <= 65535, 1 <= k <= 256, 1 <= N <= 2^22. */
+int uvit_op_knn_search(const void* query, const int32_t* query_valid, const void* bank, const int32_t* bank_labels, float* sim,
+                       int32_t* idx, int64_t ld, void* ws, int64_t ws_bytes, int B, int C, int N, int k, int slabs, uvit_stream stream);
+/* From sim, idx (B, ld) of uvit_op_knn_search and bank_labels (N): knn (B) fp32 = fmaf(-2, s_k, 2); pred (B) int32 = the arg max over
+ * classes of votes_c (double, j ascending, the lowest class on ties; a neighbour whose label is outside [0, K) does not vote);
+ * votes (B, ldv) double, nullable, ldv >= K (NULL gives the same knn and pred bits).  A row whose k-th entry is missing or NaN gets
+ * knn = NaN, pred = -1 (and NaN votes).  labels (B) int64 and correct (1) int32, both nullable: *correct += the rows whose pred equals
+ * their label (an integer atomic).  2 <= K <= 4096, temperature positive and finite, B, k, N as above. */
+int uvit_op_knn_scores(const float* sim, const int32_t* idx, int64_t ld, const int32_t* bank_labels, int N, float* knn, int32_t* pred,
+                       double* votes, int64_t ldv, const int64_t* labels, int32_t* correct, int B, int k, int K, double temperature,
+                       uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

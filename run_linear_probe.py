@@ -99,6 +99,16 @@ distance to a class mean) and `rmaha` (that minus the squared distance to the ba
 `* Mahalanobis fit on <n> images (<skipped> skipped), <K> classes (<e> empty), shrinkage <rho>, log-det <v> background <v0>` and
 `* Mahalanobis Acc@1 <a> mean <m>` (the nearest-class-mean accuracy and the mean `maha` of the evaluation set); log.txt gains
 `test_maha_acc1`, `test_maha_mean`, `test_maha_shrinkage`; with --output_dir the fit is saved as `density.pth`.
+
+`--knn_data_path DIR` (with --eval; every head, also with --laplace and --maha_*; implies --detection) stores the unit-length bf16
+features of a labelled image folder, read with the evaluation pipeline, as a neighbour bank (LinearProbe.fit_neighbours, DESIGN.md
+section 9.11).  The detection gains the column `knn` = 2 - 2 s_k, the squared distance to the k-th nearest bank feature (deep nearest
+neighbours, Sun et al. 2022), and the run reports the weighted k-NN accuracy of DINO / iBOT, which trains nothing.  `--knn_k K`
+(default 20, at most 256) and `--knn_temperature T` (default 0.07) set the neighbour count and the vote's temperature;
+`--knn_state FILE` loads a saved bank instead (exclusive with --knn_data_path; --knn_k / --knn_temperature then override the saved
+ones).  Before `* Acc@1` the run prints `* kNN bank of <n> images (<skipped> skipped), <K> classes, k <k>, temperature <T>` and
+`* kNN Acc@1 <a> mean <m>`; log.txt gains `test_knn_acc1`, `test_knn_mean`, `test_knn_k`; with --output_dir the bank is saved as
+`neighbours.pth`.
 """
 import argparse
 import json
@@ -209,6 +219,14 @@ def get_args(argv=None):
       help="shrinkage of the two covariances, Sigma + RHO tr(Sigma) / C I (default 1e-3)")
     a("--maha_state", type=str, default=argparse.SUPPRESS, metavar="FILE",
       help="with --eval: load a saved Mahalanobis fit (density.pth) instead of fitting (exclusive with --maha_data_path)")
+    a("--knn_data_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
+      help="with --eval: labelled image folder (the evaluation's classes) whose features become the neighbour bank; adds the detection "
+           "column knn and the weighted k-NN accuracy, implies --detection")
+    a("--knn_state", type=str, default=argparse.SUPPRESS, metavar="FILE",
+      help="with --eval: load a saved neighbour bank (neighbours.pth) instead of fitting (exclusive with --knn_data_path)")
+    a("--knn_k", type=int, default=argparse.SUPPRESS, metavar="K", help="neighbours per query, 1 .. 256 (default 20)")
+    a("--knn_temperature", type=float, default=argparse.SUPPRESS, metavar="T",
+      help="temperature of the k-NN vote exp((s_j - s_1) / T) (default 0.07)")
     return p.parse_args(argv)
 
 
@@ -388,6 +406,41 @@ def check_maha_flags(args):
     raise ValueError("--maha_shrinkage steers the fit of --maha_data_path DIR or --maha_state FILE: give one")
 
 
+KNN_FLAGS = ("knn_data_path", "knn_state", "knn_k", "knn_temperature")
+
+
+def check_knn_flags(args):
+    """How the run gets its neighbour bank: "fit" (--knn_data_path), "state" (--knn_state) or None.  The four --knn_* flags belong to
+    --eval, the two sources are exclusive, --knn_k / --knn_temperature need one of them; k lies in [1, 256] and the temperature is
+    positive and finite."""
+    if not any(hasattr(args, k) for k in KNN_FLAGS):
+        return None
+    if not args.eval:
+        raise ValueError("--knn_data_path / --knn_state / --knn_k / --knn_temperature belong to an evaluation: give --eval")
+    if hasattr(args, "knn_data_path") and hasattr(args, "knn_state"):
+        raise ValueError("--knn_data_path fits the neighbour bank and --knn_state loads it: give one")
+    if hasattr(args, "knn_k") and not 1 <= args.knn_k <= 256:
+        raise ValueError(f"--knn_k must lie in [1, 256], got {args.knn_k}")
+    if hasattr(args, "knn_temperature") and not 0.0 < args.knn_temperature < math.inf:
+        raise ValueError(f"--knn_temperature must be positive and finite, got {args.knn_temperature}")
+    if hasattr(args, "knn_data_path"):
+        return "fit"
+    if hasattr(args, "knn_state"):
+        return "state"
+    raise ValueError("--knn_k / --knn_temperature steer the bank of --knn_data_path DIR or --knn_state FILE: give one")
+
+
+def knn_lines(fit, stats):
+    """The two lines in front of `* Acc@1`, from fit_neighbours' (or load_neighbour_state's) result and the evaluation's stats."""
+    return ["* kNN bank of {n} images ({skipped} skipped), {classes} classes, k {k}, temperature {temperature:g}".format(**fit),
+            "* kNN Acc@1 {knn_acc1:.3f} mean {knn_mean:.5f}".format(**stats)]
+
+
+def knn_log_entries(fit, stats):
+    """What log.txt gains: the weighted k-NN accuracy, the mean knn of the evaluation set and the k in use."""
+    return {"test_knn_acc1": stats["knn_acc1"], "test_knn_mean": stats["knn_mean"], "test_knn_k": fit["k"]}
+
+
 def maha_lines(fit, stats):
     """The two lines in front of `* Acc@1`, from fit_density's result and the evaluation's stats."""
     return ["* Mahalanobis fit on {n} images ({skipped} skipped), {classes} classes ({empty_classes} empty), shrinkage {shrinkage:g}, "
@@ -520,7 +573,8 @@ def main(args):
     conformal = check_cp_flags(args)
     laplace = check_lap_flags(args)
     maha = check_maha_flags(args)
-    detection = detection or maha is not None
+    knn = check_knn_flags(args)
+    detection = detection or maha is not None or knn is not None
     gp_layer = getattr(args, "gp_layer", False)
     if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
         raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
@@ -637,6 +691,18 @@ def main(args):
         print("Load Mahalanobis state %s" % args.maha_state)
     if maha == "fit" and args.output_dir:
         torch.save(probe.density_state_dict(), os.path.join(args.output_dir, "density.pth"))
+    knn_fit = None
+    if knn == "fit":
+        loader_knn, _ = build_loader(args, encoder, args.knn_data_path, 1, train=False)
+        knn_fit = probe.fit_neighbours(DevicePrefetcher(loader_knn, device), k=getattr(args, "knn_k", 20),
+                                       temperature=getattr(args, "knn_temperature", 0.07))
+        if args.output_dir:
+            torch.save(probe.neighbour_state_dict(), os.path.join(args.output_dir, "neighbours.pth"))
+    elif knn == "state":
+        saved = torch.load(args.knn_state, map_location="cpu", weights_only=False)
+        saved = {**saved, **{key: getattr(args, "knn_" + key) for key in ("k", "temperature") if hasattr(args, "knn_" + key)}}
+        knn_fit = probe.load_neighbour_state(saved)
+        print("Load neighbour bank %s" % args.knn_state)
     ts_fit = None
     if ts_mode == "fit":
         loader_ts, _ = build_loader(args, encoder, args.ts_data_path, 1, train=False)
@@ -669,6 +735,9 @@ def main(args):
         if maha_fit is not None:
             stats["density_fit"] = maha_fit
             print("\n".join(maha_lines(maha_fit, stats)))
+        if knn_fit is not None:
+            stats["neighbour_fit"] = knn_fit
+            print("\n".join(knn_lines(knn_fit, stats)))
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
         if gp_layer:
             print(gp_variance_line(stats))
@@ -692,6 +761,7 @@ def main(args):
                                     **(temperature_log_entries(stats, ts_fit) if ts_mode else {}),
                                     **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {}),
                                     **(maha_log_entries(maha_fit, stats) if maha_fit is not None else {}),
+                                    **(knn_log_entries(knn_fit, stats) if knn_fit is not None else {}),
                                     **(conformal_log_entries(cp_fit, stats["conformal"]) if conformal else {})}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)

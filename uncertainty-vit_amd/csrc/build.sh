@@ -60,11 +60,17 @@ pids+=($!)
 # no fast-math
 ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c maha.hip -o obj/maha.o ) &
 pids+=($!)
+# knn.hip screens rows with isfinite, finds NaN similarities with s == s and folds -0 into +0 by an addition (equal similarities get
+# equal keys): no fast-math
+( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c knn.hip -o obj/knn.o ) &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 # Build-time guard (round 4): no taken branch between an MFMA and the first read of its result without the wait states the MFMA
 # needs -- hipcc pads the fall-through path only (tools/check_mfma_hazard.py; tools/micro/mfma_branch_hazard.hip is the flagged case).
 if [ -z "$UVIT_SKIP_HAZARD_CHECK" ]; then
   python3 ../../tools/check_mfma_hazard.py --compile gemm.hip attention.hip attention2.hip $UVIT_EXTRA_FLAGS || { echo "MFMA hazard check FAILED"; exit 1; }
+  # knn.hip, the one MFMA user built without fast-math (the later flag wins)
+  python3 ../../tools/check_mfma_hazard.py --compile knn.hip -fno-fast-math $UVIT_EXTRA_FLAGS || { echo "MFMA hazard check FAILED"; exit 1; }
 fi
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT" obj/*.o
 echo "$HASH" > "$OUT.hash"

@@ -35,6 +35,9 @@ CP_KINDS = {"lac": 0, "aps": 1, "raps": 2}                         # the `kind` 
 MAHA_MAX_C, MAHA_MAX_K = 2048, 4096          # csrc/maha.hip: C % 4 == 0, 4 <= C <= 2048, 2 <= K <= 4096, 1 <= B <= 65535
 MAHA_COLUMNS = ("maha", "rmaha")             # the detection columns a fitted density appends to the class's
 MAHA_SHRINKAGE = 1e-3                        # an option's default, not a measured optimum
+KNN_MAX_K, KNN_MAX_N, KNN_MAX_C = 256, 1 << 22, 2048       # csrc/knn.hip: 1 <= k <= 256, 1 <= N <= 2^22, C % 32 == 0, 32 <= C <= 2048
+KNN_COLUMNS = ("knn",)                       # the detection column a neighbour bank appends behind the class's and MAHA_COLUMNS
+KNN_K, KNN_TEMPERATURE = 20, 0.07            # the weighted k-NN classifier of DINO / iBOT
 
 
 def _timm_trunc_normal_(t, std):
@@ -78,6 +81,8 @@ class LinearProbe(nn.Module):
         self._cp, self._cp_ws = None, None
         # feature density (Mahalanobis scores): the fitted or loaded state and the largest batch its buffers hold
         self._maha, self._maha_batch, self._maha_eval = None, 0, None
+        # neighbour bank (k-NN score and classifier): the fitted or loaded state and the largest batch its buffers hold
+        self._knn, self._knn_batch, self._knn_eval = None, 0, None
         self._setup_head(init_scale)
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
 
@@ -118,6 +123,10 @@ class LinearProbe(nn.Module):
         if self._maha is not None:                   # the density moves with the module and stays float64; its sums stay on the host
             for key in ("W", "W0", "Wmu", "Wmu0", "count_dev"):
                 self._maha[key] = self._maha[key].to(new.device)
+        self._knn_batch = 0
+        if self._knn is not None:                    # the bank moves with the module and stays bf16
+            for key in ("bank", "labels"):
+                self._knn[key] = self._knn[key].to(new.device)
         self._rebind()
         return self
 
@@ -343,6 +352,8 @@ class LinearProbe(nn.Module):
                 self._det_reserve(B)
                 if self._maha_eval is not None:
                     self._maha_columns(B, None)
+                if self._knn_eval is not None:
+                    self._knn_columns(B, None)
                 self._logits_into(B)
                 self._ts_apply(B)
                 self._det_rows(B, None)
@@ -373,9 +384,10 @@ class LinearProbe(nn.Module):
         return type(self).DETECT_COLUMNS
 
     def _det_refresh(self):
-        """The instance's DETECT_COLUMNS: the head's own columns, followed by MAHA_COLUMNS while a density is set.  An instance
-        attribute only where that differs from the class's."""
-        cols = tuple(self._det_class_columns()) + (MAHA_COLUMNS if self._maha is not None else ())
+        """The instance's DETECT_COLUMNS: the head's own columns, followed by MAHA_COLUMNS while a density is set and by KNN_COLUMNS
+        while a neighbour bank is set.  An instance attribute only where that differs from the class's."""
+        cols = tuple(self._det_class_columns()) + (MAHA_COLUMNS if self._maha is not None else ()) + \
+            (KNN_COLUMNS if self._knn is not None else ())
         if cols == type(self).DETECT_COLUMNS:
             self.__dict__.pop("DETECT_COLUMNS", None)
         else:
@@ -558,6 +570,203 @@ class LinearProbe(nn.Module):
         self._det_column("rmaha", self._rmaha_col, B)
         if labels is not None:
             ev["slabs"].append(self._maha_col[:B].clone())
+
+    # ---- neighbour bank: k-NN OOD score and weighted k-NN classifier (csrc/knn.hip) ----
+    @staticmethod
+    def _knn_settings(k, temperature):
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= KNN_MAX_K:
+            raise native.UvitError(f"k must be a whole number in [1, {KNN_MAX_K}], got {k}")
+        T = float(temperature)
+        if not 0.0 < T < math.inf:
+            raise native.UvitError(f"the k-NN temperature must be positive and finite, got {temperature}")
+        return int(k), T
+
+    def _knn_check_dims(self):
+        K, Cd = self.num_classes, self.embed_dim
+        if Cd < 32 or Cd % 32 or Cd > KNN_MAX_C or not 2 <= K <= MAHA_MAX_K:
+            raise native.UvitError(f"the k-NN ops take an embed dim that is a multiple of 32 in [32, {KNN_MAX_C}] and 2 .. {MAHA_MAX_K} "
+                                   f"classes, got {Cd} and {K}")
+
+    def _knn_install(self, bank, labels, sums, k, temperature, own=False):
+        """A bank of unit bf16 rows (n, C), their int32 labels (-1: a skipped row) and sums = {rows used, rows skipped} become the
+        state in use, on the probe's device (`own`: written by fit_neighbours just now, the labels need no look)."""
+        k, T = self._knn_settings(k, temperature)
+        self._knn_check_dims()
+        K, Cd = self.num_classes, self.embed_dim
+        if not (torch.is_tensor(bank) and torch.is_tensor(labels)) or bank.dtype != torch.bfloat16 or labels.dtype != torch.int32:
+            raise native.UvitError("the neighbour state holds a bfloat16 bank and int32 labels")
+        if bank.ndim != 2 or bank.shape[1] != Cd or tuple(labels.shape) != (bank.shape[0],) or not 1 <= bank.shape[0] <= KNN_MAX_N:
+            raise native.UvitError(f"the neighbour state belongs to another probe: its bank must have shape (n, {Cd}) with 1 <= n <= "
+                                   f"{KNN_MAX_N} and one label per row")
+        sums = torch.as_tensor(sums, dtype=torch.float64).cpu().contiguous()
+        if tuple(sums.shape) != (2,):
+            raise native.UvitError("the neighbour state's sums must be {rows used, rows skipped}")
+        if not own and (int(labels.max()) >= K or int(labels.min()) < -1):
+            raise native.UvitError(f"the neighbour state belongs to another probe: its labels must lie in [-1, {K})")
+        n, skipped = int(sums[0]), int(sums[1])
+        if n < k:
+            raise native.UvitError(f"the neighbour bank holds {n} usable rows (finite features, a label inside [0, K)), fewer than k = {k}")
+        dev = self._arena.device
+        self._knn = {"bank": bank.contiguous().to(dev), "labels": labels.contiguous().to(dev), "sums": sums,
+                     "info": {"n": n, "skipped": skipped, "classes": K, "k": k, "temperature": T}}
+        self._knn_batch = 0
+        self._det_refresh()
+        return dict(self._knn["info"])
+
+    def fit_neighbours(self, loader, k=KNN_K, temperature=KNN_TEMPERATURE):
+        """A bank of the training features for nearest-neighbour search: one pass over a labelled loader (items as evaluate()'s) of
+        the encoder forward, pool + norm and uvit_op_knn_rows, which appends the batch's unit bf16 rows and int32 labels to a device
+        bank (allocated once when the loader's data set has a length, grown geometrically otherwise); the two counters are read once,
+        at the end.  Nothing is trained and the head takes no part.  Returns {n (usable rows), skipped (rows with a non-finite
+        feature, a zero norm or a label outside [0, K): kept as zero rows that are never a neighbour), classes, k, temperature};
+        fewer usable rows than k are refused."""
+        k, T = self._knn_settings(k, temperature)
+        self._knn_check_dims()
+        K, Cd = self.num_classes, self.embed_dim
+        try:
+            cap = min(KNN_MAX_N, max(0, len(loader.dataset)))
+        except (AttributeError, TypeError):
+            cap = 0
+        bank = lab = sums = None
+        n = 0
+        for item in loader:
+            images, labels = item
+            if isinstance(images, (tuple, list)):
+                images = images[0]
+            B = self._features(images)
+            if torch.is_tensor(labels) and not labels.is_cuda:
+                labels = labels.to(images.device, non_blocking=True)
+            labels = self._labels(labels, B)
+            if n + B > KNN_MAX_N:
+                raise native.UvitError(f"a neighbour bank holds at most {KNN_MAX_N} rows, the loader holds more")
+            if bank is None or n + B > bank.shape[0]:
+                cap = min(KNN_MAX_N, max(n + B, cap, 2 * (bank.shape[0] if bank is not None else 0), 1024))
+                grown = torch.zeros(cap, Cd, dtype=torch.bfloat16, device=images.device)
+                glab = torch.full((cap,), -1, dtype=torch.int32, device=images.device)
+                if n:
+                    grown[:n].copy_(bank[:n])
+                    glab[:n].copy_(lab[:n])
+                bank, lab = grown, glab
+            if sums is None:
+                sums = torch.zeros(2, dtype=torch.float64, device=images.device)
+            check(lib().uvit_op_knn_rows(ptr(self._feat), ptr(labels), C.c_void_p(bank.data_ptr() + 2 * n * Cd),
+                                         C.c_void_p(lab.data_ptr() + 4 * n), ptr(sums), B, Cd, K, cur_stream()), "uvit_op_knn_rows")
+            n += B
+        if bank is None:
+            raise native.UvitError("the neighbour fit needs at least k labelled samples")
+        return self._knn_install(bank[:n].clone(), lab[:n].clone(), sums.cpu(), k, T, own=True)  # the one read
+
+    def set_neighbours(self, state):
+        """None forgets the bank (the detection columns are what they were); a dict of neighbour_state_dict() is loaded."""
+        if state is not None:
+            return self.load_neighbour_state(state)
+        self._knn, self._knn_batch = None, 0
+        self._det_refresh()
+
+    @property
+    def neighbours(self):
+        """{n, skipped, classes, k, temperature} of the bank in use, None when there is none."""
+        return dict(self._knn["info"]) if self._knn is not None else None
+
+    def set_neighbours_k(self, k, temperature=None):
+        """Another k (and temperature) for the bank in use; the data are not read again."""
+        st = self._knn
+        if st is None:
+            raise native.UvitError("set_neighbours_k needs fit_neighbours() or load_neighbour_state() first")
+        k, T = self._knn_settings(k, st["info"]["temperature"] if temperature is None else temperature)
+        if st["info"]["n"] < k:
+            raise native.UvitError(f"the neighbour bank holds {st['info']['n']} usable rows, fewer than k = {k}")
+        st["info"].update(k=k, temperature=T)
+        self._knn_batch = 0
+        return dict(st["info"])
+
+    def neighbour_state_dict(self):
+        """What a bank is made of, on the host: bank (n, C) bfloat16, labels (n) int32, sums = {rows used, rows skipped}, k and
+        temperature.  Not part of state_dict(): neither a parameter nor a buffer."""
+        st = self._knn
+        if st is None:
+            raise native.UvitError("neighbour_state_dict needs fit_neighbours() or load_neighbour_state() first")
+        return {"bank": st["bank"].cpu().clone(), "labels": st["labels"].cpu().clone(), "sums": st["sums"].clone(), "k": st["info"]["k"],
+                "temperature": st["info"]["temperature"]}
+
+    def load_neighbour_state(self, sd):
+        """Install a saved bank (neighbour_state_dict()); one of another embed dim or class count is refused."""
+        keys = ("bank", "labels", "sums", "k", "temperature")
+        if not (isinstance(sd, dict) and set(keys) <= set(sd)):
+            raise native.UvitError("load_neighbour_state takes a dict of neighbour_state_dict()")
+        return self._knn_install(*(sd[k] for k in keys))
+
+    def _knn_buffers_for(self, B):
+        st = self._knn
+        k, n, Cd, dev = st["info"]["k"], st["bank"].shape[0], self.embed_dim, self._arena.device
+        if st["bank"].device != dev:
+            raise native.UvitError("the neighbour bank and the probe are on different devices")
+        if B > self._knn_batch:
+            self._knn_query = torch.zeros(B, Cd, dtype=torch.bfloat16, device=dev)
+            self._knn_valid, self._knn_pred = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
+            self._knn_sim = torch.zeros(B, k, dtype=torch.float32, device=dev)
+            self._knn_idx = torch.zeros(B, k, dtype=torch.int32, device=dev)
+            self._knn_col = torch.zeros(B, dtype=torch.float32, device=dev)
+            self._knn_ws = torch.empty(0, dtype=torch.uint8, device=dev)
+            self._knn_batch = B
+        ws = lib().uvit_op_knn_search_ws_bytes(B, Cd, n, k, 0)
+        if ws < 0:
+            check(int(ws), "uvit_op_knn_search_ws_bytes")
+        if self._knn_ws.numel() < ws:
+            self._knn_ws = torch.empty(int(ws), dtype=torch.uint8, device=dev)
+
+    def _knn_into(self, feat, B, labels=None, correct=None):
+        """uvit_op_knn_rows, uvit_op_knn_search and uvit_op_knn_scores of feat[:B] on the current stream into self._knn_sim,
+        self._knn_idx (B, k), self._knn_col and self._knn_pred."""
+        st = self._knn
+        if st is None:
+            raise native.UvitError("the k-NN scores need fit_neighbours() or load_neighbour_state() first")
+        if self._arena.device.type != "cuda":
+            raise native.UvitError("the k-NN scores run as HIP kernels: move the encoder and the probe to a GPU (no CPU fallback)")
+        self._knn_buffers_for(B)
+        K, Cd, k, n = self.num_classes, self.embed_dim, st["info"]["k"], st["bank"].shape[0]
+        s = cur_stream()
+        check(lib().uvit_op_knn_rows(ptr(feat), None, ptr(self._knn_query), ptr(self._knn_valid), None, B, Cd, K, s), "uvit_op_knn_rows")
+        check(lib().uvit_op_knn_search(ptr(self._knn_query), ptr(self._knn_valid), ptr(st["bank"]), ptr(st["labels"]), ptr(self._knn_sim),
+                                       ptr(self._knn_idx), k, ptr(self._knn_ws), self._knn_ws.numel(), B, Cd, n, k, 0, s),
+              "uvit_op_knn_search")
+        check(lib().uvit_op_knn_scores(ptr(self._knn_sim), ptr(self._knn_idx), k, ptr(st["labels"]), n, ptr(self._knn_col),
+                                       ptr(self._knn_pred), None, 0, ptr(labels), ptr(correct), B, k, K,
+                                       C.c_double(st["info"]["temperature"]), s), "uvit_op_knn_scores")
+
+    def _knn_result(self, feat, B, neighbours):
+        self._knn_into(feat, B)
+        out = {"knn": self._knn_col[:B].clone(), "pred": self._knn_pred[:B].clone()}
+        if neighbours:
+            out["sim"], out["idx"] = self._knn_sim[:B].clone(), self._knn_idx[:B].clone()
+        return out
+
+    def neighbour_scores(self, images, neighbours=False):
+        """{"knn" (B) fp32, "pred" (B) int32} of the images' features against the bank in use, device tensors; with `neighbours`, also
+        "sim" (B, k) fp32 and "idx" (B, k) int32, the k nearest bank rows by (similarity descending, index ascending).  knn = 2 - 2 s_k,
+        the squared distance between the unit vectors to the k-th nearest bank row (larger = more out of distribution); pred = the
+        class with the largest vote sum_j exp((s_j - s_1) / T) over the k neighbours.  A row with a non-finite feature: NaN, -1."""
+        if self._knn is None:
+            raise native.UvitError("neighbour_scores needs fit_neighbours() or load_neighbour_state() first")
+        B = self._features(images)
+        return self._knn_result(self._feat, B, neighbours)
+
+    def neighbour_batch(self, feat, neighbours=False):
+        """neighbour_scores() of caller-supplied GPU features (B, C) fp32; nothing synchronises with the host."""
+        if not torch.is_tensor(feat) or not feat.is_cuda:
+            raise native.UvitError("feat must be a GPU tensor: the HIP path has no CPU fallback")
+        if feat.dtype != torch.float32 or feat.ndim != 2 or feat.shape[1] != self.embed_dim or not feat.is_contiguous() or not feat.shape[0]:
+            raise native.UvitError(f"feat must be a contiguous float32 tensor of shape (B, {self.embed_dim})")
+        return self._knn_result(feat, feat.shape[0], neighbours)
+
+    def _knn_columns(self, B, labels):
+        """Inside evaluate(detection=True) with a bank: the column of self._feat[:B] into the store (behind _maha_columns, in front of
+        _det_rows).  The evaluation set's rows (labels given) are also counted against their labels and kept for the mean."""
+        ev = self._knn_eval
+        self._knn_into(self._feat, B, labels, ev["correct"] if labels is not None else None)
+        self._det_column("knn", self._knn_col, B)
+        if labels is not None:
+            ev["slabs"].append(self._knn_col[:B].clone())
 
     # ---- post-hoc temperature scaling (csrc/tscale.hip, DESIGN.md section 9.7) ----
     def _ts_fit(self, logits, ld, labels, N, t_min, t_max, tol, max_iter):
@@ -908,6 +1117,9 @@ class LinearProbe(nn.Module):
         While a density is set (fit_density, load_density_state), detection also stores the columns `maha` and `rmaha` of every batch's
         features, the OOD images' included, behind the head's own columns, and stats gains "maha_mean" (the mean of `maha` over the
         evaluation rows that are not NaN) and "maha_acc1" (the nearest-class-mean accuracy in percent, counted on the device).
+        While a neighbour bank is set (fit_neighbours, load_neighbour_state), detection also stores the column `knn` of every batch's
+        features, the OOD images' included, behind those, and stats gains "knn_mean" (the mean of `knn` over the evaluation rows that
+        are not NaN) and "knn_acc1" (the weighted k-NN accuracy in percent, counted on the device).
         `temperature`: None launches and returns exactly the above.  True applies the fitted or set post-hoc temperature
         (fit_temperature, set_temperature; an error when there is none), a number applies that T: uvit_op_ts_scale then runs in place
         on the logits directly behind every _logits_into of the evaluation, the OOD images included, with 1 / T read from a device
@@ -919,13 +1131,14 @@ class LinearProbe(nn.Module):
         self._ts_on, ts_value = self._ts_begin(temperature)
         self._det = {"scores": None, "flags": None, "cap": 0, "n": 0} if detection else None
         self._maha_eval = {"correct": None, "slabs": []} if detection and self._maha is not None else None
+        self._knn_eval = {"correct": None, "slabs": []} if detection and self._knn is not None else None
         try:
             stats = self._evaluate(loader, calibration, ood_loader)
             if ts_value is not None:
                 stats["temperature"] = ts_value
             return stats
         finally:
-            self._det, self._in_ood, self._ts_on, self._maha_eval = None, False, None, None
+            self._det, self._in_ood, self._ts_on, self._maha_eval, self._knn_eval = None, False, None, None, None
 
     def _evaluate(self, loader, calibration, ood_loader):
         detection = self._det is not None
@@ -949,6 +1162,10 @@ class LinearProbe(nn.Module):
                     if self._maha_eval["correct"] is None:
                         self._maha_eval["correct"] = torch.zeros(1, dtype=torch.int32, device=images.device)
                     self._maha_columns(B, labels)
+                if self._knn_eval is not None:
+                    if self._knn_eval["correct"] is None:
+                        self._knn_eval["correct"] = torch.zeros(1, dtype=torch.int32, device=images.device)
+                    self._knn_columns(B, labels)
             self._logits_into(B)
             self._ts_apply(B)
             slot = C.c_void_p(slab.data_ptr() + 4 * (len(losses) % 256))
@@ -974,6 +1191,8 @@ class LinearProbe(nn.Module):
                 empty["detection"] = self._det_stats(mis, ood, 0, 0, n_ood, ood_loader is not None)
             if self._maha_eval is not None:
                 empty.update(maha_mean=float("nan"), maha_acc1=float("nan"))
+            if self._knn_eval is not None:
+                empty.update(knn_mean=float("nan"), knn_acc1=float("nan"))
             return empty
         slabs = {id(s): s for s, _ in losses}
         host = {k: v.cpu() for k, v in slabs.items()}                       # the one read
@@ -995,6 +1214,10 @@ class LinearProbe(nn.Module):
             vals = [v for v in torch.cat(self._maha_eval["slabs"]).cpu().tolist() if not math.isnan(v)]
             stats["maha_mean"] = math.fsum(vals) / len(vals) if vals else float("nan")
             stats["maha_acc1"] = 100.0 * int(self._maha_eval["correct"].cpu()) / n
+        if self._knn_eval is not None:
+            vals = [v for v in torch.cat(self._knn_eval["slabs"]).cpu().tolist() if not math.isnan(v)]
+            stats["knn_mean"] = math.fsum(vals) / len(vals) if vals else float("nan")
+            stats["knn_acc1"] = 100.0 * int(self._knn_eval["correct"].cpu()) / n
         return stats
 
     # ---- stability under perturbation sequences ----

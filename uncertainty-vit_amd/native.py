@@ -238,6 +238,10 @@ _PROTOTYPES = {
     "uvit_op_maha_accumulate": (_i, [_vp] * 8 + [_i64, _i, _i, _i, _vp]),
     "uvit_op_maha_scores_ws_bytes": (_i64, [_i, _i, _i]),
     "uvit_op_maha_scores": (_i, [_vp] * 10 + [_i64, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "uvit_op_knn_rows": (_i, [_vp] * 5 + [_i, _i, _i, _vp]),
+    "uvit_op_knn_search_ws_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "uvit_op_knn_search": (_i, [_vp] * 6 + [_i64, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "uvit_op_knn_scores": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, C.c_double, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
