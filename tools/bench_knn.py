@@ -74,9 +74,9 @@ def main():
         n = p._features(x)
         p._det["n"] = 0
         p._det_reserve(n)
-        if p._knn_eval is not None:
-            p._knn_columns(n, y)
-            p._knn_eval["slabs"].clear()
+        for score, ev in p._score_eval:
+            score.eval_batch(n, y, ev)
+            ev["slabs"].clear()
         p._logits_into(n)
         p._det_rows(n, y)
 
@@ -92,10 +92,10 @@ def main():
         near.load_neighbour_state({"bank": bank, "labels": labels, "sums": torch.tensor([float(N), 0.0]), "k": k, "temperature": 0.07})
         for p in (plain, near):
             p._det = {"scores": None, "flags": None, "cap": 0, "n": 0}
-        near._knn_eval = {"correct": torch.zeros(1, dtype=torch.int32, device="cuda"), "slabs": []}
+        near._score_eval = [(near._bank, {"correct": torch.zeros(1, dtype=torch.int32, device="cuda"), "slabs": []})]
         groups = [(timed(fused, a.iters, a.warmup), timed(vendor, a.iters, a.warmup), timed(lambda: det_batch(plain), a.iters, a.warmup),
                    timed(lambda: det_batch(near), a.iters, a.warmup)) for _ in range(a.repeats)]
-        plain._det = near._det = near._knn_eval = None
+        plain._det, near._det, near._score_eval = None, None, ()
         t_fused, t_vendor, t_plain, t_near = (sorted(grp[i] for grp in groups)[len(groups) // 2] for i in range(4))
         fused()
         tv, ti = vendor()

@@ -66,20 +66,20 @@ def main():
     onehot[torch.arange(4 * K), lab] = 1.0
     fit = dens.load_density_state({"S": rows.T @ rows, "class_sum": onehot.T @ rows, "total_sum": rows.sum(0), "class_count": onehot.sum(0),
                                    "sums": torch.tensor([4.0 * K, 0.0]), "shrinkage": 1e-3})
-    L, s, st = lib(), cur_stream, dens._maha
+    L, s, st, sc = lib(), cur_stream, dens._maha, dens._density
     n_acc = Cd * Cd + K * Cd + Cd + K + 2
     acc = torch.zeros(n_acc, dtype=torch.float64, device="cuda")
     at = lambda off: C.c_void_p(acc.data_ptr() + 8 * off)      # noqa: E731
     aws = torch.empty(int(L.uvit_op_maha_accumulate_ws_bytes(B, Cd, K)), dtype=torch.uint8, device="cuda")
     for p in (plain, dens):
         p._features(x)
-    dens._maha_buffers_for(B)
+    sc.buffers_for(B)
     parts = {
         "accumulate": lambda: check(L.uvit_op_maha_accumulate(ptr(dens._feat), ptr(y), at(0), at(Cd * Cd), at(Cd * Cd + K * Cd),
                                                               at(Cd * Cd + K * Cd + Cd), at(n_acc - 2), ptr(aws), aws.numel(), B, Cd, K, s())),
         "scores": lambda: check(L.uvit_op_maha_scores(ptr(dens._feat), ptr(st["W"]), ptr(st["W0"]), ptr(st["Wmu"]), ptr(st["Wmu0"]),
-                                                      ptr(st["count_dev"]), ptr(dens._maha_col), ptr(dens._rmaha_col), ptr(dens._maha_pred), None, K,
-                                                      None, None, ptr(dens._maha_ws), dens._maha_ws.numel(), B, Cd, K, s())),
+                                                      ptr(st["count_dev"]), ptr(sc.col), ptr(sc.rcol), ptr(sc.pred), None, K,
+                                                      None, None, ptr(sc.ws), sc.ws.numel(), B, Cd, K, s())),
     }
 
     def det_batch(p):
@@ -87,21 +87,21 @@ def main():
         n = p._features(x)
         p._det["n"] = 0
         p._det_reserve(n)
-        if p._maha_eval is not None:
-            p._maha_columns(n, y)
-            p._maha_eval["slabs"].clear()
+        for score, ev in p._score_eval:
+            score.eval_batch(n, y, ev)
+            ev["slabs"].clear()
         p._logits_into(n)
         p._det_rows(n, y)
 
     for p in (plain, dens):
         p._det = {"scores": None, "flags": None, "cap": 0, "n": 0}
-    dens._maha_eval = {"correct": torch.zeros(1, dtype=torch.int32, device="cuda"), "slabs": []}
+    dens._score_eval = [(sc, {"correct": torch.zeros(1, dtype=torch.int32, device="cuda"), "slabs": []})]
     groups = []
     for _ in range(a.repeats):
         groups.append((timed(lambda: model.forward_features(x, None, None), a.iters, a.warmup),
                        timed(lambda: det_batch(plain), a.iters, a.warmup), timed(lambda: det_batch(dens), a.iters, a.warmup)))
     fwd, ev_plain, ev_dens = (sorted(grp[i] for grp in groups)[len(groups) // 2] for i in range(3))
-    plain._det = dens._det = dens._maha_eval = None
+    plain._det, dens._det, dens._score_eval = None, None, ()
     ms = {k: timed(fn, a.iters, a.warmup) for k, fn in parts.items()}
     # accumulate: B C^2 FMAs into S, B C adds twice; S read and written, the touched class rows, the features
     acc_flops, acc_bytes = 2 * B * Cd * Cd + 2 * B * Cd, 16 * Cd * Cd + 16 * min(B, K) * Cd + 4 * B * Cd

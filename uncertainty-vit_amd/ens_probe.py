@@ -13,7 +13,6 @@ counter-based, nothing stored), the per-member gradient clip and the combination
 csrc/ens.hip.  Each member receives exactly the gradient it would receive alone, and the clip is per member: without bagging member m
 trains as a LinearProbe started from its initial values would.
 """
-import ctypes as C
 import math
 
 import torch
@@ -47,7 +46,8 @@ class EnsembleProbe(LinearProbe):
         super().__init__(encoder, num_classes, smoothing=smoothing, init_scale=init_scale)
 
     # ---- arena plumbing ----
-    def _keys(self):
+    @property
+    def _OPT_KEYS(self):
         return [f"heads.{m}.{n}" for n in ("weight", "bias") for m in range(self.members)]
 
     def _views(self):
@@ -79,31 +79,18 @@ class EnsembleProbe(LinearProbe):
         with torch.no_grad():
             for m in range(M):
                 getattr(self.heads, str(m)).weight.copy_(_timm_trunc_normal_(torch.empty(K, Cd), std=0.02).mul_(init_scale))
-        self._ens_batch, self._eval = 0, None
-
-    def _rebind(self):
-        for p, lo, hi, shape in self._views():
-            p.data = self._arena[lo:hi].view(shape)
-            p.grad = self._grad_arena[lo:hi].view(shape)
+        self._eval = None
 
     def _apply(self, fn, recurse=True):
-        self._ens_batch = 0
         self.member_norms = fn(self.member_norms)
         return super()._apply(fn, recurse)
 
-    def _buffers_for(self, B, calibration=False):
-        super()._buffers_for(B, calibration)
-        if B > self._ens_batch:
-            M, dev = self.members, self._arena.device
-            z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)      # noqa: E731
-            self._lin, self._dlin, self._bag, self._member_rows = z(B, self._rows), z(B, self._rows), z(B, M), z(B, M)
-            self._member_loss = z(M + 1)             # the members' losses of the last train_step, then their mean
-            self._unc = z(B, 5, dt=torch.float64)
-            self._ens_batch = B
-        return self._buf_batch
-
-    def _bias_ptr(self, arena):
-        return C.c_void_p(arena.data_ptr() + 4 * self._n_decay)
+    def _head_buffers_for(self, B):
+        M, dev = self.members, self._arena.device
+        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)      # noqa: E731
+        self._lin, self._dlin, self._bag, self._member_rows = z(B, self._rows), z(B, self._rows), z(B, M), z(B, M)
+        self._member_loss = z(M + 1)             # the members' losses of the last train_step, then their mean
+        self._unc = z(B, 5, dt=torch.float64)
 
     # ---- forward ----
     def _lin_into(self, B):
@@ -133,7 +120,7 @@ class EnsembleProbe(LinearProbe):
         self._combine_into(B, slab)
         if det:      # evaluate(detection=True): the five columns of the batch go to the set-level store
             for col, name in enumerate(UNC_KEYS):
-                self._det_column(name, slab[:, col], B)
+                self._own_column(name, slab[:, col], B, None)
         if ev is not None and ev["losses"] is not None and ev.get("labels") is not None:
             M, dev = self.members, self._arena.device
             if ev["counters"] is None:
@@ -253,14 +240,3 @@ class EnsembleProbe(LinearProbe):
         for m, sd in enumerate(heads):
             probe.load_member(m, sd)
         return probe
-
-    # ---- optimizer state beside heads.* in a checkpoint ----
-    def optimizer_state_dict(self):
-        cut = lambda t: {k: t[lo:hi].view(shape).cpu().clone() for k, (_, lo, hi, shape) in zip(self._keys(), self._views())}  # noqa: E731
-        return {"step": self.step_count, "exp_avg": cut(self.exp_avg), "exp_avg_sq": cut(self.exp_avg_sq)}
-
-    def load_optimizer_state_dict(self, sd):
-        self.step_count = int(sd["step"])
-        for arena, key in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
-            for k, (_, lo, hi, shape) in zip(self._keys(), self._views()):
-                arena[lo:hi].view(shape).copy_(sd[key][k])

@@ -10,6 +10,7 @@ pad to 4] whose decay group (W_out) comes first.  inv(P) is formed on the host i
 double: plumbing, not the hot path, and no device solver is needed.  The class is the specification: the reference's
 VisionTransformer overwrites this head with an nn.Linear (modeling_finetune.py:416-421) and never uses it.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -20,6 +21,7 @@ from . import native
 from .linear_probe import LinearProbe
 from .modeling_cyclical import _Holder
 from .native import check, cur_stream, f32, lib, ptr
+from .probe_util import ws_size
 
 __all__ = ["GPProbe"]
 
@@ -88,13 +90,11 @@ class GPProbe(LinearProbe):
             h._gp_input_normalize_layer.bias.zero_()
             self._w_rf.copy_(w_rf)
             self._b_rf.copy_(b_rf)
-        self._gp_batch, self._cov_tick, self._sigma_key, self._mf, self._var_slabs = 0, 0, None, 0.0, None
+        self._cov_tick, self._sigma_key, self._mf = 0, None, 0.0
         self.reset_cov()
 
     def _rebind(self):
-        for p, lo, hi, shape in self._views():
-            p.data = self._arena[lo:hi].view(shape)
-            p.grad = self._grad_arena[lo:hi].view(shape)
+        super()._rebind()
         self.head._random_feature.weight.data, self.head._random_feature.bias.data = self._w_rf, self._b_rf
         self.head.precision_matrix.data = self._P
 
@@ -102,7 +102,7 @@ class GPProbe(LinearProbe):
         self._w_rf, self._b_rf, self._P = (fn(t).contiguous() for t in (self._w_rf, self._b_rf, self._P))
         if self._P.dtype != torch.float32:
             raise NotImplementedError("the head stays fp32")
-        self._gp_batch, self._sigma_key = 0, None
+        self._sigma_key = None
         self._cov_tick += 1
         return super()._apply(fn, recurse)
 
@@ -111,19 +111,13 @@ class GPProbe(LinearProbe):
         self._cov_tick += 1                      # the precision matrix may have changed: inv(P) is formed again
         return out
 
-    def _buffers_for(self, B, calibration=False):
-        super()._buffers_for(B, calibration)
-        if B > self._gp_batch:
-            K, Cd, D, dev = self.num_classes, self.embed_dim, self.num_inducing, self._arena.device
-            ws = lib().uvit_op_gp_ln_grad_ws_bytes(B, Cd, D)
-            if ws < 0:
-                check(int(ws), "uvit_op_gp_ln_grad_ws_bytes")
-            z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)      # noqa: E731
-            self._phi, self._u, self._ghat, self._gp_scratch = z(B, D), z(B, D), z(B, Cd), z(ws // 4)
-            self._var = z(B, dt=torch.float64)
-            self._zero_bias, self._dbias = z(K), z(K)      # the output layer has no bias: gp_output_bias is the constant 0 (:561, :590)
-            self._gp_batch = B
-        return self._buf_batch
+    def _head_buffers_for(self, B):
+        K, Cd, D, dev = self.num_classes, self.embed_dim, self.num_inducing, self._arena.device
+        ws = ws_size(lib().uvit_op_gp_ln_grad_ws_bytes, B, Cd, D)
+        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)      # noqa: E731
+        self._phi, self._u, self._ghat, self._gp_scratch = z(B, D), z(B, D), z(B, Cd), z(ws // 4)
+        self._var = z(B, dt=torch.float64)
+        self._zero_bias, self._dbias = z(K), z(K)      # the output layer has no bias: gp_output_bias is the constant 0 (:561, :590)
 
     # ---- forward ----
     def _phi_into(self, B, keep=False):
@@ -153,15 +147,12 @@ class GPProbe(LinearProbe):
               "uvit_op_probe_logits")
         if keep:
             return
-        var, det = None, self._det is not None
-        if self._var_slabs is not None and not self._in_ood:     # evaluate(variance=True): the batch's variances stay on the device until the last batch
-            var = torch.empty(B, dtype=torch.float64, device=self._arena.device)
-            self._var_slabs.append(var)
-        if var is not None or self._mf > 0.0 or det:
-            var = self._var if var is None else var
+        # evaluate(variance=True) keeps the batch's variances on the device until the last batch: they get a tensor of their own
+        keep_var = self._var_slabs is not None and not self._in_ood
+        var = torch.empty(B, dtype=torch.float64, device=self._arena.device) if keep_var else self._var
+        if keep_var or self._mf > 0.0 or self._det is not None:
             self._variance_into(B, var)
-        if det:                                  # evaluate(detection=True): the variance is a column of the set-level store
-            self._det_column("gp_var", var, B)
+            self._own_column("gp_var", var, B, self._var_slabs, fresh=keep_var)     # evaluate(detection=True): a column of the store
         if self._mf > 0.0:
             check(lib().uvit_op_gp_mean_field(ptr(self._logits), ptr(var), C.c_double(self._mf), ptr(self._logits), B, K, cur_stream()),
                   "uvit_op_gp_mean_field")
@@ -202,39 +193,35 @@ class GPProbe(LinearProbe):
         return self._clip_and_update(lr, weight_decay, max_norm)
 
     # ---- evaluation ----
-    @staticmethod
-    def _factor(mean_field):
+    @contextlib.contextmanager
+    def _mean_field(self, mean_field):
+        """`mean_field` in force (self._mf) for the _logits_into calls of one loop."""
         mf = float(mean_field)
         if not mf >= 0.0:
             raise native.UvitError(f"mean_field must be >= 0, got {mean_field}")
-        return mf
+        self._mf = mf
+        try:
+            yield
+        finally:
+            self._mf = 0.0
 
     DETECT_COLUMNS = LinearProbe.DETECT_COLUMNS + ("gp_var",)
 
     def fit_temperature(self, loader, mean_field=0.0, **kw):
         """LinearProbe.fit_temperature on the GP logits, on the mean-field logits with `mean_field` > 0: give the factor of the
         evaluation the temperature is meant for, so that the fit sees the logits that evaluation sees."""
-        self._mf = self._factor(mean_field)
-        try:
+        with self._mean_field(mean_field):
             return super().fit_temperature(loader, **kw)
-        finally:
-            self._mf = 0.0
 
     def fit_conformal(self, loader, alpha=0.1, mean_field=0.0, **kw):
         """LinearProbe.fit_conformal on the GP logits, on the mean-field logits with `mean_field` > 0 (as fit_temperature)."""
-        self._mf = self._factor(mean_field)
-        try:
+        with self._mean_field(mean_field):
             return super().fit_conformal(loader, alpha, **kw)
-        finally:
-            self._mf = 0.0
 
     def evaluate_conformal(self, loader, sizes=False, temperature=None, mean_field=0.0):
         """LinearProbe.evaluate_conformal on the GP logits, on the mean-field logits with `mean_field` > 0."""
-        self._mf = self._factor(mean_field)
-        try:
+        with self._mean_field(mean_field):
             return super().evaluate_conformal(loader, sizes=sizes, temperature=temperature)
-        finally:
-            self._mf = 0.0
 
     def evaluate(self, loader, calibration=False, variance=False, mean_field=0.0, detection=False, ood_loader=None, temperature=None):
         """LinearProbe.evaluate on the GP logits; the precision matrix is not touched.  `variance`: the result gains `gp_var_mean`, the
@@ -243,33 +230,13 @@ class GPProbe(LinearProbe):
         (an addition: the reference has no such step); 0 leaves the logits as they are.  `detection`, `ood_loader`: as
         LinearProbe.evaluate, with the predictive variance as the column `gp_var` whatever `variance` says.  `temperature`: as
         LinearProbe.evaluate, applied behind the mean-field step; `gp_var` and `gp_var_mean` do not depend on it."""
-        self._mf, self._var_slabs = self._factor(mean_field), [] if variance else None
-        try:
-            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader, temperature=temperature)
-            if variance:
-                host = torch.cat(self._var_slabs).cpu().tolist() if self._var_slabs else []
-                stats["gp_var_mean"] = math.fsum(host) / len(host) if host else float("nan")
-        finally:
-            self._mf, self._var_slabs = 0.0, None
-        return stats
+        with self._mean_field(mean_field):
+            return self._evaluate_with_mean("gp_var_mean", variance, loader, calibration=calibration, detection=detection,
+                                            ood_loader=ood_loader, temperature=temperature)
 
     def evaluate_stability(self, loader, frames, noise, n_sequences=None, mean_field=0.0):
         """LinearProbe.evaluate_stability on the GP logits, on the mean-field logits with `mean_field` > 0."""
-        self._mf = self._factor(mean_field)
-        try:
+        with self._mean_field(mean_field):
             return super().evaluate_stability(loader, frames, noise, n_sequences=n_sequences)
-        finally:
-            self._mf = 0.0
 
-    # ---- optimizer state beside head.* in a checkpoint ----
     _OPT_KEYS = ("head._gp_output_layer.weight", "head._gp_input_normalize_layer.weight", "head._gp_input_normalize_layer.bias")
-
-    def optimizer_state_dict(self):
-        cut = lambda t: {k: t[lo:hi].view(shape).cpu().clone() for k, (_, lo, hi, shape) in zip(self._OPT_KEYS, self._views())}  # noqa: E731
-        return {"step": self.step_count, "exp_avg": cut(self.exp_avg), "exp_avg_sq": cut(self.exp_avg_sq)}
-
-    def load_optimizer_state_dict(self, sd):
-        self.step_count = int(sd["step"])
-        for arena, key in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
-            for k, (_, lo, hi, shape) in zip(self._OPT_KEYS, self._views()):
-                arena[lo:hi].view(shape).copy_(sd[key][k])

@@ -12,7 +12,6 @@ what the class's docstrings describe (edward2's MCSoftmaxDenseFA), not what its 
 call and takes the softmax over the batch axis (section 9.4).  Evaluation shares the draws across the batch under the fixed seed, so a
 prediction is a function of the image alone; training draws per row under a seed that changes with every step.
 """
-import ctypes as C
 import math
 
 import torch
@@ -21,6 +20,7 @@ import torch.nn as nn
 from .linear_probe import LinearProbe
 from .modeling_cyclical import _Holder
 from .native import check, cur_stream, f32, lib, ptr
+from .probe_util import ws_size
 
 __all__ = ["HetProbe"]
 
@@ -64,7 +64,7 @@ class HetProbe(LinearProbe):
         super().__init__(encoder, num_classes, smoothing=smoothing)
 
     # ---- arena plumbing ----
-    _KEYS = ("head._loc_layer.weight", "head._diag_layer.weight", "head._scale_layer.weight", "head._loc_layer.bias", "head._diag_layer.bias",
+    _OPT_KEYS = ("head._loc_layer.weight", "head._diag_layer.weight", "head._scale_layer.weight", "head._loc_layer.bias", "head._diag_layer.bias",
              "head._scale_layer.bias")
 
     def _views(self):
@@ -97,33 +97,14 @@ class HetProbe(LinearProbe):
                 lin = nn.Linear(Cd, rows)
                 getattr(h, name).weight.copy_(lin.weight)
                 getattr(h, name).bias.copy_(lin.bias)
-        self._het_batch, self._var_slabs = 0, None
 
-    def _rebind(self):
-        for p, lo, hi, shape in self._views():
-            p.data = self._arena[lo:hi].view(shape)
-            p.grad = self._grad_arena[lo:hi].view(shape)
-
-    def _apply(self, fn, recurse=True):
-        self._het_batch = 0
-        return super()._apply(fn, recurse)
-
-    def _buffers_for(self, B, calibration=False):
-        super()._buffers_for(B, calibration)
-        if B > self._het_batch:
-            K, R, dev = self.num_classes, self.num_factors, self._arena.device
-            ws = max(lib().uvit_op_het_mc_ws_bytes(B, S, K, R) for S in (self.train_mc_samples, self.test_mc_samples))
-            if ws < 0:
-                check(int(ws), "uvit_op_het_mc_ws_bytes")
-            z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
-            self._lin, self._dlin, self._p, self._pvar, self._het_scratch = z(B, self._rows), z(B, self._rows), z(B, K), z(B, K), z(ws // 4)
-            self._het_batch = B
-        return self._buf_batch
+    def _head_buffers_for(self, B):
+        K, R, dev = self.num_classes, self.num_factors, self._arena.device
+        ws = max(ws_size(lib().uvit_op_het_mc_ws_bytes, B, S, K, R) for S in (self.train_mc_samples, self.test_mc_samples))
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
+        self._lin, self._dlin, self._p, self._pvar, self._het_scratch = z(B, self._rows), z(B, self._rows), z(B, K), z(B, K), z(ws // 4)
 
     # ---- forward ----
-    def _bias_ptr(self, arena):
-        return C.c_void_p(arena.data_ptr() + 4 * self._n_decay)
-
     def _mc_into(self, B, samples, seed, share, pvar=False):
         """lin of self._feat[:B], then z into self._logits, p into self._p and, with `pvar`, the predictive variance into self._pvar."""
         K, Cd, R, L, s = self.num_classes, self.embed_dim, self.num_factors, lib(), cur_stream()
@@ -134,15 +115,11 @@ class HetProbe(LinearProbe):
 
     def _logits_into(self, B):
         """Evaluation: the draws are shared across the batch under the fixed seed, so a row's logits do not depend on its place."""
-        want, det = self._var_slabs is not None and not self._in_ood, self._det is not None
-        self._mc_into(B, self.test_mc_samples, self.seed, 1, pvar=want or det)
-        if want or det:
+        want = self._det is not None or (self._var_slabs is not None and not self._in_ood)
+        self._mc_into(B, self.test_mc_samples, self.seed, 1, pvar=want)
+        if want:     # the variance at the predicted class: a column of evaluate(detection=True), kept for evaluate(variance=True)'s mean
             pred = self._logits[:B].argmax(1, keepdim=True)
-            var = self._pvar[:B].gather(1, pred).squeeze(1)
-            if want:     # evaluate(variance=True): the variance at the predicted class stays on the device until the last batch
-                self._var_slabs.append(var)
-            if det:      # evaluate(detection=True): it is a column of the set-level store
-                self._det_column("het_var", var, B)
+            self._own_column("het_var", self._pvar[:B].gather(1, pred).squeeze(1), B, self._var_slabs, fresh=True)
 
     def predictive_variance(self, images):
         """(B, K) fp32: the variance over the Monte-Carlo samples of each class's softmax probability (compute_pred_variance)."""
@@ -180,23 +157,5 @@ class HetProbe(LinearProbe):
         LinearProbe.evaluate, with that variance as the column `het_var` whatever `variance` says.  `temperature`: as
         LinearProbe.evaluate, the post-hoc temperature on z (not the softmax temperature of the samples); `het_var` and `het_var_mean`
         are variances of probabilities formed before it and do not change."""
-        self._var_slabs = [] if variance else None
-        try:
-            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader, temperature=temperature)
-            if variance:
-                host = torch.cat(self._var_slabs).cpu().tolist() if self._var_slabs else []
-                stats["het_var_mean"] = math.fsum(host) / len(host) if host else float("nan")
-        finally:
-            self._var_slabs = None
-        return stats
-
-    # ---- optimizer state beside head.* in a checkpoint ----
-    def optimizer_state_dict(self):
-        cut = lambda t: {k: t[lo:hi].view(shape).cpu().clone() for k, (_, lo, hi, shape) in zip(self._KEYS, self._views())}  # noqa: E731
-        return {"step": self.step_count, "exp_avg": cut(self.exp_avg), "exp_avg_sq": cut(self.exp_avg_sq)}
-
-    def load_optimizer_state_dict(self, sd):
-        self.step_count = int(sd["step"])
-        for arena, key in ((self.exp_avg, "exp_avg"), (self.exp_avg_sq, "exp_avg_sq")):
-            for k, (_, lo, hi, shape) in zip(self._KEYS, self._views()):
-                arena[lo:hi].view(shape).copy_(sd[key][k])
+        return self._evaluate_with_mean("het_var_mean", variance, loader, calibration=calibration, detection=detection, ood_loader=ood_loader,
+                                        temperature=temperature)

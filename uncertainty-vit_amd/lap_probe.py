@@ -26,6 +26,7 @@ import torch
 from . import native
 from .linear_probe import LinearProbe
 from .native import check, cur_stream, lib, ptr
+from .probe_util import labelled_batches, workspace
 
 __all__ = ["LaplaceProbe", "marglik_grid", "log_marglik", "choose_prior_precision"]
 
@@ -81,7 +82,7 @@ class LaplaceProbe(LinearProbe):
             raise ValueError(f"the Laplace ops take an embed dim that is a multiple of 4 in [4, {LAP_MAX_C}] and 2 .. {LAP_MAX_K} classes, "
                              f"got {Cd} and {K}")
         super().__init__(encoder, num_classes, smoothing=smoothing, init_scale=init_scale)
-        self._lap_batch, self._lap_slabs = 0, None
+        self._lap_batch = 0
         self.set_laplace(None)
 
     # ---- state ----
@@ -125,20 +126,17 @@ class LaplaceProbe(LinearProbe):
 
     def _lap_buffers_for(self, B):
         if B > self._lap_batch:
-            K, Cd, dev, L = self.num_classes, self.embed_dim, self._arena.device, lib()
-            fws, vws = L.uvit_op_lap_factors_ws_bytes(B, Cd, K), L.uvit_op_lap_variance_ws_bytes(B, Cd, K)
-            if fws < 0 or vws < 0:
-                check(int(min(fws, vws)), "uvit_op_lap_*_ws_bytes")
-            self._lap_ws = torch.empty(int(max(fws, vws)), dtype=torch.uint8, device=dev)
+            K, Cd, dev = self.num_classes, self.embed_dim, self._arena.device
+            for query in (lib().uvit_op_lap_factors_ws_bytes, lib().uvit_op_lap_variance_ws_bytes):      # one workspace for both ops
+                workspace(self, "_lap_ws", dev, query, B, Cd, K, name="uvit_op_lap_*_ws_bytes")
             self._lap_var = torch.zeros(B, K, dtype=F64, device=dev)
             self._lap_col = torch.zeros(B, dtype=torch.float32, device=dev)
             self._lap_batch = B
 
     def _install(self, A, G_sum, sums, prior, head=None):
         """Host float64 factors -> eigen-decompositions, the prior precision, the uploads and uvit_op_lap_prepare."""
+        self._need_gpu("the Laplace probe runs")
         dev = self._arena.device
-        if dev.type != "cuda":
-            raise native.UvitError("the Laplace probe runs as HIP kernels: move the encoder and the probe to a GPU (no CPU fallback)")
         K, D = self.num_classes, self.embed_dim + 1
         A, G_sum, sums = (torch.as_tensor(t, dtype=F64).cpu().contiguous() for t in (A, G_sum, sums))
         if tuple(A.shape) != (D, D) or tuple(G_sum.shape) != (K, K) or tuple(sums.shape) != (3,):
@@ -185,14 +183,7 @@ class LaplaceProbe(LinearProbe):
         self.set_laplace(None)
         K, Cd = self.num_classes, self.embed_dim
         D, acc = Cd + 1, None
-        for item in loader:
-            images, labels = item
-            if isinstance(images, (tuple, list)):
-                images = images[0]
-            B = self._features(images)
-            if torch.is_tensor(labels) and not labels.is_cuda:
-                labels = labels.to(images.device, non_blocking=True)
-            labels = self._labels(labels, B)
+        for images, labels, B in labelled_batches(self, loader):
             if acc is None:
                 acc = torch.zeros(D * D + K * K + 4, dtype=F64, device=images.device)        # A | G_sum | sums: one allocation, one read
             self._lap_buffers_for(B)
@@ -240,10 +231,7 @@ class LaplaceProbe(LinearProbe):
         self._variance_into(B)
         check(lib().uvit_op_lap_probit(ptr(self._logits), K, ptr(self._lap_var), C.c_double(PROBIT_FACTOR), ptr(self._logits), K,
                                        ptr(self._lap_col), B, K, cur_stream()), "uvit_op_lap_probit")
-        if self._det is not None:                # evaluate(detection=True): the variance of the predicted class is a column of the store
-            self._det_column("lap_var", self._lap_col, B)
-        if self._lap_slabs is not None and not self._in_ood:
-            self._lap_slabs.append(self._lap_col[:B].clone())
+        self._own_column("lap_var", self._lap_col, B, self._var_slabs)      # the variance of the predicted class
 
     def predictive_variance(self, images):
         """(B, K) float64 on the device: the diagonal of J (G (x) A + tau I)^-1 J^T at the images' features."""
@@ -260,12 +248,5 @@ class LaplaceProbe(LinearProbe):
         the class the unscaled logits predict) and, with `variance`, the result gains `lap_var_mean`, the mean of that column over
         the evaluation set, from per-batch device slabs read after the last batch.  Without a fit: LinearProbe.evaluate's launches
         and result."""
-        self._lap_slabs = [] if variance and self._lap is not None else None
-        try:
-            stats = super().evaluate(loader, calibration=calibration, detection=detection, ood_loader=ood_loader, temperature=temperature)
-            if self._lap_slabs is not None:
-                host = torch.cat(self._lap_slabs).cpu().tolist() if self._lap_slabs else []
-                stats["lap_var_mean"] = math.fsum(host) / len(host) if host else float("nan")
-        finally:
-            self._lap_slabs = None
-        return stats
+        return self._evaluate_with_mean("lap_var_mean", variance and self._lap is not None, loader, calibration=calibration,
+                                        detection=detection, ood_loader=ood_loader, temperature=temperature)
