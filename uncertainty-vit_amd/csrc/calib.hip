@@ -16,30 +16,19 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 
 #define CALIB_MAX_B 1024
 #define CALIB_MAX_BINS 64
 #define TACE_THREADS 1024    // 16 waves: the sorting network is a chain of LDS round trips, hidden by waves and by nothing else
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double calib_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
 
 // 1 when any label lies outside [0, K); every lane of the wave gets the answer
 __device__ __forceinline__ int any_bad_label(const int64_t* __restrict__ labels, int B, int K, int lane) {
     int bad = 0;
     for (int b = lane; b < B; b += 64) {
         const int64_t y = labels[b];
-        bad |= !(y >= 0 && y < (int64_t)K);
+        bad |= !label_ok(y, K);
     }
     return __any(bad) ? 1 : 0;
 }
@@ -47,7 +36,7 @@ __device__ __forceinline__ int any_bad_label(const int64_t* __restrict__ labels,
 // ---- softmax: fp32, max-shifted, one wave per row; lane l adds its terms k = l, l + 64, ... in ascending order, then the xor tree ----
 __global__ __launch_bounds__(256)
 void calib_softmax_kernel(const float* __restrict__ logits, float* __restrict__ probs, int B, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* z = logits + (size_t)b * K;
     float* p = probs + (size_t)b * K;
@@ -66,11 +55,11 @@ void calib_softmax_kernel(const float* __restrict__ logits, float* __restrict__ 
 __global__ __launch_bounds__(256)
 void calib_conf_rows_kernel(const float* __restrict__ probs, const int64_t* __restrict__ labels, float* __restrict__ row_conf,
                             int* __restrict__ row_pred_correct, double* __restrict__ row_nll, int B, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* p = probs + (size_t)b * K;
     const int64_t y = labels[b];
-    const bool valid = y >= 0 && y < (int64_t)K;
+    const bool valid = label_ok(y, K);
     float best = -INFINITY;
     int bi = 0x7FFFFFFF;
     double s = 0.0;
@@ -79,18 +68,13 @@ void calib_conf_rows_kernel(const float* __restrict__ probs, const int64_t* __re
         s += (double)v;
         if (v > best) { best = v; bi = k; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    s = wave_sum_d(s);
+    WAVE_ARGMAX(best, bi);
+    s = wave_sum(s);
     if (lane == 0) {
         const double eps = 1.1920928955078125e-07;       // torch.finfo(torch.float32).eps
         double q = (valid ? (double)p[y] : 0.0) / s;
         q = q < eps ? eps : (q > 1.0 - eps ? 1.0 - eps : q);
-        row_nll[b] = valid ? -log(q) : calib_nan();
+        row_nll[b] = valid ? -log(q) : quiet_nan();
         row_conf[b] = best;
         row_pred_correct[b] = bi;
         row_pred_correct[B + b] = (valid && (int64_t)bi == y) ? 1 : 0;
@@ -133,12 +117,12 @@ void calib_conf_bins_kernel(const float* __restrict__ row_conf, const int* __res
     }
     const int bad = any_bad_label(labels, B, K, lane);
     double nll = 0.0;
-    for (int b0 = 0; b0 < B; b0 += 64) nll += wave_sum_d(b0 + lane < B ? row_nll[b0 + lane] : 0.0);
+    for (int b0 = 0; b0 < B; b0 += 64) nll += wave_sum(b0 + lane < B ? row_nll[b0 + lane] : 0.0);
     __syncthreads();
     if (lane == 0) {
         double ece = 0.0;
         for (int i = 0; i < n_bins; ++i) ece += score[i];
-        ece_nll[0] = bad ? calib_nan() : ece;
+        ece_nll[0] = bad ? quiet_nan() : ece;
         ece_nll[1] = nll / (double)B;
     }
 }
@@ -151,9 +135,7 @@ void calib_conf_bins_kernel(const float* __restrict__ row_conf, const int* __res
 // starts at or after i * bin_n, so the owner of (class, bin) walks it once, ascending: equal values commute exactly, hence the sum
 // does not depend on how the network ordered ties.  Class value = sum over bins in bin order, one owner thread per class. ----
 __device__ __forceinline__ double tace_key_value(unsigned long long key) {
-    unsigned int u = (unsigned int)(key >> 32);
-    u ^= (u >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-    return (double)__uint_as_float(u);
+    return (double)key32_value((unsigned int)(key >> 32));
 }
 
 __global__ __launch_bounds__(TACE_THREADS)
@@ -167,9 +149,7 @@ void calib_tace_kernel(const float* __restrict__ probs, const int64_t* __restric
         if (j < B && c < K) {
             const float p = probs[(size_t)j * K + c];
             const float v = ((double)p < thr) ? 0.f : p;
-            unsigned int u = __float_as_uint(v);
-            u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;   // unsigned order of u = numeric order of v
-            key = ((unsigned long long)u << 32) | (unsigned long long)(labels[j] == (int64_t)c);
+            key = ((unsigned long long)key32(v) << 32) | (unsigned long long)(labels[j] == (int64_t)c);
         }
         keys[idx] = key;
     }
@@ -178,10 +158,8 @@ void calib_tace_kernel(const float* __restrict__ probs, const int64_t* __restric
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int idx = tid; idx < ((P >> 1) << cg_shift); idx += TACE_THREADS) {
                 const int q = idx >> cg_shift, cc = idx & cmask;
-                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;
-                const bool asc = (i & k) == 0;
-                const unsigned long long a = keys[(i << cg_shift) + cc], b = keys[(l << cg_shift) + cc];
-                if ((a > b) == asc) { keys[(i << cg_shift) + cc] = b; keys[(l << cg_shift) + cc] = a; }
+                const int i = BITONIC_LO(q, j), l = i | j;
+                BITONIC_CMPX_AT(keys, (i << cg_shift) + cc, (l << cg_shift) + cc, (i & k) == 0);
             }
             __syncthreads();
         }
@@ -225,8 +203,8 @@ void calib_tace_mean_kernel(const double* __restrict__ per_class, const int64_t*
     const int lane = threadIdx.x;
     const int bad = any_bad_label(labels, B, K, lane);
     double acc = 0.0;
-    for (int c0 = 0; c0 < K; c0 += 64) acc += wave_sum_d(c0 + lane < K ? per_class[c0 + lane] : 0.0);
-    if (lane == 0) *tace = bad ? calib_nan() : acc / (double)K;
+    for (int c0 = 0; c0 < K; c0 += 64) acc += wave_sum(c0 + lane < K ? per_class[c0 + lane] : 0.0);
+    if (lane == 0) *tace = bad ? quiet_nan() : acc / (double)K;
 }
 
 // ---- AUROC, rows: one wave per sample i walks column y_i.  u2_i = sum over j with y_j != y_i of 2 [p_i > p_j] + [p_i == p_j]
@@ -234,10 +212,10 @@ void calib_tace_mean_kernel(const double* __restrict__ per_class, const int64_t*
 // u2 | n_pos | first.  A row with a label outside [0, K) writes zeros and reads no probability. ----
 __global__ __launch_bounds__(256)
 void calib_auroc_rows_kernel(const float* __restrict__ probs, const int64_t* __restrict__ labels, int* __restrict__ rows, int B, int K) {
-    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), i = WavePerRow::row();
     if (i >= B) return;
     const int64_t y = labels[i];
-    const bool valid = y >= 0 && y < (int64_t)K;
+    const bool valid = label_ok(y, K);
     int u2 = 0, npos = 0, earlier = 0;
     if (valid) {
         const double pi = (double)probs[(size_t)i * K + y];
@@ -251,7 +229,7 @@ void calib_auroc_rows_kernel(const float* __restrict__ probs, const int64_t* __r
             }
         }
     }
-    u2 = wave_sum_i(u2); npos = wave_sum_i(npos); earlier = wave_sum_i(earlier);
+    u2 = wave_sum(u2); npos = wave_sum(npos); earlier = wave_sum(earlier);
     if (lane == 0) {
         rows[i] = u2;
         rows[B + i] = npos;
@@ -278,11 +256,11 @@ void calib_auroc_finish_kernel(const int* __restrict__ rows, const int64_t* __re
                 first = rows[2 * B + i];
             }
         }
-        sum += wave_sum_d(term);
-        count += wave_sum_i(first);
+        sum += wave_sum(term);
+        count += wave_sum(first);
     }
     if (lane == 0) {
-        out[0] = bad ? calib_nan() : sum;
+        out[0] = bad ? quiet_nan() : sum;
         out[1] = (double)count;
     }
 }
@@ -293,7 +271,7 @@ static inline bool calib_shape_ok(int B, int K) { return B >= 1 && B <= CALIB_MA
 extern "C" int uvit_op_calib_softmax(const float* logits, float* probs, int B, int K, uvit_stream stream) {
     if (!logits || !probs) return UVIT_ERR_ARG;
     if (!calib_shape_ok(B, K)) return UVIT_ERR_SHAPE;
-    hipLaunchKernelGGL(calib_softmax_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, probs, B, K);
+    hipLaunchKernelGGL(calib_softmax_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, (hipStream_t)stream, logits, probs, B, K);
     return uvit_check_launch();
 }
 
@@ -305,7 +283,7 @@ extern "C" int uvit_op_calib_confidence(const float* probs, const int64_t* label
     CalibBounds bd;
     for (int i = 0; i <= CALIB_MAX_BINS; ++i) bd.v[i] = i <= n_bins ? bounds[i] : 0.0;      // travels by value: the call stays asynchronous
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(calib_conf_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, s, probs, labels, row_conf, (int*)row_pred_correct, row_nll, B, K);
+    hipLaunchKernelGGL(calib_conf_rows_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, s, probs, labels, row_conf, (int*)row_pred_correct, row_nll, B, K);
     hipLaunchKernelGGL(calib_conf_bins_kernel, dim3(1), dim3(64), 0, s, (const float*)row_conf, (const int*)row_pred_correct,
                        (const double*)row_nll, labels, bd, n_bins, positional_acc, bin_table, ece_nll, B, K);
     return uvit_check_launch();
@@ -330,7 +308,7 @@ extern "C" int uvit_op_calib_auroc(const float* probs, const int64_t* labels, in
     if (!probs || !labels || !rows || !out) return UVIT_ERR_ARG;
     if (!calib_shape_ok(B, K)) return UVIT_ERR_SHAPE;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(calib_auroc_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, s, probs, labels, (int*)rows, B, K);
+    hipLaunchKernelGGL(calib_auroc_rows_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, s, probs, labels, (int*)rows, B, K);
     hipLaunchKernelGGL(calib_auroc_finish_kernel, dim3(1), dim3(64), 0, s, (const int*)rows, labels, out, B, K);
     return uvit_check_launch();
 }

@@ -28,7 +28,7 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 
 #define CP_MAX_N (1 << 20)
 #define CP_MAX_K 4096
@@ -38,8 +38,7 @@
 #define CP_LAC 0
 #define CP_APS 1
 #define CP_RAPS 2
-#define CP_SKIP_BITS 0x7FF8000000000000ULL      // the score of a row with a non-finite logit
-#define CP_BAD_BITS 0x7FF8000000000BADULL       // the score of a row whose label is outside [0, K)
+#define CP_BAD_BITS 0x7FF8000000000BADULL       // the score of a row whose label is outside [0, K); a non-finite logit: quiet_nan()
 #define CP_PASSES 8              // radix select: eight bits per pass, from the top byte down
 #define CP_GLOBAL 4              // counters: rows used | rows skipped | bad labels | 0, then CP_LEVEL per level, then the classes
 #define CP_LEVEL 20              // covered | size sum | empty | singleton | max size | 7 bins: rows | 7 bins: covered | 0
@@ -50,16 +49,6 @@
 
 typedef unsigned long long u64;
 
-__device__ __forceinline__ double cp_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int cp_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ double cp_bits(u64 b) { return __longlong_as_double((long long)b); }
 
 // The score of the class with rank o: `before` = sum of the e_i ranked before it, e its own exponential, S the row's sum.
@@ -78,16 +67,16 @@ __device__ __forceinline__ CpRow cp_row(const float* __restrict__ z, int K, int6
     bool ok = true;
     for (int k = lane; k < K; k += 64) {
         const float v = z[k];
-        ok = ok && fabsf(v) < INFINITY;                                   // false for NaN and for +-inf
+        ok = ok && finite32(v);
         m = fmaxf(m, v);
     }
     m = wave_max(m);
-    const bool inside = y >= 0 && y < (int64_t)K;
+    const bool inside = label_ok(y, K);
     r.m = m;
     r.state = !inside ? 2 : (__any(!ok) ? 1 : 0);                         // uniform over the wave
     if (r.state) {
-        r.S = cp_bits(CP_SKIP_BITS);
-        r.score = cp_bits(r.state == 2 ? CP_BAD_BITS : CP_SKIP_BITS);
+        r.S = quiet_nan();
+        r.score = cp_bits(r.state == 2 ? CP_BAD_BITS : QUIET_NAN_BITS);
         return r;
     }
     const float zy = z[y];
@@ -99,9 +88,9 @@ __device__ __forceinline__ CpRow cp_row(const float* __restrict__ z, int K, int6
         S += e;
         if (v > zy || (v == zy && k < (int)y)) { before += e; ++ahead; }
     }
-    S = cp_wave_sum(S);
-    before = cp_wave_sum(before);
-    ahead = cp_wave_sum(ahead);
+    S = wave_sum(S);
+    before = wave_sum(before);
+    ahead = wave_sum(ahead);
     r.S = S;
     r.score = cp_score_of(kind, before, (double)expf(zy - m), (double)u, S, ahead + 1, lam, kreg);
     return r;
@@ -180,7 +169,7 @@ void cp_select_kernel(const uint32_t* __restrict__ hist, int N, int A, int pass,
         const int64_t bad = (int64_t)glob[1];
         const double kd = ceil((double)(n + 1) * lv.one_minus[a]);
         if (bad > 0) {
-            for (int q = 0; q < CP_TABLE; ++q) t[q] = cp_bits(CP_SKIP_BITS);
+            for (int q = 0; q < CP_TABLE; ++q) t[q] = quiet_nan();
             state[a * 4 + 2] = 2;
             return;
         }
@@ -274,9 +263,8 @@ void cp_sets_kernel(const float* __restrict__ logits, int64_t ld, const int64_t*
         for (int k = 2; k <= KP; k <<= 1)
             for (int j = k >> 1; j > 0; j >>= 1) {
                 for (int p = tid; p < KP / 2; p += T) {
-                    const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
-                    const u64 x = key[i], w = key[l];
-                    if ((x > w) == ((i & k) == 0)) { key[i] = w; key[l] = x; }
+                    const int i = BITONIC_LO(p, j), l = i | j;
+                    BITONIC_CMPX_AT(key, i, l, (i & k) == 0);
                 }
                 __syncthreads();
             }
@@ -310,7 +298,7 @@ void cp_sets_kernel(const float* __restrict__ logits, int64_t ld, const int64_t*
     }
 #pragma unroll
     for (int a = 0; a < CP_MAX_A; ++a) {
-        const int w = cp_wave_sum(c[a]);
+        const int w = wave_sum(c[a]);
         if (lane == 0 && a < A && w) atomicAdd(&cnt[a], w);
     }
     __syncthreads();
@@ -357,7 +345,7 @@ void cp_finish_kernel(const u64* __restrict__ counters, double* __restrict__ tab
     }
     if (tid != 0) return;
     double* t = table + a * CP_TABLE;
-    const double n = (double)counters[0], nan = cp_bits(CP_SKIP_BITS), target = 1.0 - t[0];
+    const double n = (double)counters[0], nan = quiet_nan(), target = 1.0 - t[0];
     const bool good = counters[2] == 0 && counters[0] > 0 && t[1] == t[1];
     double sscv = 0.0;
     for (int b = 0; b < CP_BINS; ++b)
@@ -396,7 +384,7 @@ extern "C" int64_t uvit_op_cp_ws_bytes(int N, int A) {
 
 extern "C" int uvit_op_cp_quantile(const double* scores, int N, const double* alphas, int A, double* table, void* ws, int64_t ws_bytes,
                                    uvit_stream stream) {
-    if (!scores || !alphas || !table || !ws || ((uintptr_t)ws & 15)) return UVIT_ERR_ARG;
+    if (!scores || !alphas || !table || !ws || misaligned(ws, 16)) return UVIT_ERR_ARG;
     if (N < 1 || N > CP_MAX_N || A < 1 || A > CP_MAX_A) return UVIT_ERR_SHAPE;
     CpLevels lv;
     for (int a = 0; a < CP_MAX_A; ++a) {

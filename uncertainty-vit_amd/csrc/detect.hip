@@ -20,7 +20,7 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 
 #define DET_MAX_N (1 << 20)
 #define DET_MAX_S 16
@@ -33,25 +33,6 @@
 
 typedef unsigned long long det_key;
 
-__device__ __forceinline__ double det_wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int det_wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long det_wave_sum_ll(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int lo = __shfl_xor((int)(v & 0xFFFFFFFFll), o, 64), hi = __shfl_xor((int)(v >> 32), o, 64);
-        v += (long long)(((unsigned long long)(unsigned int)hi << 32) | (unsigned long long)(unsigned int)lo);
-    }
-    return v;
-}
-__device__ __forceinline__ double det_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
 __device__ __forceinline__ unsigned int det_image(det_key k) { return (unsigned int)(k >> 32); }
 
 // ---- rows: one wave per row of z (B, K).  m = max z (lowest index on ties), e_k = expf(z_k - m) in fp32, S = sum e_k and
@@ -60,7 +41,7 @@ __device__ __forceinline__ unsigned int det_image(det_key k) { return (unsigned 
 __global__ __launch_bounds__(256)
 void det_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, float* __restrict__ scores, int64_t ld, int64_t n0,
                      uint8_t* __restrict__ flags, int B, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* z = logits + (size_t)b * K;
     float best = -INFINITY;
@@ -69,12 +50,7 @@ void det_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict
         const float v = z[k];
         if (v > best) { best = v; bi = k; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
+    WAVE_ARGMAX(best, bi);
     double s = 0.0, t = 0.0;
     for (int k = lane; k < K; k += 64) {
         const float d = z[k] - best;
@@ -82,8 +58,8 @@ void det_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict
         s += (double)e;
         if (e != 0.f) t += (double)e * (double)d;
     }
-    s = det_wave_sum_d(s);
-    t = det_wave_sum_d(t);
+    s = wave_sum(s);
+    t = wave_sum(t);
     if (lane == 0) {
         const double ls = log(s);
         double ent = ls - t / s;
@@ -94,7 +70,7 @@ void det_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict
         scores[2 * (size_t)ld + at] = (float)(-((double)best + ls));
         if (labels) {
             const int64_t y = labels[b];
-            flags[at] = !(y >= 0 && y < (int64_t)K) ? 2 : ((int64_t)bi != y ? 1 : 0);
+            flags[at] = !label_ok(y, K) ? 2 : ((int64_t)bi != y ? 1 : 0);
         }
     }
 }
@@ -110,19 +86,12 @@ void det_column_kernel(const void* __restrict__ src, int is_double, int64_t stri
 // ---- keys ----
 __device__ __forceinline__ det_key det_make_key(const float* __restrict__ col, const uint8_t* __restrict__ flags, int gi, int N) {
     if (gi >= N) return ~0ull;
-    float v = col[gi];
+    const float v = col[gi];
     const unsigned int f = flags[gi];
     const bool nan = v != v;
-    if (v == 0.f) v = 0.f;                                   // -0 ranks as +0
-    unsigned int u = __float_as_uint(v);
-    u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;               // unsigned order of u = numeric order of v
-    if (nan) u = DET_NAN_IMAGE;
+    const unsigned int u = nan ? DET_NAN_IMAGE : key32(fold_zero(v));                 // -0 ranks as +0
     const unsigned int low = ((unsigned int)gi << 2) | (f >= 2u ? 2u : 0u) | ((f == 1u && !nan) ? 1u : 0u);
     return ((det_key)u << 32) | (det_key)low;
-}
-
-__device__ __forceinline__ void det_cmpx(det_key& a, det_key& b, bool asc) {
-    if ((a > b) == asc) { const det_key t = a; a = b; b = t; }
 }
 
 // ---- sort, in LDS: workgroup x of column y owns the Lc = min(P, 4096) keys behind x * Lc and runs the levels k_lo .. k_hi of the
@@ -146,16 +115,15 @@ void det_sort_local_kernel(const float* __restrict__ scores, int64_t ld, const u
                 for (int t = tid; t < (Lc >> 2); t += DET_SORT_THREADS) {
                     const bool asc = ((base + 4 * t) & k) == 0;
                     det_key x0 = sk[4 * t], x1 = sk[4 * t + 1], x2 = sk[4 * t + 2], x3 = sk[4 * t + 3];
-                    det_cmpx(x0, x2, asc); det_cmpx(x1, x3, asc); det_cmpx(x0, x1, asc); det_cmpx(x2, x3, asc);
+                    cmpx(x0, x2, asc); cmpx(x1, x3, asc); cmpx(x0, x1, asc); cmpx(x2, x3, asc);
                     sk[4 * t] = x0; sk[4 * t + 1] = x1; sk[4 * t + 2] = x2; sk[4 * t + 3] = x3;
                 }
                 __syncthreads();
                 break;
             }
             for (int q = tid; q < (Lc >> 1); q += DET_SORT_THREADS) {
-                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;
-                det_key a = sk[i], b = sk[l];
-                if ((a > b) == (((base + i) & k) == 0)) { sk[i] = b; sk[l] = a; }
+                const int i = BITONIC_LO(q, j), l = i | j;
+                BITONIC_CMPX_AT(sk, i, l, ((base + i) & k) == 0);
             }
             __syncthreads();
         }
@@ -169,9 +137,8 @@ void det_sort_global_kernel(det_key* __restrict__ keys, int P, int k, int j) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= (P >> 1)) return;
     det_key* kcol = keys + (size_t)blockIdx.y * P;
-    const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;
-    const det_key a = kcol[i], b = kcol[l];
-    if ((a > b) == ((i & k) == 0)) { kcol[i] = b; kcol[l] = a; }
+    const int i = BITONIC_LO(q, j), l = i | j;
+    BITONIC_CMPX_AT(kcol, i, l, (i & k) == 0);
 }
 
 // ---- the sorted set: positions [0, n) hold the numbers ascending, [n, N) the NaN rows by index, [N, P) the padding.  A segment is
@@ -192,8 +159,8 @@ void det_seg_sums_kernel(const det_key* __restrict__ keys, int* __restrict__ seg
             bad += (low >> 1) & 1u;
         }
     }
-    pos = det_wave_sum_i(pos);
-    bad = det_wave_sum_i(bad);
+    pos = wave_sum(pos);
+    bad = wave_sum(bad);
     if ((tid & 63) == 0) { red[0][tid >> 6] = pos; red[1][tid >> 6] = bad; }
     __syncthreads();
     if (tid == 0) {
@@ -308,9 +275,9 @@ void det_metric_parts_kernel(const det_key* __restrict__ keys, const int* __rest
         }
         before = u;
     }
-    num = det_wave_sum_ll(num);
-    ap = det_wave_sum_d(ap);
-    rc = det_wave_sum_d(rc);
+    num = wave_sum(num);
+    ap = wave_sum(ap);
+    rc = wave_sum(rc);
     if ((tid & 63) == 0) { redl[tid >> 6] = num; redd[0][tid >> 6] = ap; redd[1][tid >> 6] = rc; }
     __syncthreads();
     if (tid == 0) {
@@ -337,10 +304,10 @@ void det_metric_finish_kernel(const int* __restrict__ meta, const double* __rest
     }
     const bool ranked = Ptot > 0 && Nn > 0 && !bad;
     double* o = out + 8 * (size_t)s;
-    o[0] = ranked ? (double)num / (2.0 * (double)Ptot * (double)Nn) : det_nan();
-    o[1] = (Ptot > 0 && !bad) ? ap : det_nan();
-    o[2] = ranked ? (double)meta[4 * s + 3] / (double)Nn : det_nan();
-    o[3] = (n > 0 && !bad) ? rc / (double)n : det_nan();
+    o[0] = ranked ? (double)num / (2.0 * (double)Ptot * (double)Nn) : quiet_nan();
+    o[1] = (Ptot > 0 && !bad) ? ap : quiet_nan();
+    o[2] = ranked ? (double)meta[4 * s + 3] / (double)Nn : quiet_nan();
+    o[3] = (n > 0 && !bad) ? rc / (double)n : quiet_nan();
     o[4] = (double)n; o[5] = (double)Ptot; o[6] = (double)(N - n); o[7] = 0.0;
 }
 
@@ -354,7 +321,7 @@ static inline DetLayout det_layout(int N, int S) {
     d.Lc = d.P < DET_CHUNK ? d.P : DET_CHUNK;
     d.nseg = (d.P + DET_SEG - 1) / DET_SEG;
     size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t here = at; at += (bytes + 15) / 16 * 16; return here; };
+    auto take = [&at](size_t bytes) { const size_t here = at; at += align16(bytes); return here; };
     d.keys = take((size_t)S * d.P * sizeof(det_key));
     d.prefix = take((size_t)S * d.P * sizeof(int));
     d.segsum = take((size_t)S * d.nseg * 2 * sizeof(int));
@@ -371,7 +338,7 @@ extern "C" int uvit_op_detect_rows(const float* logits, const int64_t* labels, f
                                    uvit_stream stream) {
     if (!logits || !scores || (labels && !flags)) return UVIT_ERR_ARG;
     if (B < 1 || K < 1 || n0 < 0 || ld < n0 + (int64_t)B) return UVIT_ERR_SHAPE;
-    hipLaunchKernelGGL(det_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, labels, scores, ld, n0, flags, B, K);
+    hipLaunchKernelGGL(det_rows_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, (hipStream_t)stream, logits, labels, scores, ld, n0, flags, B, K);
     return uvit_check_launch();
 }
 
@@ -389,7 +356,7 @@ extern "C" int64_t uvit_op_detect_ws_bytes(int N, int S) {
 
 extern "C" int uvit_op_detect_metrics(const float* scores, int64_t ld, const uint8_t* flags, int N, int S, int32_t* order, double* out, void* ws,
                                       int64_t ws_bytes, uvit_stream stream) {
-    if (!scores || !flags || !out || !ws || ((uintptr_t)ws & 15)) return UVIT_ERR_ARG;
+    if (!scores || !flags || !out || !ws || misaligned(ws, 16)) return UVIT_ERR_ARG;
     if (!det_set_ok(N, S) || ld < (int64_t)N) return UVIT_ERR_SHAPE;
     const DetLayout d = det_layout(N, S);
     if (ws_bytes < (int64_t)d.total) return UVIT_ERR_WORKSPACE;

@@ -20,7 +20,7 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 
 #define ENS_MAX_M 16             // the combination keeps (max, lse) and the running argmax of every member in registers
 #define ENS_CLIP_THREADS 1024
@@ -41,17 +41,6 @@ void ens_bag_weights_kernel(float* __restrict__ w, size_t n, uint32_t key) {
     if (i < n) w[i] = ens_bag_weight(key, (uint32_t)i);
 }
 
-__device__ __forceinline__ int ens_wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double ens_wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- criterion: one wave per (row, member) pair r = b M + m, whose K logits start at lin + r K; probe_ce_kernel's row
 // body, except that lse - v is formed as log(sum) - (v - max).
 // row_loss holds the unweighted loss; the weight enters dlin here and the member's mean in the kernel below. ----
@@ -64,7 +53,7 @@ void ens_ce_kernel(const float* __restrict__ lin, const int64_t* __restrict__ la
     const int b = (int)(r / M), m = (int)(r % M);
     const float* z = lin + r * K;
     const int64_t y = labels[b];
-    const bool valid = y >= 0 && y < (int64_t)K;
+    const bool valid = y >= 0 && y < (int64_t)K;     // spelled out, as in probe_ce_kernel
     float mx = -INFINITY;
     for (int k = lane; k < K; k += 64) mx = fmaxf(mx, z[k]);
     mx = wave_max(mx);
@@ -79,7 +68,7 @@ void ens_ce_kernel(const float* __restrict__ lin, const int64_t* __restrict__ la
         ge += (v >= zy) && k != (int)y;
     }
     se = wave_sum(se); sz = wave_sum(sz);
-    gt = ens_wave_sum_int(gt); ge = ens_wave_sum_int(ge);
+    gt = wave_sum(gt); ge = wave_sum(ge);
     // lse - v is formed as log(se) - (v - mx): the row maximum cancels exactly instead of costing an ulp of lse
     const float lg = logf(se);
     const float nan = __uint_as_float(0x7FC00000u);
@@ -188,7 +177,7 @@ void ens_clip_kernel(float* __restrict__ grad, float* __restrict__ norms, int M,
 // var_pred and disagreement at k*.  p_m[k] = expf((lin - max_m) - log sum_m) in fp32, widened; every sum and logarithm of unc in double. ----
 __global__ __launch_bounds__(256)
 void ens_combine_kernel(const float* __restrict__ lin, int mode, float* __restrict__ z, double* __restrict__ unc, int B, int M, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* row = lin + (size_t)b * M * K;
     float mxs[ENS_MAX_M], lse[ENS_MAX_M];          // lse_m = mxs[m] + lse[m]; x - lse_m is formed as (x - mxs[m]) - lse[m]
@@ -253,34 +242,23 @@ void ens_combine_kernel(const float* __restrict__ lin, int mode, float* __restri
     }
     if (!unc) return;
     // argmax across the lanes: the larger value, the lower index on ties (a lane without a class holds -inf and the largest index)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(besti, o, 64);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-    }
+    WAVE_ARGMAX(best, besti);
     int differ = 0;
 #pragma unroll
     for (int m = 0; m < ENS_MAX_M; ++m) {
         if (m < M) {
             float v = mbest[m];
             int i = mbesti[m];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(v, o, 64);
-                const int oi = __shfl_xor(i, o, 64);
-                if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-            }
+            WAVE_ARGMAX(v, i);
             differ += i != besti;
         }
     }
-    h_total = ens_wave_sum_f64(h_total);
-    h_member = ens_wave_sum_f64(h_member);
+    h_total = wave_sum(h_total);
+    h_member = wave_sum(h_member);
     if (lane != 0) return;
     double* out = unc + (size_t)b * 5;
     if (has_nan || besti >= K) {
-        const double nan = __longlong_as_double(0x7FF8000000000000LL);
-        for (int i = 0; i < 5; ++i) out[i] = nan;
+        for (int i = 0; i < 5; ++i) out[i] = quiet_nan();
         return;
     }
     double pk[ENS_MAX_M], pbar = 0.0, var = 0.0;
@@ -329,7 +307,7 @@ extern "C" int uvit_op_ens_ce(const float* lin, const int64_t* labels, const flo
 extern "C" int uvit_op_ens_clip(float* grad, float* norms, int M, int K, int C, float max_norm, uvit_stream stream) {
     if (!grad || !norms) return UVIT_ERR_ARG;
     if (K < 1 || M < 1 || M > ENS_MAX_M || C < 4 || (C % 4)) return UVIT_ERR_SHAPE;
-    if (((uintptr_t)grad & 15) == 0)
+    if (!misaligned(grad, 16))
         hipLaunchKernelGGL(ens_clip_kernel<true>, dim3(M), dim3(ENS_CLIP_THREADS), 0, (hipStream_t)stream, grad, norms, M, K, C, max_norm);
     else
         hipLaunchKernelGGL(ens_clip_kernel<false>, dim3(M), dim3(ENS_CLIP_THREADS), 0, (hipStream_t)stream, grad, norms, M, K, C, max_norm);
@@ -339,6 +317,6 @@ extern "C" int uvit_op_ens_clip(float* grad, float* norms, int M, int K, int C, 
 extern "C" int uvit_op_ens_combine(const float* lin, int mode, float* z, double* unc, int B, int M, int K, uvit_stream stream) {
     if (!lin || !z || (mode != 0 && mode != 1)) return UVIT_ERR_ARG;
     if (ens_bad_shape(B, M, K)) return UVIT_ERR_SHAPE;
-    hipLaunchKernelGGL(ens_combine_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, lin, mode, z, unc, B, M, K);
+    hipLaunchKernelGGL(ens_combine_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, (hipStream_t)stream, lin, mode, z, unc, B, M, K);
     return uvit_check_launch();
 }

@@ -15,7 +15,7 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 #include "rowwise.h"
 
 #define GT 64                // output tile edge: 256 threads with a 4 x 4 micro-tile each
@@ -218,11 +218,6 @@ void gp_ln_colsum_kernel(const float* __restrict__ dg, const float* __restrict__
 // shuffle tree and the sixteen waves are added in wave order.
 #define VB 4
 #define VT 1024
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(VT)
 void gp_variance_kernel(const float* __restrict__ phi, const double* __restrict__ Sigma, double ridge, double* __restrict__ var,
@@ -246,7 +241,7 @@ void gp_variance_kernel(const float* __restrict__ phi, const double* __restrict_
         for (int v = 0; v < VB; ++v) s[v] = fma(t[v], (double)ph[v][j], s[v]);
     }
 #pragma unroll
-    for (int v = 0; v < VB; ++v) s[v] = wave_sum_f64(s[v]);     // every wave takes part: threads without a column carry zeros
+    for (int v = 0; v < VB; ++v) s[v] = wave_sum(s[v]);     // every wave takes part: threads without a column carry zeros
     if (lane == 0) {
 #pragma unroll
         for (int v = 0; v < VB; ++v) red[wave][v] = s[v];
@@ -262,7 +257,7 @@ void gp_variance_kernel(const float* __restrict__ phi, const double* __restrict_
 // ---- mean field: out[b, k] = z[b, k] / sqrt(1 + factor var[b]) in double, rounded once to fp32; one wave per row; out may be z ----
 __global__ __launch_bounds__(256)
 void gp_mean_field_kernel(const float* logits, const double* __restrict__ var, double factor, float* out, int B, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const double den = sqrt(1.0 + factor * var[b]);
     const float* z = logits + (size_t)b * K;
@@ -331,6 +326,6 @@ extern "C" int uvit_op_gp_mean_field(const float* logits, const double* var, dou
                                      uvit_stream stream) {
     if (!logits || !var || !out || !(factor >= 0.0)) return UVIT_ERR_ARG;
     if (B < 1 || B > GP_MAX_B || K < 1) return UVIT_ERR_SHAPE;
-    hipLaunchKernelGGL(gp_mean_field_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, var, factor, out, B, K);
+    hipLaunchKernelGGL(gp_mean_field_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, (hipStream_t)stream, logits, var, factor, out, B, K);
     return uvit_check_launch();
 }

@@ -22,7 +22,7 @@
 #include <type_traits>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 
 #define HET_MAX_B 65535
 #define HET_MIN_K 3

@@ -16,7 +16,7 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 
 #define KNN_MAX_B 65535
 #define KNN_MAX_ROWS (1 << 22)
@@ -32,18 +32,12 @@
 #define KNN_LD 144           // bytes per LDS tile row: 128 + 16, so the 16 rows of a fragment read fall into 16 distinct bank groups
 #define KNN_TILE (KNN_QM * KNN_LD)
 
-__device__ __forceinline__ double knn_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- rows ----
 // One wave per row: |f|^2 in double (lane partial sums over ascending c, the xor tree), then (float)(f_c / sqrt(|f|^2)) to bf16 RNE.
 __global__ __launch_bounds__(256)
 void knn_rows_kernel(const float* __restrict__ feat, const int64_t* __restrict__ labels, bf16* __restrict__ out,
                      int* __restrict__ out_labels, int B, int C, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* f = feat + (size_t)b * C;
     double s = 0.0;
@@ -54,12 +48,12 @@ void knn_rows_kernel(const float* __restrict__ feat, const int64_t* __restrict__
         bad |= !isfinite(v);
         s = fma((double)v, (double)v, s);
     }
-    s = knn_wave_sum(s);
+    s = wave_sum(s);
     bad = __any(bad);
     int64_t y = 0;
     if (labels) {
         y = labels[b];
-        bad |= (y < 0 || y >= K) ? 1 : 0;
+        bad |= label_ok(y, K) ? 0 : 1;
     }
     bad |= !(s > 0.0);
     const double inv = 1.0 / sqrt(s);
@@ -349,7 +343,6 @@ void knn_scores_kernel(const float* __restrict__ sim, const int* __restrict__ id
 }
 
 // ---- launchers: arguments are validated before anything touches the device ----
-static inline bool knn_mis(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 static inline bool knn_bad_c(int C) { return C < 32 || (C % 32) || C > KNN_MAX_C; }
 static inline bool knn_bad_search(int B, int C, int N, int k, int slabs) {
     return B < 1 || B > KNN_MAX_B || knn_bad_c(C) || N < 1 || N > KNN_MAX_N || k < 1 || k > KNN_MAX_K || slabs < 0 || slabs > KNN_MAX_SLABS;
@@ -380,10 +373,10 @@ static int knn_slabs(int B, int N, int slabs) {
 extern "C" int uvit_op_knn_rows(const float* feat, const int64_t* labels, void* out, int32_t* out_labels, double* sums, int B, int C,
                                 int K, uvit_stream stream) {
     if (!feat || !out || !out_labels) return UVIT_ERR_ARG;
-    if (knn_mis(feat, 4) || knn_mis(labels, 8) || knn_mis(out, 16) || knn_mis(out_labels, 4) || knn_mis(sums, 8)) return UVIT_ERR_ARG;
+    if (misaligned(feat, 4) || misaligned(labels, 8) || misaligned(out, 16) || misaligned(out_labels, 4) || misaligned(sums, 8)) return UVIT_ERR_ARG;
     if (B < 1 || B > KNN_MAX_ROWS || knn_bad_c(C) || (labels && (K < 2 || K > KNN_MAX_CLASSES))) return UVIT_ERR_SHAPE;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(knn_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, s, feat, labels, (bf16*)out, out_labels, B, C, K);
+    hipLaunchKernelGGL(knn_rows_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, s, feat, labels, (bf16*)out, out_labels, B, C, K);
     if (sums) hipLaunchKernelGGL(knn_count_kernel, dim3(1), dim3(256), 0, s, (const int*)out_labels, sums, B);
     return uvit_check_launch();
 }
@@ -391,15 +384,15 @@ extern "C" int uvit_op_knn_rows(const float* feat, const int64_t* labels, void* 
 // workspace of uvit_op_knn_search: the slabs' unsorted lists, (B, slabs, k) 64-bit keys
 extern "C" int64_t uvit_op_knn_search_ws_bytes(int B, int C, int N, int k, int slabs) {
     if (knn_bad_search(B, C, N, k, slabs)) return UVIT_ERR_SHAPE;
-    return (((int64_t)B * knn_slabs(B, N, slabs) * k * 8) + 15) & ~(int64_t)15;
+    return align16((int64_t)B * knn_slabs(B, N, slabs) * k * 8);
 }
 
 extern "C" int uvit_op_knn_search(const void* query, const int32_t* query_valid, const void* bank, const int32_t* bank_labels, float* sim,
                                   int32_t* idx, int64_t ld, void* ws, int64_t ws_bytes, int B, int C, int N, int k, int slabs,
                                   uvit_stream stream) {
     if (!query || !query_valid || !bank || !bank_labels || !sim || !idx || !ws) return UVIT_ERR_ARG;
-    if (knn_mis(query, 16) || knn_mis(query_valid, 4) || knn_mis(bank, 16) || knn_mis(bank_labels, 4) || knn_mis(sim, 4) ||
-        knn_mis(idx, 4) || knn_mis(ws, 16))
+    if (misaligned(query, 16) || misaligned(query_valid, 4) || misaligned(bank, 16) || misaligned(bank_labels, 4) || misaligned(sim, 4) ||
+        misaligned(idx, 4) || misaligned(ws, 16))
         return UVIT_ERR_ARG;
     if (knn_bad_search(B, C, N, k, slabs) || ld < k) return UVIT_ERR_SHAPE;
     if (ws_bytes < uvit_op_knn_search_ws_bytes(B, C, N, k, slabs)) return UVIT_ERR_WORKSPACE;
@@ -421,8 +414,8 @@ extern "C" int uvit_op_knn_scores(const float* sim, const int32_t* idx, int64_t 
                                   int32_t* pred, double* votes, int64_t ldv, const int64_t* labels, int32_t* correct, int B, int k,
                                   int K, double temperature, uvit_stream stream) {
     if (!sim || !idx || !bank_labels || !knn || !pred) return UVIT_ERR_ARG;
-    if (knn_mis(sim, 4) || knn_mis(idx, 4) || knn_mis(bank_labels, 4) || knn_mis(knn, 4) || knn_mis(pred, 4) || knn_mis(votes, 8) ||
-        knn_mis(labels, 8) || knn_mis(correct, 4))
+    if (misaligned(sim, 4) || misaligned(idx, 4) || misaligned(bank_labels, 4) || misaligned(knn, 4) || misaligned(pred, 4) || misaligned(votes, 8) ||
+        misaligned(labels, 8) || misaligned(correct, 4))
         return UVIT_ERR_ARG;
     if (!(temperature > 0.0) || !(temperature < INFINITY)) return UVIT_ERR_ARG;
     if (B < 1 || B > KNN_MAX_B || N < 1 || N > KNN_MAX_N || k < 1 || k > KNN_MAX_K || ld < k || K < 2 || K > KNN_MAX_CLASSES ||

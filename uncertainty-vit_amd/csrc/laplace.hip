@@ -15,35 +15,24 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 #include "gram.h"
 
 #define LAP_MAX_B 65535
 #define LAP_MAX_C 2048
 #define LAP_MAX_K 4096
 
-__device__ __forceinline__ double lap_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double lap_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // ---- factors, launch 1: the double max-shifted softmax of every row, its NLL and whether the row is used; one wave per row ----
 // A row with a non-finite logit or a label outside [0, K) gets p = 0, nll = 0 and used = 0: it then adds exact zeros to every sum.
 __global__ __launch_bounds__(256)
 void lap_softmax_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, double* __restrict__ p,
                         double* __restrict__ row_nll, int* __restrict__ used, int B, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* z = logits + (size_t)b * ld;
     double* pr = p + (size_t)b * K;
     const int64_t y = labels[b];
-    int bad = (y < 0 || y >= K) ? 1 : 0;
+    int bad = label_ok(y, K) ? 0 : 1;
     double m = -INFINITY;
     for (int k = lane; k < K; k += 64) {
         const float v = z[k];
@@ -56,14 +45,14 @@ void lap_softmax_kernel(const float* __restrict__ logits, int64_t ld, const int6
         if (lane == 0) { row_nll[b] = 0.0; used[b] = 0; }
         return;
     }
-    m = lap_wave_max(m);
+    m = wave_max(m);
     double s = 0.0;
     for (int k = lane; k < K; k += 64) {
         const double e = exp((double)z[k] - m);
         pr[k] = e;
         s += e;
     }
-    s = lap_wave_sum(s);                                  // every lane holds the same bits: a + b == b + a at every level
+    s = wave_sum(s);                                  // every lane holds the same bits: a + b == b + a at every level
     for (int k = lane; k < K; k += 64) pr[k] = pr[k] / s;  // a lane reads back what it wrote
     if (lane == 0) { row_nll[b] = log(s) - ((double)z[y] - m); used[b] = 1; }
 }
@@ -115,8 +104,8 @@ void lap_sums_kernel(const double* __restrict__ row_nll, const int* __restrict__
         s += row_nll[b];
         n += (double)used[b];
     }
-    s = lap_wave_sum(s);
-    n = lap_wave_sum(n);                                  // whole numbers below 2^53: exact
+    s = wave_sum(s);
+    n = wave_sum(n);                                  // whole numbers below 2^53: exact
     if (lane == 0) {
         sums[0] = sums[0] + s;
         sums[1] = sums[1] + n;
@@ -225,7 +214,7 @@ void lap_mm_kernel(const float* __restrict__ feat, const double* __restrict__ X,
 __global__ __launch_bounds__(256)
 void lap_probit_kernel(const float* logits, int64_t ld, const double* __restrict__ var, double factor, float* out, int64_t ld_out,
                        float* __restrict__ lap_var, int B, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* z = logits + (size_t)b * ld;
     const double* v = var + (size_t)b * K;
@@ -253,20 +242,19 @@ void lap_probit_kernel(const float* logits, int64_t ld, const double* __restrict
 }
 
 // ---- launchers: arguments are validated before anything touches the device ----
-static inline bool lap_mis(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 static inline bool lap_bad_ck(int C, int K) { return C < 4 || (C % 4) || C > LAP_MAX_C || K < 2 || K > LAP_MAX_K; }
 static inline bool lap_bad_b(int B) { return B < 1 || B > LAP_MAX_B; }
 
 // workspace of uvit_op_lap_factors: p (B, K) double | row NLL (B) double | row used (B) int32, padded to 16 bytes
 extern "C" int64_t uvit_op_lap_factors_ws_bytes(int B, int C, int K) {
     if (lap_bad_b(B) || lap_bad_ck(C, K)) return UVIT_ERR_SHAPE;
-    return ((int64_t)B * K + B) * 8 + (((int64_t)B * 4 + 15) & ~(int64_t)15);
+    return ((int64_t)B * K + B) * 8 + align16((int64_t)B * 4);
 }
 
 extern "C" int uvit_op_lap_factors(const float* feat, const float* logits, int64_t ld, const int64_t* labels, double* A, double* G,
                                    double* sums, void* ws, int64_t ws_bytes, int B, int C, int K, uvit_stream stream) {
     if (!feat || !logits || !labels || !A || !G || !sums || !ws) return UVIT_ERR_ARG;
-    if (lap_mis(feat, 4) || lap_mis(logits, 4) || lap_mis(labels, 8) || lap_mis(A, 8) || lap_mis(G, 8) || lap_mis(sums, 8) || lap_mis(ws, 16))
+    if (misaligned(feat, 4) || misaligned(logits, 4) || misaligned(labels, 8) || misaligned(A, 8) || misaligned(G, 8) || misaligned(sums, 8) || misaligned(ws, 16))
         return UVIT_ERR_ARG;
     if (lap_bad_b(B) || lap_bad_ck(C, K) || ld < K) return UVIT_ERR_SHAPE;
     if (ws_bytes < uvit_op_lap_factors_ws_bytes(B, C, K)) return UVIT_ERR_WORKSPACE;
@@ -275,7 +263,7 @@ extern "C" int uvit_op_lap_factors(const float* feat, const float* logits, int64
     double* row_nll = p + (size_t)B * K;
     int* used = (int*)(row_nll + B);
     const int D = C + 1, ta = (D + FT - 1) / FT, tg = (K + FT - 1) / FT;
-    hipLaunchKernelGGL(lap_softmax_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, ld, labels, p, row_nll, used, B, K);
+    hipLaunchKernelGGL(lap_softmax_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, s, logits, ld, labels, p, row_nll, used, B, K);
     hipLaunchKernelGGL((lap_gram_kernel<0>), dim3(ta, ta), dim3(256), 0, s, feat, (const double*)nullptr, (const int*)used, A, B, C, D);
     hipLaunchKernelGGL((lap_gram_kernel<1>), dim3(tg, tg), dim3(256), 0, s, (const float*)nullptr, (const double*)p, (const int*)used, G, B,
                        C, K);
@@ -286,7 +274,7 @@ extern "C" int uvit_op_lap_factors(const float* feat, const float* logits, int64
 extern "C" int uvit_op_lap_prepare(const double* UG, const double* lamA, const double* lamG, double tau, double* T, int C, int K,
                                    uvit_stream stream) {
     if (!UG || !lamA || !lamG || !T || !(tau > 0.0) || !(tau < INFINITY)) return UVIT_ERR_ARG;
-    if (lap_mis(UG, 8) || lap_mis(lamA, 8) || lap_mis(lamG, 8) || lap_mis(T, 8)) return UVIT_ERR_ARG;
+    if (misaligned(UG, 8) || misaligned(lamA, 8) || misaligned(lamG, 8) || misaligned(T, 8)) return UVIT_ERR_ARG;
     if (lap_bad_ck(C, K)) return UVIT_ERR_SHAPE;
     const int D = C + 1;
     hipLaunchKernelGGL(lap_prepare_kernel, dim3((K + 15) / 16, (D + 15) / 16), dim3(256), 0, (hipStream_t)stream, UG, lamA, lamG, tau, T,
@@ -297,13 +285,13 @@ extern "C" int uvit_op_lap_prepare(const double* UG, const double* lamA, const d
 // workspace of uvit_op_lap_variance: the squares a^2 (B, C + 1) double
 extern "C" int64_t uvit_op_lap_variance_ws_bytes(int B, int C, int K) {
     if (lap_bad_b(B) || lap_bad_ck(C, K)) return UVIT_ERR_SHAPE;
-    return (((int64_t)B * (C + 1)) * 8 + 15) & ~(int64_t)15;
+    return align16((int64_t)B * (C + 1) * 8);
 }
 
 extern "C" int uvit_op_lap_variance(const float* feat, const double* UA, const double* T, double* var, void* ws, int64_t ws_bytes, int B,
                                     int C, int K, uvit_stream stream) {
     if (!feat || !UA || !T || !var || !ws) return UVIT_ERR_ARG;
-    if (lap_mis(feat, 4) || lap_mis(UA, 8) || lap_mis(T, 8) || lap_mis(var, 8) || lap_mis(ws, 16)) return UVIT_ERR_ARG;
+    if (misaligned(feat, 4) || misaligned(UA, 8) || misaligned(T, 8) || misaligned(var, 8) || misaligned(ws, 16)) return UVIT_ERR_ARG;
     if (lap_bad_b(B) || lap_bad_ck(C, K)) return UVIT_ERR_SHAPE;
     if (ws_bytes < uvit_op_lap_variance_ws_bytes(B, C, K)) return UVIT_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -318,9 +306,9 @@ extern "C" int uvit_op_lap_variance(const float* feat, const double* UA, const d
 extern "C" int uvit_op_lap_probit(const float* logits, int64_t ld, const double* var, double factor, float* out, int64_t ld_out,
                                   float* lap_var, int B, int K, uvit_stream stream) {
     if (!logits || !var || !out || !(factor >= 0.0) || !(factor < INFINITY)) return UVIT_ERR_ARG;
-    if (lap_mis(logits, 4) || lap_mis(var, 8) || lap_mis(out, 4) || lap_mis(lap_var, 4)) return UVIT_ERR_ARG;
+    if (misaligned(logits, 4) || misaligned(var, 8) || misaligned(out, 4) || misaligned(lap_var, 4)) return UVIT_ERR_ARG;
     if (lap_bad_b(B) || K < 2 || K > LAP_MAX_K || ld < K || ld_out < K) return UVIT_ERR_SHAPE;
-    hipLaunchKernelGGL(lap_probit_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, ld, var, factor, out, ld_out, lap_var,
+    hipLaunchKernelGGL(lap_probit_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, (hipStream_t)stream, logits, ld, var, factor, out, ld_out, lap_var,
                        B, K);
     return uvit_check_launch();
 }

@@ -15,27 +15,21 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 #include "gram.h"
 
 #define MAHA_MAX_B 65535
 #define MAHA_MAX_C 2048
 #define MAHA_MAX_K 4096
 
-__device__ __forceinline__ double maha_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- accumulate, launch 1: eff[b] = the label of a usable row, -1 for a row with a non-finite feature or a label outside [0, K) ----
 __global__ __launch_bounds__(256)
 void maha_screen_kernel(const float* __restrict__ feat, const int64_t* __restrict__ labels, int* __restrict__ eff, int B, int C, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* f = feat + (size_t)b * C;
     const int64_t y = labels[b];
-    int bad = (y < 0 || y >= K) ? 1 : 0;
+    int bad = label_ok(y, K) ? 0 : 1;
     for (int c = lane; c < C; c += 64)
         if (!isfinite(f[c])) bad = 1;
     bad = __any(bad);
@@ -170,7 +164,7 @@ void maha_rows_kernel(const float* __restrict__ feat, const double* __restrict__
                       const double* __restrict__ class_count, double* d, int64_t ld, int write_nan, float* __restrict__ maha,
                       float* __restrict__ rmaha, int* __restrict__ pred, const int64_t* __restrict__ labels, int* __restrict__ correct,
                       int B, int C, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* f = feat + (size_t)b * C;
     int bad = 0;
@@ -191,7 +185,7 @@ void maha_rows_kernel(const float* __restrict__ feat, const double* __restrict__
         const double t = g[c] - Wmu0[c];
         s0 = fma(t, t, s0);
     }
-    s0 = maha_wave_sum(s0);
+    s0 = wave_sum(s0);
     double best = INFINITY;
     int at = K;                                           // K: no class with a row and a comparable distance seen yet
 #pragma unroll 4
@@ -215,29 +209,28 @@ void maha_rows_kernel(const float* __restrict__ feat, const double* __restrict__
 }
 
 // ---- launchers: arguments are validated before anything touches the device ----
-static inline bool maha_mis(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 static inline bool maha_bad_ck(int C, int K) { return C < 4 || (C % 4) || C > MAHA_MAX_C || K < 2 || K > MAHA_MAX_K; }
 static inline bool maha_bad_b(int B) { return B < 1 || B > MAHA_MAX_B; }
 
 // workspace of uvit_op_maha_accumulate: the rows' effective labels (B) int32, padded to 16 bytes
 extern "C" int64_t uvit_op_maha_accumulate_ws_bytes(int B, int C, int K) {
     if (maha_bad_b(B) || maha_bad_ck(C, K)) return UVIT_ERR_SHAPE;
-    return ((int64_t)B * 4 + 15) & ~(int64_t)15;
+    return align16((int64_t)B * 4);
 }
 
 extern "C" int uvit_op_maha_accumulate(const float* feat, const int64_t* labels, double* S, double* class_sum, double* total_sum,
                                        double* class_count, double* sums, void* ws, int64_t ws_bytes, int B, int C, int K,
                                        uvit_stream stream) {
     if (!feat || !labels || !S || !class_sum || !total_sum || !class_count || !sums || !ws) return UVIT_ERR_ARG;
-    if (maha_mis(feat, 4) || maha_mis(labels, 8) || maha_mis(S, 8) || maha_mis(class_sum, 8) || maha_mis(total_sum, 8) ||
-        maha_mis(class_count, 8) || maha_mis(sums, 8) || maha_mis(ws, 16))
+    if (misaligned(feat, 4) || misaligned(labels, 8) || misaligned(S, 8) || misaligned(class_sum, 8) || misaligned(total_sum, 8) ||
+        misaligned(class_count, 8) || misaligned(sums, 8) || misaligned(ws, 16))
         return UVIT_ERR_ARG;
     if (maha_bad_b(B) || maha_bad_ck(C, K)) return UVIT_ERR_SHAPE;
     if (ws_bytes < uvit_op_maha_accumulate_ws_bytes(B, C, K)) return UVIT_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     int* eff = (int*)ws;
     const int tg = (C + GRAM_T - 1) / GRAM_T;
-    hipLaunchKernelGGL(maha_screen_kernel, dim3((B + 3) / 4), dim3(256), 0, s, feat, labels, eff, B, C, K);
+    hipLaunchKernelGGL(maha_screen_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, s, feat, labels, eff, B, C, K);
     hipLaunchKernelGGL(maha_gram_kernel, dim3(tg, tg), dim3(256), 0, s, feat, (const int*)eff, S, B, C);
     hipLaunchKernelGGL(maha_class_kernel, dim3((C + 255) / 256, K + 1), dim3(256), 0, s, feat, (const int*)eff, class_sum, total_sum,
                        class_count, sums, B, C, K);
@@ -255,9 +248,9 @@ extern "C" int uvit_op_maha_scores(const float* feat, const double* W, const dou
                                    const int64_t* labels, int32_t* correct, void* ws, int64_t ws_bytes, int B, int C, int K,
                                    uvit_stream stream) {
     if (!feat || !W || !W0 || !Wmu || !Wmu0 || !class_count || !maha || !rmaha || !pred || !ws) return UVIT_ERR_ARG;
-    if (maha_mis(feat, 4) || maha_mis(W, 8) || maha_mis(W0, 8) || maha_mis(Wmu, 8) || maha_mis(Wmu0, 8) || maha_mis(class_count, 8) ||
-        maha_mis(maha, 4) || maha_mis(rmaha, 4) || maha_mis(pred, 4) || maha_mis(dist, 8) || maha_mis(labels, 8) || maha_mis(correct, 4) ||
-        maha_mis(ws, 16))
+    if (misaligned(feat, 4) || misaligned(W, 8) || misaligned(W0, 8) || misaligned(Wmu, 8) || misaligned(Wmu0, 8) || misaligned(class_count, 8) ||
+        misaligned(maha, 4) || misaligned(rmaha, 4) || misaligned(pred, 4) || misaligned(dist, 8) || misaligned(labels, 8) || misaligned(correct, 4) ||
+        misaligned(ws, 16))
         return UVIT_ERR_ARG;
     if (maha_bad_b(B) || maha_bad_ck(C, K) || (dist && ld < K)) return UVIT_ERR_SHAPE;
     if (ws_bytes < uvit_op_maha_scores_ws_bytes(B, C, K)) return UVIT_ERR_WORKSPACE;
@@ -271,7 +264,7 @@ extern "C" int uvit_op_maha_scores(const float* feat, const double* W, const dou
                        (int64_t)C, B, C, C);
     hipLaunchKernelGGL((maha_mm_kernel<1>), dim3((K + VN - 1) / VN, tm, 1), dim3(VT), 0, s, (const float*)nullptr, (const double*)g, Wmu,
                        Wmu, d, d, ldd, B, C, K);
-    hipLaunchKernelGGL(maha_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, s, feat, (const double*)g0, Wmu0, class_count, d, ldd,
+    hipLaunchKernelGGL(maha_rows_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, s, feat, (const double*)g0, Wmu0, class_count, d, ldd,
                        dist ? 1 : 0, maha, rmaha, pred, labels, correct, B, C, K);
     return uvit_check_launch();
 }

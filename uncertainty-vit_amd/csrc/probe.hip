@@ -13,7 +13,7 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 #include "rowwise.h"
 
 #define POOL_SLICES 8        // token slices per sample: B x 8 workgroups stream the residual stream (1024 at B = 128 for 256 CUs)
@@ -59,7 +59,7 @@ void probe_pool_partial_kernel(const float* __restrict__ x, float* __restrict__ 
 template <int NV>
 __global__ __launch_bounds__(256)
 void probe_pool_norm_kernel(const float* __restrict__ scratch, float* __restrict__ feat, int B, int N, int C, float eps) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6), nv = C >> 2;
+    const int lane = WavePerRow::lane(), b = WavePerRow::row(), nv = C >> 2;
     if (b >= B) return;
     RowVec<NV> acc, r;
     load_row(acc, scratch + (size_t)b * POOL_SLICES * C, C, lane);
@@ -178,23 +178,17 @@ void probe_head_grad_kernel(const float* __restrict__ dlogits, const float* __re
 }
 
 // ---- criterion: one wave per row ----
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // loss_b = (1 - s) (lse - z_y) + s (lse - mean_k z_k);  dlogits = (softmax - (1 - s) onehot - s / K) / B.
 // counters[0] += z_y is the strict row maximum, counters[1] += fewer than five logits are greater than z_y.
 // A label outside [0, K): the row's loss and gradient are NaN, nothing is read at the label, no counter moves.
 __global__ __launch_bounds__(256)
 void probe_ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, float smoothing, float* __restrict__ dlogits,
                      float* __restrict__ row_loss, int* __restrict__ counters, int B, int K) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = WavePerRow::lane(), b = WavePerRow::row();
     if (b >= B) return;
     const float* z = logits + (size_t)b * K;
     const int64_t y = labels[b];
-    const bool valid = y >= 0 && y < (int64_t)K;
+    const bool valid = y >= 0 && y < (int64_t)K;     // spelled out: through label_ok() the compiler orders two operands differently
     float m = -INFINITY;
     for (int k = lane; k < K; k += 64) m = fmaxf(m, z[k]);
     m = wave_max(m);
@@ -209,7 +203,7 @@ void probe_ce_kernel(const float* __restrict__ logits, const int64_t* __restrict
         ge += (v >= zy) && k != (int)y;
     }
     se = wave_sum(se); sz = wave_sum(sz);
-    gt = wave_sum_int(gt); ge = wave_sum_int(ge);
+    gt = wave_sum(gt); ge = wave_sum(ge);
     const float lse = m + logf(se);
     const float nan = __uint_as_float(0x7FC00000u);
     if (lane == 0) {
@@ -250,7 +244,7 @@ extern "C" int uvit_op_probe_pool_norm(const float* x, float* feat, float* scrat
     dispatch_nv(C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         hipLaunchKernelGGL((probe_pool_partial_kernel<NV>), dim3(POOL_SLICES, B), dim3(64 * POOL_WAVES), 0, s, x, scratch, N, C);
-        hipLaunchKernelGGL((probe_pool_norm_kernel<NV>), dim3((B + 3) / 4), dim3(256), 0, s, (const float*)scratch, feat, B, N, C, eps);
+        hipLaunchKernelGGL((probe_pool_norm_kernel<NV>), WavePerRow::grid(B), WavePerRow::block(), 0, s, (const float*)scratch, feat, B, N, C, eps);
     });
     return uvit_check_launch();
 }
@@ -269,7 +263,7 @@ extern "C" int uvit_op_probe_ce(const float* logits, const int64_t* labels, floa
     if (!logits || !labels || !row_loss || !loss_out || !(smoothing >= 0.f && smoothing < 1.f)) return UVIT_ERR_ARG;
     if (B < 1 || K < 1) return UVIT_ERR_SHAPE;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(probe_ce_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, labels, smoothing, dlogits, row_loss, (int*)top1_top5, B, K);
+    hipLaunchKernelGGL(probe_ce_kernel, WavePerRow::grid(B), WavePerRow::block(), 0, s, logits, labels, smoothing, dlogits, row_loss, (int*)top1_top5, B, K);
     hipLaunchKernelGGL(probe_loss_mean_kernel, dim3(1), dim3(64), 0, s, (const float*)row_loss, loss_out, B);
     return uvit_check_launch();
 }

@@ -20,7 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 
 #define STAB_MAX_K 4096
 #define STAB_MAX_F 256
@@ -33,11 +33,7 @@
 // number is that of -z = +inf, 0xFF800000, so the padding key (all ones) sorts strictly behind every real key, a logit of -inf
 // included; in a row with a NaN (whose ranks are not used) the low word, k < 4096, still keeps every real key in front of the padding.
 __device__ __forceinline__ unsigned long long stab_key(float z, int k) {
-    float n = -z;
-    if (n == 0.f) n = 0.f;                                // -0 -> +0
-    unsigned int u = __float_as_uint(n);
-    u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
-    return ((unsigned long long)u << 32) | (unsigned long long)(unsigned int)k;
+    return ((unsigned long long)key32(fold_zero(-z)) << 32) | (unsigned long long)(unsigned int)k;
 }
 
 // ---- ranks: each row is sorted in LDS by a bitonic network over P = K rounded up to a power of two.  A row belongs to TPR =
@@ -87,10 +83,8 @@ void stability_ranks_kernel(const float* __restrict__ logits, int* __restrict__ 
         for (int k = 2; k <= P; k <<= 1) {
             for (int j = k >> 1; j > 0; j >>= 1) {
                 for (int q = t; q < (P >> 1); q += TPR) {
-                    const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), l = i | j;
-                    const bool asc = (i & k) == 0;
-                    const unsigned long long a = kr[i], b = kr[l];
-                    if ((a > b) == asc) { kr[i] = b; kr[l] = a; }
+                    const int i = BITONIC_LO(q, j), l = i | j;
+                    BITONIC_CMPX_AT(kr, i, l, (i & k) == 0);
                 }
                 __syncthreads();
             }
@@ -108,12 +102,6 @@ void stability_ranks_kernel(const float* __restrict__ logits, int* __restrict__ 
         }
         __syncthreads();                                  // the keys and the flag are read out before the next group overwrites them
     }
-}
-
-__device__ __forceinline__ int stab_wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // the double that lane i (uniform) holds as the words (lo, hi), in every lane
@@ -165,7 +153,7 @@ void stability_sequences_kernel(const int* __restrict__ ranks, double* __restric
                 for (int i = 0; i < n; ++i) zipf += stab_lane_double(lo, hi, i);
             }
         }
-        flip = stab_wave_sum_i(flip); top5 = stab_wave_sum_i(top5); bad = stab_wave_sum_i(bad);
+        flip = wave_sum(flip); top5 = wave_sum(top5); bad = wave_sum(bad);
         if (lane == 0) { pair_flip[t - 1] = flip; pair_top5[t - 1] = top5; pair_bad[t - 1] = bad; pair_zipf[t - 1] = zipf; }
     }
     __syncthreads();
@@ -173,7 +161,7 @@ void stability_sequences_kernel(const int* __restrict__ ranks, double* __restric
         int flip = 0, top5 = 0, bad = 0;
         double zipf = 0.0;
         for (int p = 0; p < F - 1; ++p) { flip += pair_flip[p]; top5 += pair_top5[p]; bad |= pair_bad[p]; zipf += pair_zipf[p]; }
-        const double nan = __longlong_as_double(0x7FF8000000000000LL);
+        const double nan = quiet_nan();
         double* o = seq + (size_t)blockIdx.x * 3;
         o[0] = bad ? nan : (double)flip;
         o[1] = bad ? nan : (double)top5;
@@ -191,7 +179,7 @@ extern "C" int uvit_op_stability_ranks(const float* logits, int32_t* ranks, int 
     while ((1 << tpr_shift) < (P >> 1) && tpr_shift < 10) ++tpr_shift;
     const int TPR = 1 << tpr_shift, threads = TPR > 256 ? TPR : 256, rpb = threads / TPR;
     const size_t lds = (size_t)rpb * P * sizeof(unsigned long long) + (size_t)rpb * sizeof(int);   // at most 32 KB + 4
-    const int vec = (K % 4 == 0) && (((uintptr_t)logits & 15) == 0);
+    const int vec = (K % 4 == 0) && !misaligned(logits, 16);
     const int groups = (R + rpb - 1) / rpb;
     hipLaunchKernelGGL(stability_ranks_kernel, dim3(groups < STAB_MAX_GRID ? groups : STAB_MAX_GRID), dim3(threads), lds, (hipStream_t)stream, logits, (int*)ranks, R, K, P,
                        tpr_shift, rpb, vec);

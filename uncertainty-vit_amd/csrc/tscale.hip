@@ -32,7 +32,7 @@
 #include <math.h>
 
 #include "../../include/uvit.h"
-#include "common.h"
+#include "probe_common.h"
 
 #define TS_MAX_N (1 << 20)
 #define TS_ROWS 16               // rows per workgroup of a pass: four waves, four consecutive rows each (small workgroups: a compute
@@ -48,13 +48,6 @@
 
 struct TsPoints { double s[TS_MAX_POINTS]; };
 
-__device__ __forceinline__ double ts_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double ts_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
-__device__ __forceinline__ bool ts_finite(float v) { return fabsf(v) < INFINITY; }      // false for NaN and for +-inf
 
 // S, T1, T2 of one column at NP points.  The difference is kept finite (a spread beyond the fp32 range ends at -FLT_MAX), so that a
 // term with e = 0 adds 0 and not 0 * inf.
@@ -123,18 +116,18 @@ void ts_pass_kernel(const float* __restrict__ logits, int64_t ld, const int64_t*
             if (NR > 0) {
 #pragma unroll
                 for (int j = 0; j < NC; ++j) {
-                    ok = ok && (lane + 64 * j >= K || ts_finite(c[r][j]));
+                    ok = ok && (lane + 64 * j >= K || finite32(c[r][j]));
                     m = fmaxf(m, c[r][j]);
                 }
             } else {
                 for (int k = lane; k < K; k += 64) {
                     const float v = z[r][k];
-                    ok = ok && ts_finite(v);
+                    ok = ok && finite32(v);
                     m = fmaxf(m, v);
                 }
             }
             const int64_t y = labels[valid ? row : (int64_t)N - 1];
-            const bool inside = y >= 0 && y < (int64_t)K;
+            const bool inside = label_ok(y, K);
             use[r] = valid && inside && !__any(!ok);
             badl[r] = valid && !inside;
             m = wave_max(m);
@@ -150,7 +143,7 @@ void ts_pass_kernel(const float* __restrict__ logits, int64_t ld, const int64_t*
             }
             dy[r] = (double)(z[r][inside ? y : 0] - m);      // nothing is read at a label outside [0, K)
 #pragma unroll
-            for (int p = 0; p < NP; ++p) { S[r][p] = ts_wave_sum(a0[p]); T1[r][p] = ts_wave_sum(a1[p]); T2[r][p] = ts_wave_sum(a2[p]); }
+            for (int p = 0; p < NP; ++p) { S[r][p] = wave_sum(a0[p]); T1[r][p] = wave_sum(a1[p]); T2[r][p] = wave_sum(a2[p]); }
         }
         // every lane holds the sums of all RPI rows: lane r takes row r's
         double Sx[NP], T1x[NP], T2x[NP], dyx = dy[0];
@@ -218,7 +211,7 @@ void ts_step_kernel(const double* __restrict__ part, int nblk, double* __restric
 #pragma unroll
         for (int q = 0; q < Q; ++q) acc[q] += part[(size_t)b * Q + q];
 #pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = ts_wave_sum(acc[q]);
+    for (int q = 0; q < Q; ++q) acc[q] = wave_sum(acc[q]);
     if ((tid & 63) == 0)
 #pragma unroll
         for (int q = 0; q < Q; ++q) red[tid >> 6][q] = acc[q];
@@ -240,12 +233,12 @@ void ts_step_kernel(const double* __restrict__ part, int nblk, double* __restric
         out[7] = (double)fit.N - n - bad;
         if (bad > 0.0) {
 #pragma unroll
-            for (int q = 0; q < 8; ++q) out[q] = ts_nan();
+            for (int q = 0; q < 8; ++q) out[q] = quiet_nan();
             state[3] = 1.0;
             return;
         }
         if (!(n > 0.0)) {
-            out[0] = out[1] = out[2] = out[3] = out[4] = ts_nan();
+            out[0] = out[1] = out[2] = out[3] = out[4] = quiet_nan();
             out[5] = 1.0; out[6] = 0.0;
             state[3] = 1.0;
             return;
@@ -303,7 +296,7 @@ static inline void ts_launch_pass(hipStream_t st, const float* logits, int64_t l
 
 extern "C" int uvit_op_ts_fit(const float* logits, int64_t ld, const int64_t* labels, int N, int K, double t_min, double t_max, double tol,
                               int max_iter, double* out, void* ws, int64_t ws_bytes, uvit_stream stream) {
-    if (!logits || !labels || !out || !ws || ((uintptr_t)ws & 15)) return UVIT_ERR_ARG;
+    if (!logits || !labels || !out || !ws || misaligned(ws, 16)) return UVIT_ERR_ARG;
     if (!ts_set_ok(N, K) || ld < (int64_t)K) return UVIT_ERR_SHAPE;
     if (!(t_min > 0.0) || !(t_max > t_min) || !(t_max < INFINITY) || !(tol > 0.0) || max_iter < 1 || max_iter > TS_MAX_ITER) return UVIT_ERR_SHAPE;
     if (ws_bytes < (int64_t)ts_ws_total(N)) return UVIT_ERR_WORKSPACE;
