@@ -833,6 +833,28 @@ int uvit_op_knn_scores(const float* sim, const int32_t* idx, int64_t ld, const i
                        double* votes, int64_t ldv, const int64_t* labels, int32_t* correct, int B, int k, int K, double temperature,
                        uvit_stream stream);
 
+/* ---- ViM and residual OOD scores of the probe's feature (csrc/vim.hip) ----
+ * Virtual-logit matching (Wang et al., CVPR 2022) for a frozen encoder with an affine head z = W f + b.  With o = -pinv(W) b, the
+ * rows of R (Cn, C) an orthonormal basis of the Cn = C - D smallest principal directions of the training features centred at o:
+ * residual = |R (f - o)|, vim = alpha residual - logsumexp(z), pred = arg max z; larger = more out of distribution.  The host stacks
+ * A = [R ; W] (Cn + K, C) and a = [-R o ; b] (Cn + K), both double, row-major.  Arguments are checked before anything touches the
+ * device (-1: a NULL or misaligned pointer, a non-finite alpha; -2: a shape; -4: the workspace), nothing synchronises with the host,
+ * a second run gives the same bits, and a row's outputs do not depend on the other rows of the batch.
+ * C % 4 == 0, 4 <= C <= 2048, 1 <= Cn <= C - 1, 2 <= K <= 4096, 1 <= B <= 65535. */
+/* Workspace of uvit_op_vim_scores in bytes: y (B, Cn + K) double and two doubles per row, padded to 16 bytes. */
+int64_t uvit_op_vim_scores_ws_bytes(int B, int C, int Cn, int K);
+/* vim (B) fp32, residual (B) fp32 and pred (B) int32 of feat (B, C) fp32.  y = A f + a goes to ws (16 x 32 output tiles; every
+ * element is one fma chain over ascending c from zero, then one addition of a_j).  Per row, by one wave: residual = sqrt(sum_{j < Cn}
+ * y_j^2) (lane partial sums in ascending j, then the xor tree); max and arg max of the K logits behind them (the lowest class on
+ * ties); lse = max + log(sum_k exp(z_k - max)) in double, same order; vim = fma(alpha, residual, -lse); each output rounded to its type
+ * once.  A row with a non-finite feature gets NaN, NaN, -1.  labels (B) int64 and correct (1) int32, both nullable: *correct += the
+ * rows whose pred equals their label (an integer atomic).  sums (4) double, nullable: {sum of max_k z, sum of residual, rows used,
+ * rows skipped} over the batch's usable rows, added in place by one owner in a fixed order (a third launch of one workgroup; without
+ * sums the call makes two launches). */
+int uvit_op_vim_scores(const float* feat, const double* A, const double* a, double alpha, float* vim, float* residual, int32_t* pred,
+                       const int64_t* labels, int32_t* correct, double* sums, void* ws, int64_t ws_bytes, int B, int C, int Cn, int K,
+                       uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,17 @@ neighbours, Sun et al. 2022), and the run reports the weighted k-NN accuracy of 
 ones).  Before `* Acc@1` the run prints `* kNN bank of <n> images (<skipped> skipped), <K> classes, k <k>, temperature <T>` and
 `* kNN Acc@1 <a> mean <m>`; log.txt gains `test_knn_acc1`, `test_knn_mean`, `test_knn_k`; with --output_dir the bank is saved as
 `neighbours.pth`.
+
+`--vim_data_path DIR` (with --eval; the linear head, --laplace and --ensembles with --ens_combine logits, also with --maha_* and
+--knn_*; implies --detection) fits ViM (virtual-logit matching, Wang et al. 2022; LinearProbe.fit_vim) on
+the frozen features of a labelled image folder, which is read twice (once when --maha_data_path names the same folder: the density's
+moments are reused).  The detection gains the columns `vim` = alpha |R (f - o)| - logsumexp(z) and `residual` = |R (f - o)|, the
+length of the feature's part outside the principal space of the training features.  `--vim_dim D` is that space's dimension
+(default 1000 for C >= 2048, 512 for C >= 768, else C // 2); `--vim_state FILE` loads a saved fit instead (exclusive with
+--vim_data_path).  --gp_layer, --het_layer and --ens_combine probs are refused: their logits are not affine in the feature.  Before
+`* Acc@1` the run prints `* ViM fit on <n> images (<skipped> skipped), dim <D> of <C>, alpha <a>, explained <e>` and
+`* ViM Acc@1 <a> mean <m>`; log.txt gains `test_vim_acc1`, `test_vim_mean`, `test_vim_dim`, `test_vim_alpha`; with --output_dir the
+fit is saved as `vim.pth`.
 """
 import argparse
 import json
@@ -227,6 +238,13 @@ def get_args(argv=None):
     a("--knn_k", type=int, default=argparse.SUPPRESS, metavar="K", help="neighbours per query, 1 .. 256 (default 20)")
     a("--knn_temperature", type=float, default=argparse.SUPPRESS, metavar="T",
       help="temperature of the k-NN vote exp((s_j - s_1) / T) (default 0.07)")
+    a("--vim_data_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
+      help="with --eval: labelled image folder (the evaluation's classes) on whose features ViM is fitted (read twice); adds the "
+           "detection columns vim and residual, implies --detection")
+    a("--vim_dim", type=int, default=argparse.SUPPRESS, metavar="D",
+      help="dimension of the principal space, 1 .. C - 1 (default 1000 for C >= 2048, 512 for C >= 768, else C // 2)")
+    a("--vim_state", type=str, default=argparse.SUPPRESS, metavar="FILE",
+      help="with --eval: load a saved ViM fit (vim.pth) instead of fitting (exclusive with --vim_data_path)")
     return p.parse_args(argv)
 
 
@@ -441,6 +459,44 @@ def knn_log_entries(fit, stats):
     return {"test_knn_acc1": stats["knn_acc1"], "test_knn_mean": stats["knn_mean"], "test_knn_k": fit["k"]}
 
 
+VIM_FLAGS = ("vim_data_path", "vim_dim", "vim_state")
+
+
+def check_vim_flags(args):
+    """How the run gets its ViM fit: "fit" (--vim_data_path), "state" (--vim_state) or None.  The three --vim_* flags belong to --eval,
+    the two sources are exclusive, --vim_dim (at least 1) steers a fit on --vim_data_path.  ViM needs a head whose logits are affine
+    in the feature: --gp_layer, --het_layer and --ensembles --ens_combine probs are refused."""
+    if not any(hasattr(args, k) for k in VIM_FLAGS):
+        return None
+    if not args.eval:
+        raise ValueError("--vim_data_path / --vim_dim / --vim_state belong to an evaluation: give --eval")
+    if hasattr(args, "vim_data_path") and hasattr(args, "vim_state"):
+        raise ValueError("--vim_data_path fits ViM and --vim_state loads it: give one")
+    if hasattr(args, "vim_dim") and args.vim_dim < 1:
+        raise ValueError(f"--vim_dim must lie in [1, C - 1], got {args.vim_dim}")
+    if getattr(args, "gp_layer", False) or getattr(args, "het_layer", False) or \
+            (getattr(args, "ensembles", False) and getattr(args, "ens_combine", "logits") == "probs"):
+        raise ValueError("--vim_* need logits that are affine in the feature: not with --gp_layer, --het_layer or --ens_combine probs")
+    if hasattr(args, "vim_state"):
+        if hasattr(args, "vim_dim"):
+            raise ValueError("--vim_dim steers the fit of --vim_data_path DIR: a saved fit keeps its dimension (alpha needs the rows)")
+        return "state"
+    if hasattr(args, "vim_data_path"):
+        return "fit"
+    raise ValueError("--vim_dim steers the fit of --vim_data_path DIR: give it")
+
+
+def vim_lines(fit, stats, embed_dim):
+    """The two lines in front of `* Acc@1`, from fit_vim's (or load_vim_state's) result and the evaluation's stats."""
+    return ["* ViM fit on {n} images ({skipped} skipped), dim {dim} of {}, alpha {alpha:.5f}, explained {explained:.5f}".format(embed_dim, **fit),
+            "* ViM Acc@1 {vim_acc1:.3f} mean {vim_mean:.5f}".format(**stats)]
+
+
+def vim_log_entries(fit, stats):
+    """What log.txt gains: the snapshot head's accuracy, the mean vim of the evaluation set, the dimension and alpha in use."""
+    return {"test_vim_acc1": stats["vim_acc1"], "test_vim_mean": stats["vim_mean"], "test_vim_dim": fit["dim"], "test_vim_alpha": fit["alpha"]}
+
+
 def maha_lines(fit, stats):
     """The two lines in front of `* Acc@1`, from fit_density's result and the evaluation's stats."""
     return ["* Mahalanobis fit on {n} images ({skipped} skipped), {classes} classes ({empty_classes} empty), shrinkage {shrinkage:g}, "
@@ -574,7 +630,8 @@ def main(args):
     laplace = check_lap_flags(args)
     maha = check_maha_flags(args)
     knn = check_knn_flags(args)
-    detection = detection or maha is not None or knn is not None
+    vim = check_vim_flags(args)
+    detection = detection or maha is not None or knn is not None or vim is not None
     gp_layer = getattr(args, "gp_layer", False)
     if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
         raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
@@ -703,6 +760,17 @@ def main(args):
         saved = {**saved, **{key: getattr(args, "knn_" + key) for key in ("k", "temperature") if hasattr(args, "knn_" + key)}}
         knn_fit = probe.load_neighbour_state(saved)
         print("Load neighbour bank %s" % args.knn_state)
+    vim_fit = None
+    if vim == "fit":
+        loader_vim, _ = build_loader(args, encoder, args.vim_data_path, 1, train=False)
+        same = maha == "fit" and os.path.realpath(args.maha_data_path) == os.path.realpath(args.vim_data_path)
+        vim_fit = probe.fit_vim(DevicePrefetcher(loader_vim, device), dim=getattr(args, "vim_dim", None),
+                                moments=probe.density_state_dict() if same else None)      # the density's pass has read this folder
+        if args.output_dir:
+            torch.save(probe.vim_state_dict(), os.path.join(args.output_dir, "vim.pth"))
+    elif vim == "state":
+        vim_fit = probe.load_vim_state(torch.load(args.vim_state, map_location="cpu", weights_only=False))
+        print("Load ViM state %s" % args.vim_state)
     ts_fit = None
     if ts_mode == "fit":
         loader_ts, _ = build_loader(args, encoder, args.ts_data_path, 1, train=False)
@@ -738,6 +806,9 @@ def main(args):
         if knn_fit is not None:
             stats["neighbour_fit"] = knn_fit
             print("\n".join(knn_lines(knn_fit, stats)))
+        if vim_fit is not None:
+            stats["vim_fit"] = vim_fit
+            print("\n".join(vim_lines(vim_fit, stats, probe.embed_dim)))
         print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
         if gp_layer:
             print(gp_variance_line(stats))
@@ -762,6 +833,7 @@ def main(args):
                                     **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {}),
                                     **(maha_log_entries(maha_fit, stats) if maha_fit is not None else {}),
                                     **(knn_log_entries(knn_fit, stats) if knn_fit is not None else {}),
+                                    **(vim_log_entries(vim_fit, stats) if vim_fit is not None else {}),
                                     **(conformal_log_entries(cp_fit, stats["conformal"]) if conformal else {})}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)

@@ -85,6 +85,14 @@ class EnsembleProbe(LinearProbe):
         self.member_norms = fn(self.member_norms)
         return super()._apply(fn, recurse)
 
+    def _vim_head(self):
+        """combine="logits": the mean of the members' heads, whose logits are the mean of theirs; "probs" is not affine."""
+        if self.combine != "logits":
+            self._vim_not_affine('the ensemble with combine="probs" reports the logarithm of a mean of softmaxes')
+        heads = [getattr(self.heads, str(m)) for m in range(self.members)]
+        return (torch.stack([h.weight.detach().to("cpu", torch.float64) for h in heads]).mean(0),
+                torch.stack([h.bias.detach().to("cpu", torch.float64) for h in heads]).mean(0))
+
     def _head_buffers_for(self, B):
         M, dev = self.members, self._arena.device
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)      # noqa: E731

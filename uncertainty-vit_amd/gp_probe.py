@@ -106,6 +106,9 @@ class GPProbe(LinearProbe):
         self._cov_tick += 1
         return super()._apply(fn, recurse)
 
+    def _vim_head(self):
+        self._vim_not_affine("the GP head passes the feature through random Fourier features")
+
     def load_state_dict(self, state_dict, strict=True, **kw):
         out = super().load_state_dict(state_dict, strict=strict, **kw)
         self._cov_tick += 1                      # the precision matrix may have changed: inv(P) is formed again

@@ -98,6 +98,9 @@ class HetProbe(LinearProbe):
                 getattr(h, name).weight.copy_(lin.weight)
                 getattr(h, name).bias.copy_(lin.bias)
 
+    def _vim_head(self):
+        self._vim_not_affine("the heteroscedastic head reports the logarithm of a Monte-Carlo mean of softmaxes")
+
     def _head_buffers_for(self, B):
         K, R, dev = self.num_classes, self.num_factors, self._arena.device
         ws = max(ws_size(lib().uvit_op_het_mc_ws_bytes, B, S, K, R) for S in (self.train_mc_samples, self.test_mc_samples))

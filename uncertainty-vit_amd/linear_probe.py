@@ -26,6 +26,7 @@ from .probe_neighbours import KNN_COLUMNS, KNN_K, KNN_MAX_C, KNN_MAX_K, KNN_MAX_
 from .probe_stability import STABILITY_MAX_FRAMES, StabilityMixin                                                         # noqa: F401
 from .probe_temperature import TS_MAX_ITER, TS_MAX_N, TS_STATUS, TS_T_MAX, TS_T_MIN, TS_TOL, TemperatureMixin             # noqa: F401
 from .probe_util import column_mean, labelled_batches, ws_size
+from .probe_vim import VIM_COLUMNS, VimMethods, VimScore, vim_default_dim                                                # noqa: F401
 
 __all__ = ["LinearProbe", "build_probe_encoder", "load_encoder_checkpoint"]
 
@@ -42,11 +43,11 @@ def _timm_trunc_normal_(t, std):
     return t
 
 
-class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, TemperatureMixin, ConformalMixin, StabilityMixin, nn.Module):
+class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, VimMethods, TemperatureMixin, ConformalMixin, StabilityMixin, nn.Module):
     """`encoder`: a VisionTransformerForCyclicalTraining in .eval() (it is NOT a sub-module: state_dict() holds `head.weight`
     (K, C) and `head.bias` (K,), the reference's keys).  Owns the head, gradient and Adam moment arenas.  The post-hoc families are
-    the mixins of probe_detect.py, probe_temperature.py, probe_conformal.py and probe_stability.py; the two feature-side scores are
-    objects (probe_density.py, probe_neighbours.py) that `_scores` holds in the order of their detection columns."""
+    the mixins of probe_detect.py, probe_temperature.py, probe_conformal.py and probe_stability.py; the three feature-side scores
+    are objects (probe_density.py, probe_neighbours.py, probe_vim.py) that `_scores` holds in the order of their detection columns."""
 
     BETAS, EPS = (0.9, 0.999), 1e-8          # create_optimizer's adamw defaults (optim_factory.py:133-134)
     # per-sample uncertainty columns of evaluate(detection=True), larger = more uncertain: the three of uvit_op_detect_rows on the
@@ -75,8 +76,8 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, TemperatureM
         # conformal sets: the fitted or set state (settings and the device table of uvit_op_cp_quantile) and the quantile's workspace
         self._cp, self._cp_ws = None, None
         # the feature-side scores, and those of them that the running evaluate(detection=True) stores: (score, {"correct", "slabs"})
-        self._density, self._bank = FeatureDensity(self), NeighbourBank(self)
-        self._scores, self._score_eval = (self._density, self._bank), ()
+        self._density, self._bank, self._vim_score = FeatureDensity(self), NeighbourBank(self), VimScore(self)
+        self._scores, self._score_eval = (self._density, self._bank, self._vim_score), ()
         self._var_slabs = None                   # a head's own column, kept for its mean by _evaluate_with_mean
         self._setup_head(init_scale)
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
@@ -120,7 +121,7 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, TemperatureM
         self._grad_arena, self.exp_avg, self.exp_avg_sq = (fn(t).contiguous() for t in (self._grad_arena, self.exp_avg, self.exp_avg_sq))
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
         self._det_ws = self._ts_table = self._ts_ws = self._cp = self._cp_ws = None
-        for score in self._scores:                   # a density stays float64 (its sums stay on the host), a bank bf16
+        for score in self._scores:                   # a density and a ViM fit stay float64 (their host parts stay on the host), a bank bf16
             score.moved(new.device)
         self._rebind()
         return self
@@ -311,6 +312,10 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, TemperatureM
         While a neighbour bank is set (fit_neighbours, load_neighbour_state), detection also stores the column `knn` of every batch's
         features, the OOD images' included, behind those, and stats gains "knn_mean" (the mean of `knn` over the evaluation rows that
         are not NaN) and "knn_acc1" (the weighted k-NN accuracy in percent, counted on the device).
+        While a ViM fit is set (fit_vim, load_vim_state), detection also stores the columns `vim` and `residual` of every batch's
+        features, the OOD images' included, behind those, and stats gains "vim_mean" (the mean of `vim` over the evaluation rows that
+        are not NaN) and "vim_acc1" (the accuracy in percent of the head the fit took its snapshot of, counted on the device: it
+        differs from acc1 when the head was trained on after the fit).  The post-hoc temperature does not reach `vim`.
         `temperature`: None launches and returns exactly the above.  True applies the fitted or set post-hoc temperature
         (fit_temperature, set_temperature; an error when there is none), a number applies that T: uvit_op_ts_scale then runs in place
         on the logits directly behind every _logits_into of the evaluation, the OOD images included, with 1 / T read from a device

@@ -242,6 +242,8 @@ _PROTOTYPES = {
     "uvit_op_knn_search_ws_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "uvit_op_knn_search": (_i, [_vp] * 6 + [_i64, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "uvit_op_knn_scores": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, C.c_double, _vp]),
+    "uvit_op_vim_scores_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "uvit_op_vim_scores": (_i, [_vp, _vp, _vp, C.c_double] + [_vp] * 7 + [_i64, _i, _i, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 

@@ -67,8 +67,9 @@ class FeatureDensity(FeatureScore):
         self.probe._det_refresh()
         return self.info
 
-    def fit(self, loader, shrinkage):
-        rho = _shrinkage(shrinkage)
+    def accumulate(self, loader):
+        """One pass of uvit_op_maha_accumulate over a labelled loader and one read: the host float64 (S, class_sum, total_sum,
+        class_count, sums), None for a loader without a batch.  The density's fit and the first pass of the ViM fit (probe_vim.py)."""
         p = self.probe
         K, Cd, acc = p.num_classes, p.embed_dim, None
         o_cs, o_ts, o_cc, o_sums = Cd * Cd, Cd * Cd + K * Cd, Cd * Cd + K * Cd + Cd, Cd * Cd + K * Cd + Cd + K
@@ -81,10 +82,16 @@ class FeatureDensity(FeatureScore):
                                                 ws.numel(), B, Cd, K, cur_stream()), "uvit_op_maha_accumulate")
         self.fit_ws = None                                                                    # the fit's workspace is not kept
         if acc is None:
-            raise native.UvitError("the density fit needs at least two labelled samples")
+            return None
         host = acc.cpu()                                                                      # the one read
-        return self.install(host[:o_cs].view(Cd, Cd), host[o_cs:o_ts].view(K, Cd), host[o_ts:o_cc], host[o_cc:o_sums],
-                            host[o_sums:o_sums + 2], rho)
+        return host[:o_cs].view(Cd, Cd), host[o_cs:o_ts].view(K, Cd), host[o_ts:o_cc], host[o_cc:o_sums], host[o_sums:o_sums + 2]
+
+    def fit(self, loader, shrinkage):
+        rho = _shrinkage(shrinkage)
+        sums = self.accumulate(loader)
+        if sums is None:
+            raise native.UvitError("the density fit needs at least two labelled samples")
+        return self.install(*sums, rho)
 
     def buffers_for(self, B):
         p = self.probe

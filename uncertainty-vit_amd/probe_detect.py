@@ -119,7 +119,7 @@ class DetectionMixin:
 
     def _det_refresh(self):
         """The instance's DETECT_COLUMNS: the head's own columns, followed by the columns of every feature-side score that has a state
-        (MAHA_COLUMNS, then KNN_COLUMNS).  An instance attribute only where that differs from the class's."""
+        (MAHA_COLUMNS, then KNN_COLUMNS, then VIM_COLUMNS).  An instance attribute only where that differs from the class's."""
         cols = tuple(self._det_class_columns()) + tuple(c for score in self._scores if score.state is not None for c in score.columns)
         if cols == type(self).DETECT_COLUMNS:
             self.__dict__.pop("DETECT_COLUMNS", None)

@@ -1,5 +1,5 @@
 """What every probe family needs, written once: the two batch loops, the workspace query, the growing device store, the mean of a
-per-sample column, and the part of a feature-side score (probe_density.py, probe_neighbours.py) that does not depend on the score."""
+per-sample column, and the part of a feature-side score (probe_density.py, probe_neighbours.py, probe_vim.py) that does not depend on the score."""
 import math
 
 import torch
