@@ -136,6 +136,20 @@ int uvit_engine_sync_shadows(uvit_engine* e, int which, uvit_stream stream);
  * <= cfg.batch.  train_dropout applies attention dropout / drop-path with (seed, it). */
 int uvit_engine_forward_features(uvit_engine* e, int which, const float* images, const int64_t* mask, int batch,
                                  int train_dropout, uint32_t seed, uint32_t it, uvit_stream stream);
+/* Blocks first_layer .. depth-1 once more, from the residual stream X[first_layer] that the preceding uvit_engine_forward_features
+ * (same `which`, same `batch`) left in the workspace: the stochastic passes of MC-dropout.  No images: im2col
+ * and the embedding are skipped.  With train_dropout (student weights), block l draws the attention-dropout masks it draws in a full
+ * forward at (seed, it); drop-path is never applied (the reference's enable_dropout leaves DropPath in eval mode).  Overwrites
+ * X[first_layer+1 .. depth], the "xm" of those blocks and their activations; X[0 .. first_layer] are only read, so any number of tails
+ * from the same or a lower block may follow one forward, and a tail changes nothing that a later forward or training step computes.
+ * A tail from a HIGHER block than an earlier tail since the forward would continue that tail's stream, not the forward's: it is refused
+ * (run uvit_engine_forward_features again first).
+ * Refused before any launch: UVIT_ERR_SHAPE for the two-stream model; UVIT_ERR_ARG for a NULL engine, first_layer outside [0, depth) or
+ * above the lowest first_layer of a tail since the forward, and a `which` or `batch` other than that of the last
+ * uvit_engine_forward_features -- which includes the case that there is none, or that a training step, or a tail whose launch failed,
+ * has come since (the engine keeps this "tail valid" record). */
+int uvit_engine_forward_tail(uvit_engine* e, int which, int batch, int first_layer, int train_dropout, uint32_t seed, uint32_t it,
+                             uvit_stream stream);
 /* norm + drop cls + (masked-row gather) + lm_head (modeling_cyclical.py:207,215-225) on the last
  * forward_features result.  all_tokens=1: out (B*P, C); else out (count, C) rows in mask order.
  * out must hold B*P*C floats; *count_dev (device int) receives the number of valid rows.
@@ -854,6 +868,29 @@ int64_t uvit_op_vim_scores_ws_bytes(int B, int C, int Cn, int K);
 int uvit_op_vim_scores(const float* feat, const double* A, const double* a, double alpha, float* vim, float* residual, int32_t* pred,
                        const int64_t* labels, int32_t* correct, double* sums, void* ws, int64_t ws_bytes, int B, int C, int Cn, int K,
                        uvit_stream stream);
+
+/* ---- MC-dropout: streaming combination of T stochastic passes (csrc/mcd.hip) ----
+ * The reference keeps the logits of all T passes over the whole loader and takes torch.mean(outputs, 0) (uncertainty_evaluations.py:42-89); here
+ * every pass is added to a caller-owned per-row state and nothing of size (T, B, K) exists.  One wave per row, no float atomics, every
+ * sum has one owner and a fixed order: the bits do not depend on the launch shape (a batch split into two calls gives the bits of one
+ * call) and are the same on every run.  Arguments are checked before anything touches the device: UVIT_ERR_ARG for a NULL required
+ * pointer, a mode outside {0, 1}, a `first` outside {0, 1} or a state that is not 16-byte aligned; UVIT_ERR_SHAPE for B < 1, K < 1,
+ * T < 1.  Asynchronous on `stream`.
+ * State of row b: uvit_op_mcd_state_bytes(1, K) bytes at state + b * uvit_op_mcd_state_bytes(1, K):
+ *   double sum_z[K], sum_p[K], sum_p2[K], sum_h | int32 votes[K], nan flag | padding to 16 bytes. */
+int64_t uvit_op_mcd_state_bytes(int B, int K);        /* < 0: UVIT_ERR_SHAPE */
+/* One pass: logits (B, K) fp32.  p[k] = expf((z[k] - max) - logf(sum_k expf(z[k] - max))) in fp32 (uvit_op_ens_combine's formula),
+ * widened; sum_z += z, sum_p += p, sum_p2 += p p (double), sum_h += -sum_k p log p (double, 0 log 0 = 0; per-lane partial sums over
+ * ascending k, then the xor tree), votes[argmax z] += 1 (lowest index on ties).  first = 1 overwrites instead of adding: no memset.
+ * A row with a NaN or +inf logit, or without any logit above -inf, has no softmax: it raises its flag, which stays up. */
+int uvit_op_mcd_accumulate(const float* logits, void* state, int first, int B, int K, uvit_stream stream);
+/* After T passes: z (B, K) fp32, mode 0: (float)(sum_z / T), the reference's mean of logits; mode 1: (float)log(sum_p / T).
+ * unc (B, 5, double, nullable), with pbar = sum_p / T and k* = argmax z (lowest index on ties):
+ *   {total = -sum_k pbar log pbar, aleatoric = sum_h / T, mi = max(total - aleatoric, 0),
+ *    var_pred = max(sum_p2[k*] / T - pbar[k*]^2, 0), disagreement = 1 - votes[k*] / T}.
+ * A flagged row gives five NaNs; z follows IEEE arithmetic.  z holds the same bits whether or not unc is asked for.  The state is only
+ * read. */
+int uvit_op_mcd_finalize(const void* state, int T, int mode, float* z, double* unc, int B, int K, uvit_stream stream);
 
 #ifdef __cplusplus
 }

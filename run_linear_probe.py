@@ -120,6 +120,19 @@ length of the feature's part outside the principal space of the training feature
 `* Acc@1` the run prints `* ViM fit on <n> images (<skipped> skipped), dim <D> of <C>, alpha <a>, explained <e>` and
 `* ViM Acc@1 <a> mean <m>`; log.txt gains `test_vim_acc1`, `test_vim_mean`, `test_vim_dim`, `test_vim_alpha`; with --output_dir the
 fit is saved as `vim.pth`.
+
+`--mc_dropout_forwards T` (the reference's flag; 0 or absent: off; exclusive with --gp_layer, --het_layer, --ensembles and --laplace)
+evaluates the linear head under MC-dropout (uncertainty-vit_amd/mcd_probe.py): every evaluated batch runs one
+deterministic encoder forward and T passes under attention dropout, whose logits are combined on the device.  `--attn_drop_rate P`
+(the reference's flag; required > 0 with T > 0, refused without T: every other forward of the probe is dropout-free) is the dropout
+rate the encoder is built with; `--mc_dropout_layers n` applies it in
+the last n blocks only (0, the default: in all of them), so that a batch costs 1 + T n / L encoder passes; `--mc_combine logits|probs`
+(the mean of the passes' logits, the reference's; or the logarithm of the mean of their softmaxes); `--mc_seed` (0).  Training is the
+linear probe's, on the deterministic forward.  --calibration, --detection / --ood_data_path (with the columns mcd_total,
+mcd_aleatoric, mcd_mi, mcd_var, mcd_disagreement), --ts_*, --cp_*, --perturbation_path and --maha_* / --knn_* / --vim_* (on the
+deterministic feature) work on the combined logits.  After `* Acc@1` the run prints `* MC-dropout passes <T> layers <n> of <L> rate
+<p> entropy ... expected ... MI ... variance ... disagreement ...` and `* Deterministic Acc@1 ...`; log.txt gains
+`test_mcd_{total,aleatoric,mi,var,disagreement,det_acc1,passes}`.
 """
 import argparse
 import json
@@ -245,6 +258,14 @@ def get_args(argv=None):
       help="dimension of the principal space, 1 .. C - 1 (default 1000 for C >= 2048, 512 for C >= 768, else C // 2)")
     a("--vim_state", type=str, default=argparse.SUPPRESS, metavar="FILE",
       help="with --eval: load a saved ViM fit (vim.pth) instead of fitting (exclusive with --vim_data_path)")
+    a("--mc_dropout_forwards", type=int, default=argparse.SUPPRESS, metavar="T",
+      help="evaluate under MC-dropout: T stochastic passes per batch, combined on the device (0: off); needs --attn_drop_rate > 0")
+    a("--attn_drop_rate", type=float, default=argparse.SUPPRESS, metavar="P", help="with --mc_dropout_forwards: attention dropout rate of the passes, > 0")
+    a("--mc_dropout_layers", type=int, default=argparse.SUPPRESS, metavar="N",
+      help="MC-dropout in the last N blocks only: 1 + T N / L encoder passes per batch (default 0: every block)")
+    a("--mc_combine", type=str, choices=["logits", "probs"], default=argparse.SUPPRESS,
+      help="combined logits: the mean of the passes' logits (default, the reference's) or the log of the mean of their softmaxes")
+    a("--mc_seed", type=int, default=argparse.SUPPRESS, help="seed of the dropout masks (default 0)")
     return p.parse_args(argv)
 
 
@@ -253,6 +274,8 @@ GP_FLAGS = ("gp_num_inducing", "gp_cov_momentum", "gp_cov_ridge_penalty", "gp_ke
 HET_FLAGS = ("het_num_factors", "het_temperature", "het_train_mc_samples", "het_test_mc_samples", "het_seed")
 ENS_FLAGS = ("ens_members", "ens_combine", "ens_bagging", "ens_seed", "ens_heads")
 ENS_KEYS = ("ens_total", "ens_aleatoric", "ens_mi", "ens_var", "ens_disagreement")
+MCD_FLAGS = ("mc_dropout_layers", "mc_combine", "mc_seed")
+MCD_KEYS = ("mcd_total", "mcd_aleatoric", "mcd_mi", "mcd_var", "mcd_disagreement")
 
 
 def calibration_line(stats):
@@ -280,6 +303,39 @@ def ens_lines(stats):
     lines.append("* Ens entropy {ens_total:.5f} expected {ens_aleatoric:.5f} MI {ens_mi:.5f} variance {ens_var:.6f} "
                  "disagreement {ens_disagreement:.5f}".format(**stats))
     return lines
+
+
+def check_mcd_flags(args):
+    """The number of MC-dropout passes (--mc_dropout_forwards; 0: off).  The --mc_* flags and --attn_drop_rate belong to it, it needs a rate > 0,
+    and it samples the linear head: --gp_layer, --het_layer, --ensembles and --laplace are other heads."""
+    T = getattr(args, "mc_dropout_forwards", 0)
+    if T < 0:
+        raise ValueError(f"--mc_dropout_forwards must be >= 0, got {T}")
+    if not T:
+        if any(hasattr(args, k) for k in MCD_FLAGS + ("attn_drop_rate",)):      # the probe's forward is dropout-free without it
+            raise ValueError("--mc_* options and --attn_drop_rate belong to MC-dropout: give --mc_dropout_forwards T")
+        return 0
+    if any(getattr(args, k, False) for k in ("gp_layer", "het_layer", "ensembles", "laplace")):
+        raise ValueError("--mc_dropout_forwards samples the linear head: give it without --gp_layer / --het_layer / --ensembles / --laplace")
+    if not getattr(args, "attn_drop_rate", 0.0) > 0.0:
+        raise ValueError("--mc_dropout_forwards samples the attention dropout: give --attn_drop_rate P > 0")
+    if getattr(args, "mc_dropout_layers", 0) < 0:
+        raise ValueError(f"--mc_dropout_layers must be >= 0, got {args.mc_dropout_layers}")
+    return T
+
+
+def mcd_lines(stats, depth, rate):
+    """The two lines behind `* Acc@1`: the entropy split of the passes, and the accuracy of the deterministic pass."""
+    return ["* MC-dropout passes {mcd_passes} layers {mcd_layers} of {depth} rate {rate:g} entropy {mcd_total:.5f} expected "
+            "{mcd_aleatoric:.5f} MI {mcd_mi:.5f} variance {mcd_var:.6f} disagreement {mcd_disagreement:.5f}".format(depth=depth, rate=rate, **stats),
+            "* Deterministic Acc@1 {det_acc1:.3f}".format(**stats)]
+
+
+def mcd_log_entries(stats):
+    """What log.txt gains under MC-dropout: the five means, the deterministic accuracy and the number of passes."""
+    out = {f"test_{k}": stats[k] for k in MCD_KEYS}
+    out.update(test_mcd_det_acc1=stats["det_acc1"], test_mcd_passes=stats["mcd_passes"])
+    return out
 
 
 def ens_log_entries(stats):
@@ -645,6 +701,7 @@ def main(args):
         raise ValueError("--ens_* options belong to the ensemble: give --ensembles")
     if ensembles and (gp_layer or het_layer):
         raise ValueError("--ensembles is an ensemble of linear heads: give it without --gp_layer / --het_layer")
+    mcd = check_mcd_flags(args)
     ens_heads = getattr(args, "ens_heads", None)
     if ens_heads is not None:
         if not args.eval:
@@ -659,7 +716,8 @@ def main(args):
 
     ckpt = torch.load(args.finetune, map_location="cpu", weights_only=False)
     print("Load ckpt from %s" % args.finetune)
-    encoder = build_probe_encoder(args.model, args.target_layer, img_size=args.input_size, **encoder_kwargs(ckpt))
+    drop_kw = {"attn_drop_rate": args.attn_drop_rate} if hasattr(args, "attn_drop_rate") else {}
+    encoder = build_probe_encoder(args.model, args.target_layer, img_size=args.input_size, **encoder_kwargs(ckpt), **drop_kw)
     unused = load_encoder_checkpoint(encoder, ckpt, args.model_key, args.model_prefix)
     print(f"encoder: {encoder.depth} blocks, {len(unused)} checkpoint entries not part of it")
     encoder.to(device)
@@ -688,6 +746,10 @@ def main(args):
     elif laplace:
         from uncertainty_vit_amd.lap_probe import LaplaceProbe
         probe = LaplaceProbe(encoder, args.nb_classes, smoothing=args.smoothing)
+    elif mcd:
+        from uncertainty_vit_amd.mcd_probe import MCDropoutProbe
+        probe = MCDropoutProbe(encoder, args.nb_classes, passes=mcd, layers=getattr(args, "mc_dropout_layers", 0),
+                               combine=getattr(args, "mc_combine", "logits"), seed=getattr(args, "mc_seed", 0), smoothing=args.smoothing)
     else:
         probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
     print("Trainable weights: %s" % [n for n, p in probe.named_parameters() if p.requires_grad])
@@ -705,6 +767,8 @@ def main(args):
     gp_eval = {"variance": True, "mean_field": getattr(args, "gp_mean_field", 0.0)} if gp_layer else {"variance": True} if het_layer else {}
     if ensembles:
         gp_eval = {"members": True, "uncertainty": True}
+    if mcd:
+        gp_eval = {"uncertainty": True}
     if detection:
         gp_eval["detection"] = True
         if hasattr(args, "ood_data_path"):
@@ -816,6 +880,8 @@ def main(args):
             print(het_variance_line(stats))
         if ensembles:
             print("\n".join(ens_lines(stats)))
+        if mcd:
+            print("\n".join(mcd_lines(stats, encoder.depth, encoder.attn_drop_rate)))
         if calibration:
             print(calibration_line(stats))
         if detection:
@@ -824,10 +890,11 @@ def main(args):
             stats["conformal_fit"] = cp_fit
             stats["conformal"] = probe.evaluate_conformal(DevicePrefetcher(loader_val, device), **cp_temp, **cp_kw)["conformal"]
             print("\n".join(conformal_lines(cp_fit, stats["conformal"])))
-        if (extra_keys or ensembles or detection or ts_mode or conformal or laplace) and args.output_dir:
+        if (extra_keys or ensembles or mcd or detection or ts_mode or conformal or laplace) and args.output_dir:
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
                                     **(ens_log_entries(stats) if ensembles else {}),
+                                    **(mcd_log_entries(stats) if mcd else {}),
                                     **(detection_log_entries(stats["detection"]) if detection else {}),
                                     **(temperature_log_entries(stats, ts_fit) if ts_mode else {}),
                                     **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {}),
@@ -881,6 +948,8 @@ def main(args):
             print(het_variance_line(stats))
         if ensembles:
             print("\n".join(ens_lines(stats)))
+        if mcd:
+            print("\n".join(mcd_lines(stats, encoder.depth, encoder.attn_drop_rate)))
         if calibration:
             print(calibration_line(stats))
         print(f"Epoch {epoch}: loss: {log.loss.global_avg:.4f}  lr: {log.lr.value:.8f}  acc1: {stats['acc1']:.3f}  acc5: {stats['acc5']:.3f}")
@@ -890,6 +959,7 @@ def main(args):
                 f.write(json.dumps({"epoch": epoch, "train_loss": log.loss.global_avg, "train_lr": log.lr.value,
                                     **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
                                     **(ens_log_entries(stats) if ensembles else {}),
+                                    **(mcd_log_entries(stats) if mcd else {}),
                                     **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {})})
                         + "\n")
     print("Training time %.0f s" % (time.time() - t0))

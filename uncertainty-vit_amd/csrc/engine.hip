@@ -140,6 +140,10 @@ struct uvit_engine {
     int S;                 // streams: 1 or 2
     GemmTune tune;         // launch tuning of this engine's GEMMs (uvit_engine_set_tuning)
     int cur_B;             // batch of the last forward
+    // the "tail valid" record: the weight set and batch of the uvit_engine_forward_features whose X[0..depth] are still in the workspace
+    // (uvit_engine_forward_tail reads one of them); -1 after a training step, a failed forward or tail, or on a fresh engine.
+    // tail_first: the lowest block a tail has started at since that forward (depth: none yet) -- X[l] for l > tail_first is a tail's
+    int tail_which = -1, tail_B = 0, tail_first = 0;
     // workspace
     bf16* cols;
     float* X[UVIT_MAX_DEPTH + 1];
@@ -800,9 +804,34 @@ extern "C" int uvit_engine_forward_features(uvit_engine* e, int which, const flo
                                             int train_dropout, uint32_t seed, uint32_t it, uvit_stream stream) {
     if (!e || !images || (which != 0 && which != 1)) return UVIT_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
+    e->tail_which = -1;
     if (mask) CHECK(uvit_mask_compact_launch(mask, e->rowidx, e->count, batch, e->P, s));
     const FwdPass drop_in = fwd_pass(e, PASS_DENSE, which, batch, Draw{train_dropout != 0, seed, it}, nullptr, s);
-    return run_forward(e, drop_in, images, mask);
+    CHECK(run_forward(e, drop_in, images, mask));
+    e->tail_which = which; e->tail_B = batch; e->tail_first = e->cfg.depth;
+    return UVIT_OK;
+}
+
+// Blocks first_layer .. depth-1 again, from the X[first_layer] the last uvit_engine_forward_features left: the stochastic passes of
+// MC-dropout.  The pass is the drop-in forward's with two differences: no im2col / embed, and never a drop-path
+// draw (the reference's enable_dropout switches Dropout modules to train mode and leaves DropPath in eval).  The attention seed and the
+// layer index are fwd_pass's and forward_layer's, so layer l draws the masks it draws in a full forward at (seed, it).
+extern "C" int uvit_engine_forward_tail(uvit_engine* e, int which, int batch, int first_layer, int train_dropout, uint32_t seed,
+                                        uint32_t it, uvit_stream stream) {
+    if (!e || (which != 0 && which != 1)) return UVIT_ERR_ARG;
+    if (e->S != 1) return UVIT_ERR_SHAPE;                                     // the base model only
+    if (first_layer < 0 || first_layer >= e->cfg.depth) return UVIT_ERR_ARG;
+    if (e->tail_which != which || e->tail_B != batch || batch < 1 || batch > e->B) return UVIT_ERR_ARG;      // no forward to continue
+    if (first_layer > e->tail_first) return UVIT_ERR_ARG;     // X[first_layer] is an earlier tail's by now, not the forward's
+    hipStream_t s = (hipStream_t)stream;
+    FwdPass p = fwd_pass(e, PASS_DENSE, which, batch, Draw{train_dropout != 0, seed, it}, nullptr, s);
+    p.dp_on = false;
+    // biasP of this weight set is the forward's (nothing between the two calls writes it); X[first_layer] is only read
+    e->tail_which = -1;                                       // a launch that fails midway leaves no stream to continue
+    for (int l = first_layer; l < e->cfg.depth; ++l)
+        CHECK(forward_layer(e, p, l, e->X[l], e->XM[l], e->X[l + 1], e->acts[l]));
+    e->tail_which = which; e->tail_first = first_layer;
+    return UVIT_OK;
 }
 
 // final norm (shared) + drop cls + masked-row gather + per-stream head (modeling_cyclical.py:207,215-225)
@@ -886,6 +915,7 @@ extern "C" int uvit_step_begin(uvit_engine* e, const float* images, const int64_
     hipStream_t s = (hipStream_t)stream;
     const int Bc = e->B, BP = e->BP, C = e->C;
     Layout& lo = e->lo;
+    e->tail_which = -1;      // the step's passes overwrite the residual streams a tail would continue
     // every gradient is accumulated (split-K wgrad atomics, bias/LN/gamma column sums): zero the arena once per step.
     // With two streams the ~440 MB of memsets ride on the second stream ahead of the teacher forward (which has slack
     // against the student forward); their first consumers run after the ev_teacher join below.

@@ -404,6 +404,7 @@ class VisionTransformerForCyclicalTraining(nn.Module):
                                                  C.c_uint32(int(torch.initial_seed()) & 0xFFFFFFFF),
                                                  C.c_uint32(getattr(self, "_fwd_count", 0)), cur_stream()), "forward_features")
         self._fwd_count = getattr(self, "_fwd_count", 0) + 1
+        self._fwd_batch = B
         N = self.patch_embed.num_patches + 1
         if self._two_stream:
             if layer_results == "end":
@@ -417,6 +418,23 @@ class VisionTransformerForCyclicalTraining(nn.Module):
         if layer_results == "fc":
             return [e.ws_tensor("x", i + 1, (B, N, self.embed_dim)) - e.ws_tensor("xm", i, (B, N, self.embed_dim))
                     for i in range(self.depth)]
+        return e
+
+    def forward_tail(self, first_layer, seed, it, dropout=True):
+        """Blocks first_layer .. depth-1 of the last forward_features once more, from the residual stream that forward left in front
+        of block first_layer (uvit_engine_forward_tail): with `dropout`, under the attention-dropout masks of a training-mode forward
+        at (seed, it), whatever .train() / .eval() says; never drop-path.  The stochastic passes of MC-dropout: callable in .eval(),
+        does not advance the forward counter.  Returns the engine, whose "x" buffers behind first_layer hold the new pass.  The engine
+        refuses a call that no forward_features precedes (or that a training step has come between), and a first_layer above that of
+        an earlier tail since the forward: the residual stream in front of that block is then the earlier tail's, not the forward's."""
+        if self._two_stream:
+            raise NotImplementedError("forward_tail re-runs the base model; the two-stream (mean, covariance) model is not supported")
+        e = self._engine
+        if e is None or not getattr(self, "_fwd_batch", 0):
+            raise native.UvitError("forward_tail continues a forward_features: there has been none")
+        check(lib().uvit_engine_forward_tail(e.h, 0, self._fwd_batch, int(first_layer), 1 if dropout else 0,
+                                             C.c_uint32(int(seed) & 0xFFFFFFFF), C.c_uint32(int(it) & 0xFFFFFFFF), cur_stream()),
+              "forward_tail")
         return e
 
     def forward(self, x, bool_masked_pos, return_all_tokens=False, layer_results=None):

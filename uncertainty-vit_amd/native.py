@@ -128,6 +128,7 @@ _PROTOTYPES = {
     "uvit_engine_destroy": (None, [_vp]),
     "uvit_engine_sync_shadows": (_i, [_vp, _i, _vp]),
     "uvit_engine_forward_features": (_i, [_vp, _i, _vp, _vp, _i, _i, _u32, _u32, _vp]),
+    "uvit_engine_forward_tail": (_i, [_vp, _i, _i, _i, _i, _u32, _u32, _vp]),
     "uvit_engine_head": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "uvit_engine_ws_ptr": (_vp, [_vp, C.c_char_p, _i]),
     "uvit_engine_compact_rows": (_i, [_vp]),
@@ -244,6 +245,9 @@ _PROTOTYPES = {
     "uvit_op_knn_scores": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, C.c_double, _vp]),
     "uvit_op_vim_scores_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "uvit_op_vim_scores": (_i, [_vp, _vp, _vp, C.c_double] + [_vp] * 7 + [_i64, _i, _i, _i, _i, _vp]),
+    "uvit_op_mcd_state_bytes": (_i64, [_i, _i]),
+    "uvit_op_mcd_accumulate": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "uvit_op_mcd_finalize": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
