@@ -892,6 +892,38 @@ int uvit_op_mcd_accumulate(const float* logits, void* state, int first, int B, i
  * read. */
 int uvit_op_mcd_finalize(const void* state, int T, int mode, float* z, double* unc, int B, int K, uvit_stream stream);
 
+/* ---- Learned layer weights over every block's pooled output (csrc/layerweights.hip) ----
+ * The reference's --learn_layer_weights (modeling_finetune.py:433-436, 499-510): every block's residual stream is pooled, and a
+ * trained softmax over L scalars mixes the pooled vectors in front of the head.  All fp32 in memory, no float atomics: every sum has
+ * one owner and a fixed order, so the same input gives the same bits on every run.  Every call checks its arguments before it touches
+ * the device (UVIT_ERR_ARG for a NULL required pointer, a mode or a layernorm outside {0, 1}, a negative or NaN eps, a misaligned
+ * scratch; UVIT_ERR_SHAPE for a size outside the stated conditions; outputs untouched) and is asynchronous on `stream`.
+ * Conditions of all of them: 1 <= B <= 65535, 1 <= L <= UVIT_MAX_DEPTH, C % 4 == 0, 4 <= C <= 2048; the pool: N >= 1. */
+int64_t uvit_op_lw_pool_ws_bytes(int B, int L, int N, int C);     /* < 0: the UVIT_ERR_* of the call */
+/* pooled (B, L, C) from the residual streams x_layers[l] (B, N, C), l = 0 .. L-1: x_layers is a HOST array of L device pointers, in any
+ * address order, none NULL; they travel to the kernels by value (nothing is allocated or copied, the array may be freed on return).
+ *   mode 0: the mean over tokens 0 .. N-1, the cls token included: partial column sums per (token slice, layer, sample) into scratch
+ *           (uvit_op_lw_pool_ws_bytes bytes), added in slice order by one wave per (sample, layer) row and divided by N (an IEEE
+ *           division); two launches for all layers.
+ *   mode 1: token 0 of every layer; no other token is read, scratch is not touched; one launch.
+ *   layernorm 1: each (b, l) row becomes (p - mean) / sqrt(var + eps), no affine, two-pass variance (F.layer_norm; the reference passes
+ *           eps = 1e-5, not the encoder's). */
+int uvit_op_lw_pool(const float* const* x_layers, int L, float* pooled, float* scratch, int B, int N, int C, int mode, int layernorm,
+                    float eps, uvit_stream stream);
+/* w = softmax(log_w) over L values in fp32 (the maximum subtracted, the exponentials added by the xor tree of one wave, one division
+ * each); feat[b] (C) = sum_l w_l pooled[b, l], an fma chain in layer order from 0, one wave per row.  w_out (L, nullable) receives w.
+ * A weight of exactly 1 returns its layer's bits; equal log-weights at L = 2^k give exactly 1 / L. */
+int uvit_op_lw_combine(const float* pooled, const float* log_w, float* feat, float* w_out, int B, int L, int C, uvit_stream stream);
+/* dfeat (B, C) = dlogits (B, K) . W (K, C), the third contraction of the head beside uvit_op_probe_logits and uvit_op_probe_head_grad:
+ * 64 x 64 LDS-tiled FMA, the reduction over k ascending in tiles of 16 whose sums are added to the running sum; overwritten.
+ * B >= 1, K >= 1, C % 4 == 0, C >= 4. */
+int uvit_op_probe_input_grad(const float* dlogits, const float* W, float* dfeat, int B, int K, int C, uvit_stream stream);
+/* dlog_w (L) fp32, overwritten: with g_l = sum_{b, c} dfeat[b, c] pooled[b, l, c] in double (per row: one wave, per lane over its
+ * columns ascending, then the xor tree; then lane l adds the rows in row order) and w of uvit_op_lw_combine (the same bits),
+ * dlog_w_l = (float)(w_l (g_l - sum_j w_j g_j)).  scratch: B L doubles, 8-byte aligned. */
+int uvit_op_lw_grad(const float* dfeat, const float* pooled, const float* log_w, float* dlog_w, double* scratch, int B, int L, int C,
+                    uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,18 @@ mcd_aleatoric, mcd_mi, mcd_var, mcd_disagreement), --ts_*, --cp_*, --perturbatio
 deterministic feature) work on the combined logits.  After `* Acc@1` the run prints `* MC-dropout passes <T> layers <n> of <L> rate
 <p> entropy ... expected ... MI ... variance ... disagreement ...` and `* Deterministic Acc@1 ...`; log.txt gains
 `test_mcd_{total,aleatoric,mi,var,disagreement,det_acc1,passes}`.
+
+`--learn_layer_weights` (the reference's flag; exclusive with --gp_layer, --het_layer, --ensembles, --laplace and
+--mc_dropout_forwards) probes every block at once (uncertainty-vit_amd/lw_probe.py): the encoder is built at
+full depth (a given --target_layer is ignored with one printed line, as the reference does), every block's output is pooled -- the mean
+over ALL its tokens, the cls token included -- and a trained softmax over `depth` scalars, `layer_log_weights`, mixes the pooled
+vectors in front of the nn.Linear; no LayerNorm follows the mix.  `--layernorm_before_combine` normalises every block's pooled vector
+(no affine, eps 1e-5) before the mix, `--use_cls` pools token 0 instead of the mean; both are refused without --learn_layer_weights
+(the reference's --use_cls alone needs a trained final norm, which is not built).  One run replaces a sweep over --target_layer, and
+the trained weights say which blocks carry the signal: every epoch and every --eval prints `* Layer weights w0 w1 ... (argmax: block
+l)` after `* Acc@1`, and log.txt gains `test_layer_weights`.  Checkpoints hold `head.weight`, `head.bias` and `layer_log_weights`;
+--resume refuses one without the third key or of another depth.  --calibration, --detection / --ood_data_path, --ts_*, --cp_*,
+--maha_*, --knn_*, --vim_* and --perturbation_path work unchanged on the mixed feature and its logits.
 """
 import argparse
 import json
@@ -266,6 +278,12 @@ def get_args(argv=None):
     a("--mc_combine", type=str, choices=["logits", "probs"], default=argparse.SUPPRESS,
       help="combined logits: the mean of the passes' logits (default, the reference's) or the log of the mean of their softmaxes")
     a("--mc_seed", type=int, default=argparse.SUPPRESS, help="seed of the dropout masks (default 0)")
+    a("--learn_layer_weights", action="store_true", default=argparse.SUPPRESS,
+      help="pool every block's output and train a softmax over `depth` scalars that mixes them in front of the head; supersedes --target_layer")
+    a("--layernorm_before_combine", action="store_true", default=argparse.SUPPRESS,
+      help="with --learn_layer_weights: LayerNorm (no affine, eps 1e-5) of every block's pooled vector before the mix")
+    a("--use_cls", action="store_true", default=argparse.SUPPRESS,
+      help="with --learn_layer_weights: pool the cls token of every block instead of the mean over all its tokens")
     return p.parse_args(argv)
 
 
@@ -322,6 +340,25 @@ def check_mcd_flags(args):
     if getattr(args, "mc_dropout_layers", 0) < 0:
         raise ValueError(f"--mc_dropout_layers must be >= 0, got {args.mc_dropout_layers}")
     return T
+
+
+def check_lw_flags(args):
+    """Whether the run learns layer weights (--learn_layer_weights).  --layernorm_before_combine and --use_cls belong to it; it mixes
+    the features of the linear head: --gp_layer, --het_layer, --ensembles, --laplace and --mc_dropout_forwards are other heads."""
+    if not getattr(args, "learn_layer_weights", False):
+        if getattr(args, "layernorm_before_combine", False) or getattr(args, "use_cls", False):
+            raise ValueError("--layernorm_before_combine / --use_cls belong to the layer-weighted probe: give --learn_layer_weights "
+                             "(--use_cls alone needs a trained final norm, which is not built)")
+        return False
+    if any(getattr(args, k, False) for k in ("gp_layer", "het_layer", "ensembles", "laplace", "mc_dropout_forwards")):
+        raise ValueError("--learn_layer_weights mixes the features of the linear head: give it without --gp_layer / --het_layer / "
+                         "--ensembles / --laplace / --mc_dropout_forwards")
+    return True
+
+
+def layer_weights_line(weights):
+    """The line behind `* Acc@1`: softmax(layer_log_weights) in block order and the block with the largest weight."""
+    return "* Layer weights {} (argmax: block {})".format(" ".join(f"{w:.4f}" for w in weights), max(range(len(weights)), key=weights.__getitem__))
 
 
 def mcd_lines(stats, depth, rate):
@@ -702,7 +739,10 @@ def main(args):
     if ensembles and (gp_layer or het_layer):
         raise ValueError("--ensembles is an ensemble of linear heads: give it without --gp_layer / --het_layer")
     mcd = check_mcd_flags(args)
-    ens_heads = getattr(args, "ens_heads", None)
+    lw = check_lw_flags(args)
+    if lw and args.target_layer != -1:            # run_class_finetuning.py:520: the flag supersedes --target_layer, the encoder is not cut
+        print("--learn_layer_weights supersedes --target_layer %d: the encoder keeps every block" % args.target_layer)
+    ens_heads =getattr(args, "ens_heads", None)
     if ens_heads is not None:
         if not args.eval:
             raise ValueError("--ens_heads assembles an ensemble for an evaluation: give --eval")
@@ -717,7 +757,7 @@ def main(args):
     ckpt = torch.load(args.finetune, map_location="cpu", weights_only=False)
     print("Load ckpt from %s" % args.finetune)
     drop_kw = {"attn_drop_rate": args.attn_drop_rate} if hasattr(args, "attn_drop_rate") else {}
-    encoder = build_probe_encoder(args.model, args.target_layer, img_size=args.input_size, **encoder_kwargs(ckpt), **drop_kw)
+    encoder = build_probe_encoder(args.model, -1 if lw else args.target_layer, img_size=args.input_size, **encoder_kwargs(ckpt), **drop_kw)
     unused = load_encoder_checkpoint(encoder, ckpt, args.model_key, args.model_prefix)
     print(f"encoder: {encoder.depth} blocks, {len(unused)} checkpoint entries not part of it")
     encoder.to(device)
@@ -750,6 +790,10 @@ def main(args):
         from uncertainty_vit_amd.mcd_probe import MCDropoutProbe
         probe = MCDropoutProbe(encoder, args.nb_classes, passes=mcd, layers=getattr(args, "mc_dropout_layers", 0),
                                combine=getattr(args, "mc_combine", "logits"), seed=getattr(args, "mc_seed", 0), smoothing=args.smoothing)
+    elif lw:
+        from uncertainty_vit_amd.lw_probe import LayerWeightedProbe
+        probe = LayerWeightedProbe(encoder, args.nb_classes, smoothing=args.smoothing, use_cls=getattr(args, "use_cls", False),
+                                   layernorm_before_combine=getattr(args, "layernorm_before_combine", False))
     else:
         probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
     print("Trainable weights: %s" % [n for n, p in probe.named_parameters() if p.requires_grad])
@@ -882,6 +926,9 @@ def main(args):
             print("\n".join(ens_lines(stats)))
         if mcd:
             print("\n".join(mcd_lines(stats, encoder.depth, encoder.attn_drop_rate)))
+        if lw:
+            stats["layer_weights"] = probe.layer_weights().cpu().tolist()
+            print(layer_weights_line(stats["layer_weights"]))
         if calibration:
             print(calibration_line(stats))
         if detection:
@@ -890,11 +937,12 @@ def main(args):
             stats["conformal_fit"] = cp_fit
             stats["conformal"] = probe.evaluate_conformal(DevicePrefetcher(loader_val, device), **cp_temp, **cp_kw)["conformal"]
             print("\n".join(conformal_lines(cp_fit, stats["conformal"])))
-        if (extra_keys or ensembles or mcd or detection or ts_mode or conformal or laplace) and args.output_dir:
+        if (extra_keys or ensembles or mcd or lw or detection or ts_mode or conformal or laplace) and args.output_dir:
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
                                     **(ens_log_entries(stats) if ensembles else {}),
                                     **(mcd_log_entries(stats) if mcd else {}),
+                                    **({"test_layer_weights": stats["layer_weights"]} if lw else {}),
                                     **(detection_log_entries(stats["detection"]) if detection else {}),
                                     **(temperature_log_entries(stats, ts_fit) if ts_mode else {}),
                                     **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {}),
@@ -950,6 +998,9 @@ def main(args):
             print("\n".join(ens_lines(stats)))
         if mcd:
             print("\n".join(mcd_lines(stats, encoder.depth, encoder.attn_drop_rate)))
+        if lw:
+            stats["layer_weights"] = probe.layer_weights().cpu().tolist()
+            print(layer_weights_line(stats["layer_weights"]))
         if calibration:
             print(calibration_line(stats))
         print(f"Epoch {epoch}: loss: {log.loss.global_avg:.4f}  lr: {log.lr.value:.8f}  acc1: {stats['acc1']:.3f}  acc5: {stats['acc5']:.3f}")
@@ -960,6 +1011,7 @@ def main(args):
                                     **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
                                     **(ens_log_entries(stats) if ensembles else {}),
                                     **(mcd_log_entries(stats) if mcd else {}),
+                                    **({"test_layer_weights": stats["layer_weights"]} if lw else {}),
                                     **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {})})
                         + "\n")
     print("Training time %.0f s" % (time.time() - t0))

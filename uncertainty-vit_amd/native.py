@@ -248,6 +248,11 @@ _PROTOTYPES = {
     "uvit_op_mcd_state_bytes": (_i64, [_i, _i]),
     "uvit_op_mcd_accumulate": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "uvit_op_mcd_finalize": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "uvit_op_lw_pool_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "uvit_op_lw_pool": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "uvit_op_lw_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "uvit_op_probe_input_grad": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "uvit_op_lw_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
