@@ -158,7 +158,7 @@ int uvit_engine_head(uvit_engine* e, int which, int all_tokens, float* out, int3
 
 /* Device pointers into the workspace after a forward: name in {"x" (layer 0..depth residual stream
  * (B,N,C) f32), "xm" (after the attention branch), "loss", "grad_norm", "targets", "outputs", "count"};
- * two-stream model: also "x_cov", "xm_cov", "targets_cov", "outputs_cov". */
+ * two-stream model: also "x_cov", "xm_cov", "targets_cov", "outputs_cov"; "poisoned" (one int32: the sticky flag of a skipped step). */
 void* uvit_engine_ws_ptr(uvit_engine* e, const char* name, int layer);
 /* Rows the last training step ran its last block's MLP on (uvit_step_params.n_rows_hint): 0 = every token row. */
 int uvit_engine_compact_rows(uvit_engine* e);
@@ -207,6 +207,15 @@ int uvit_engine_set_streams(uvit_engine* e, int dual);
  * are multiplied by 0, as the reference does.  Same results either way (bench.py reports both rates).  Environment UVIT_DP_ROWS=0
  * selects 0 at engine creation. */
 int uvit_engine_set_drop_path_rows(uvit_engine* e, int on);
+/* on = 0 (default): the LayerScale gradients of a training step come from the block's weight gradients,
+ *   dgamma_j = (sum_k W_jk dW_jk + b_j db_j) / gamma_j        (W: the bf16 weight the forward multiplied by; see uvit_op_ls_dgamma)
+ * so the student forward does not store the Block branches' pre-LayerScale outputs and backward does not read them back.  A gamma entry
+ * that is exactly 0 makes the quotient 0 / 0: that entry's gradient is set to 0 and the engine's sticky `poisoned` flag is raised, so the
+ * step (and every later one) leaves the weights untouched instead of training on a wrong gradient.  on = 1: the forward saves the branch
+ * outputs and the LayerScale backward sums dgamma += e * y from them, which also serves gamma == 0.  Takes effect at the next
+ * uvit_step_begin; every other gradient is computed by the same launches either way.  Environment UVIT_LS_SAVED_Y=1 selects 1 at engine
+ * creation. */
+int uvit_engine_set_ls_saved_y(uvit_engine* e, int on);
 /* The host side of those lists, callable without a GPU: kept samples per (layer, draw) for one step -- out[draws_per_block * layer + k],
  * draws_per_block = 2 (base: attn, mlp) or 4 (two-stream: mean attn, mean mlp, cov attn, cov mlp) -- from the counter-based hash the device
  * draws its DropPath multipliers with (rates linspace(0, drop_path_rate, depth), modeling_cyclical.py:94-96).  Pure host arithmetic. */
@@ -329,6 +338,8 @@ int uvit_op_ln_fwd_walk(const float* x, const float* w, const float* b, void* y_
                         uvit_stream stream);
 /* The LayerScale + DropPath backward of the branch behind a row-wise backward pass over the residual-stream gradient d
  * (modeling_finetune.py:295-298): e = d * rowscale[sample], dy = bf16(e * gamma), dgamma += e * y, dbias += dy (the stored bf16).
+ * y = NULL together with dgamma = NULL (one without the other: UVIT_ERR_ARG): y is not read and dgamma is not summed
+ * (uvit_op_ls_dgamma computes it from the weight gradient); dy and dbias are what the call with y gives, bit for bit.
  * tokens = rows per sample.  LayerNorm backward only: pos (sample -> compact slot of dy, -1 = dropped: writes nothing, adds nothing;
  * NULL = dense); cnt (samples walk: kept rows; the pad rows cnt .. roundup(pad_base + cnt, 64) - pad_base of dy are zero-filled, and the
  * same rows of pad2 [rows][pad2_cols], pad2_cols % 4 == 0). */
@@ -347,6 +358,13 @@ int uvit_op_ln_bwd_walk(const void* dy_bf16, const float* x, const float* mean, 
  * residual-stream row rowidx[r], rows r >= *count (up to M) get zeros. */
 int uvit_op_ls_bwd(const float* dx, const uvit_ls_rider* rider, int M, int C, int nrep, int64_t rep_stride, const int32_t* rowidx,
                    const int32_t* count, uvit_stream stream);
+/* LayerScale gradient from the weight gradient: dgamma[j] += sum over the nsets (1 or 2) sets of
+ * (sum_k W[j][k] * dW[j][k] + b[j] * sum_r db[r * rep_stride + j]) / gamma[j],  j < C, k < K, r < nrep.
+ * W (bf16) and dW (f32) are [C][K] row-major, K % 8 == 0, nrep <= 64 (UVIT_ERR_SHAPE otherwise).  fp32 accumulation, one wave per j, no
+ * atomics.  gamma[j] == 0: dgamma[j] = 0 and *flag = 1 (flag is never cleared). */
+typedef struct uvit_ls_dgamma_set { const void* W_bf16; const float* dW; const float* b; const float* db; } uvit_ls_dgamma_set;
+int uvit_op_ls_dgamma(const uvit_ls_dgamma_set* sets, int nsets, const float* gamma, float* dgamma, int32_t* flag, int C, int K,
+                      int nrep, int64_t rep_stride, uvit_stream stream);
 /* out[c] += sum over the M rows of y[m][col0 + c], c < ncols (ld, col0, ncols multiples of 8) */
 int uvit_op_colsum(const void* y_bf16, int ld, int col0, int ncols, int M, float* out, int nrep, int64_t rep_stride, uvit_stream stream);
 /* out[i] += sum_r rep[r * stride + i], i < n (n, stride multiples of 4) */

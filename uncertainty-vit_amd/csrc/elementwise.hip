@@ -132,7 +132,8 @@ __device__ __forceinline__ void block_col_atomic(float4 (&acc)[NV], float* out, 
 // LayerScale + DropPath backward (modeling_finetune.py:295-298):
 //   dy = dx * gamma * dp[b]   (bf16, gradient of the Linear output y)
 //   dgamma += sum_m dx * dp * y ;  dbias += sum_m dy
-template <int NV>
+// LSY = false (y null): dy and dbias only, dgamma comes from the weight gradient (ls_dgamma_kernel)
+template <int NV, bool LSY>
 __global__ __launch_bounds__(256)
 void ls_bwd_kernel(const float* __restrict__ dx, const bf16* __restrict__ y, const float* __restrict__ gamma,
                    const float* __restrict__ rowscale, bf16* __restrict__ dy, float* __restrict__ dgamma,
@@ -141,7 +142,8 @@ void ls_bwd_kernel(const float* __restrict__ dx, const bf16* __restrict__ y, con
     // rowidx != nullptr: COMPACT output -- row r of dy belongs to residual-stream row rowidx[r] (dx, y and the drop-path sample are taken
     // there); rows r >= *count are padding and get zeros
     __shared__ float red[4][64 * 4];
-    dgamma += (size_t)(blockIdx.x % nrep) * rep_stride; dbias += (size_t)(blockIdx.x % nrep) * rep_stride;
+    if constexpr (LSY) dgamma += (size_t)(blockIdx.x % nrep) * rep_stride;
+    dbias += (size_t)(blockIdx.x % nrep) * rep_stride;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = C >> 2;
     float4 ag[NV], ab[NV];
 #pragma unroll
@@ -158,13 +160,52 @@ void ls_bwd_kernel(const float* __restrict__ dx, const bf16* __restrict__ y, con
             if (i < nv) {
                 const float4 d = ((const float4*)(dx + (size_t)xr * C))[i];
                 const float4 g = ((const float4*)gamma)[i];
-                const bf16x4 yy = ((const bf16x4*)(y + (size_t)xr * C))[i];
-                ls_apply(d, dp, yy, g, (bf16x4*)(dy + (size_t)row * C) + i, ag[k], ab[k]);
+                if constexpr (LSY) {
+                    const bf16x4 yy = ((const bf16x4*)(y + (size_t)xr * C))[i];
+                    ls_apply(d, dp, yy, g, (bf16x4*)(dy + (size_t)row * C) + i, ag[k], ab[k]);
+                } else {
+                    ls_apply(d, dp, g, (bf16x4*)(dy + (size_t)row * C) + i, ab[k]);
+                }
             }
         }
     }
-    block_col_atomic(ag, dgamma, nv, red);
+    if constexpr (LSY) block_col_atomic(ag, dgamma, nv, red);
     block_col_atomic(ab, dbias, nv, red);
+}
+
+// LayerScale gradient from the weight gradient.  With dy = rowscale * gamma * dx (what the riders above write, and what the wgrad and
+// their dbias column sum consume) and y = a W^T + b the branch output:
+//   dgamma_j = sum_m rowscale_m dx_mj y_mj = (sum_k W_jk dW_jk + b_j db_j) / gamma_j
+// so the saved y is not needed.  One wave per output row j (rows are owned: no atomics), fp32 accumulation; W is the bf16 weight the forward
+// multiplied by, dW the fp32 gradient after the layer's wgrad, db the nrep replicated column-sum accumulators (summed here).  Up to two
+// (W, dW, b, db) sets share one gamma (the two-stream model's proj / cov_proj).  gamma_j == 0 makes dW_j: and db_j vanish as well (0 / 0):
+// the row gets 0 and *flag <- 1 (the engine's sticky `poisoned`: the step is skipped instead of silently wrong).
+__global__ __launch_bounds__(256)
+void ls_dgamma_kernel(LsDgammaSet s0, LsDgammaSet s1, int nsets, const float* __restrict__ gamma, float* __restrict__ dgamma,
+                      int* __restrict__ flag, int C, int K, int nrep, size_t rep_stride) {
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= C) return;
+    float total = 0.f;
+    for (int q = 0; q < nsets; ++q) {
+        const LsDgammaSet& t = q ? s1 : s0;
+        const bf16* w = t.W + (size_t)j * K;
+        const float* dw = t.dW + (size_t)j * K;
+        float acc = 0.f;
+        for (int k = lane * 8; k < K; k += 512) {
+            const bf16x8 wv = *(const bf16x8*)(w + k);
+            const float4 d0 = *(const float4*)(dw + k), d1 = *(const float4*)(dw + k + 4);
+            acc += bf2f(wv[0]) * d0.x; acc += bf2f(wv[1]) * d0.y; acc += bf2f(wv[2]) * d0.z; acc += bf2f(wv[3]) * d0.w;
+            acc += bf2f(wv[4]) * d1.x; acc += bf2f(wv[5]) * d1.y; acc += bf2f(wv[6]) * d1.z; acc += bf2f(wv[7]) * d1.w;
+        }
+        float db = lane < nrep ? t.db[(size_t)lane * rep_stride + j] : 0.f;      // nrep <= 64 (launcher)
+        acc = wave_sum(acc); db = wave_sum(db);
+        total += acc + t.b[j] * db;
+    }
+    if (lane == 0) {
+        const float g = gamma[j];
+        if (g == 0.f) { dgamma[j] = 0.f; *flag = 1; }
+        else dgamma[j] += total / g;
+    }
 }
 
 // out[c] += sum_m y[m][col0 + c]: lane = 8 columns (16 B), wave = 512 columns, 4 waves walk rows 4-way unrolled
@@ -428,11 +469,19 @@ int uvit_relpos_scatter_launch(const float* slab, int nslab, const int* index, f
 }
 int uvit_ls_bwd_launch(const float* dx, const LsNext& ls, int M, int C, int nrep, size_t rep_stride, hipStream_t s,
                        const int* rowidx, const int* count) {
-    if (C % 4 || C > ROW_MAXV * 256 || (rowidx && !count)) return UVIT_ERR_SHAPE;
+    if (C % 4 || C > ROW_MAXV * 256 || (rowidx && !count) || (ls.y && !ls.dgamma)) return UVIT_ERR_SHAPE;
     dispatch_nv(C, [&](auto nv) {
-        hipLaunchKernelGGL(ls_bwd_kernel<decltype(nv)::value>, dim3((M + CP_ROWS - 1) / CP_ROWS), dim3(256), 0, s, dx, ls.y, ls.gamma, ls.rowscale,
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((ls.y ? ls_bwd_kernel<NV, true> : ls_bwd_kernel<NV, false>), dim3((M + CP_ROWS - 1) / CP_ROWS), dim3(256), 0, s, dx, ls.y, ls.gamma, ls.rowscale,
                            ls.dy, ls.dgamma, ls.dbias, M, C, ls.tokens, nrep > 0 ? nrep : 1, rep_stride, rowidx, count);
     });
+    return uvit_check_launch();
+}
+int uvit_ls_dgamma_launch(const LsDgammaSet* sets, int nsets, const float* gamma, float* dgamma, int* flag, int C, int K, int nrep,
+                          size_t rep_stride, hipStream_t s) {
+    if (nsets < 1 || nsets > 2 || C < 1 || K < 8 || (K % 8) || nrep < 1 || nrep > 64) return UVIT_ERR_SHAPE;
+    hipLaunchKernelGGL(ls_dgamma_kernel, dim3((C + 3) / 4), dim3(256), 0, s, sets[0], sets[nsets - 1], nsets, gamma, dgamma, flag, C, K, nrep,
+                       rep_stride);
     return uvit_check_launch();
 }
 __global__ void rows_guard_kernel(const int* __restrict__ count, int limit, float* __restrict__ loss) {

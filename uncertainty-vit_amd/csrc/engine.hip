@@ -166,6 +166,10 @@ struct uvit_engine {
     int dpl_K[128] = {};                   // kept samples per list (2 S lists per layer), from the host's evaluation of the drop-path hash
     bool dpl_enable = true;                // uvit_engine_set_drop_path_rows
     bool dpl_on = false;                   // the current step runs with lists
+    // LayerScale gradient: false (default) = from the weight gradient (ls_dgamma_kernel), nothing of the branch outputs is saved; true = the
+    // student forward saves every branch's pre-LayerScale output (acts[l].projout / mlpout) and the riders sum dgamma from it
+    bool ls_saved_y = false;               // uvit_engine_set_ls_saved_y
+    bool ls_saved_step = false;            // ... as latched by uvit_step_begin for the step's forward and backward
     std::vector<float> dp_rates_host;
     float *loss, *gnorm; double* sumsq;
     float* wl_scratch;     // Wasserstein loss: scalars + per-row distances
@@ -334,6 +338,7 @@ extern "C" uvit_engine* uvit_engine_create(const uvit_config* cfg, const uvit_bu
     std::vector<float> rates = dp_rates_linspace(cfg->depth, cfg->drop_path_rate);
     e->dp_rates_host = rates;
     if (const char* v = getenv("UVIT_DP_ROWS")) e->dpl_enable = v[0] != '0';     // A/B switch (uvit_engine_set_drop_path_rows)
+    if (const char* v = getenv("UVIT_LS_SAVED_Y")) e->ls_saved_y = v[0] == '1';  // A/B switch and fallback (uvit_engine_set_ls_saved_y)
     // transposed-copy descriptors
     std::vector<TransposeDesc> td;
     int tiles = 0;
@@ -431,6 +436,12 @@ extern "C" int uvit_engine_set_streams(uvit_engine* e, int dual) {
 extern "C" int uvit_engine_set_drop_path_rows(uvit_engine* e, int on) {
     if (!e) return UVIT_ERR_ARG;
     e->dpl_enable = on != 0;
+    return UVIT_OK;
+}
+
+extern "C" int uvit_engine_set_ls_saved_y(uvit_engine* e, int on) {
+    if (!e) return UVIT_ERR_ARG;
+    e->ls_saved_y = on != 0;
     return UVIT_OK;
 }
 
@@ -650,6 +661,7 @@ static int forward_layer(uvit_engine* e, const FwdPass& p, int l, const float* x
     const int Bc = p.Bc, M = Bc * e->N, C = e->C, Hd = e->Hd, S = e->S;
     const size_t Mp = e->Mpad;                                   // row offset of stream 1 in the residual stream
     const bool save = p.kind == PASS_STUDENT;                    // keep what backward needs
+    const bool save_y = save && e->ls_saved_step;                // ... the branch outputs among it only on the saved-y path
     const BranchRows at = branch_rows(e, l, 0, p.rows, Bc), ml = branch_rows(e, l, 1, p.rows, Bc);
     LnFwd n1; n1.x = x_in; n1.w = w.f + o.n1w; n1.b = w.f + o.n1b; n1.y = a.ln1; n1.mean = a.mean1; n1.rstd = a.rstd1; n1.M = at.rows; n1.C = C;
     n1.eps = e->cfg.ln_eps;
@@ -676,7 +688,7 @@ static int forward_layer(uvit_engine* e, const FwdPass& p, int l, const float* x
     };
     auto prof_end = [&](bool on) { if (on) { (void)hipEventRecord(e->prof_ev[e->prof_used + 1], s); e->prof_used += 2; } };
     for (int st = 0; st < S; ++st) {
-        GemmEpi pj; pj.out = x_mid + st * Mp * C; pj.out2 = save ? a.projout + st * Mp * C : nullptr; pj.bias = w.f + o.projb[st];
+        GemmEpi pj; pj.out = x_mid + st * Mp * C; pj.out2 = save_y ? a.projout + st * Mp * C : nullptr; pj.bias = w.f + o.projb[st];
         pj.gamma = w.f + o.g1; pj.resid = x_in + st * Mp * C; pj.rowscale = dp_ptr(e, p.dp_on, l, st, 0, Bc); pj.ldo = C; pj.tokens = e->N;
         pj.rowmap = at.rowmap[st]; pj.rowcount = at.rowcnt[st];
         const bool pp = prof_begin(UVIT_PROF_PROJ, at.n[st]);
@@ -702,7 +714,7 @@ static int forward_layer(uvit_engine* e, const FwdPass& p, int l, const float* x
     CHECK(GEMM_NT(save ? EPI_GELU_DG : EPI_GELU, a.ln2, w.b + o.fc1w, ml.rows, Hd, C, C, C, &f1, s));
     prof_end(prof);
     for (int st = 0; st < S; ++st) {
-        GemmEpi f2; f2.out = x_out + st * Mp * C; f2.out2 = save ? a.mlpout + st * Mp * C : nullptr; f2.bias = w.f + o.fc2b;
+        GemmEpi f2; f2.out = x_out + st * Mp * C; f2.out2 = save_y ? a.mlpout + st * Mp * C : nullptr; f2.bias = w.f + o.fc2b;
         f2.gamma = w.f + o.g2; f2.resid = x_mid + st * Mp * C; f2.rowscale = dp_ptr(e, p.dp_on, l, st, 1, Bc); f2.ldo = C; f2.tokens = e->N;
         f2.rowmap = ml.rowmap[st]; f2.rowcount = ml.rowcnt[st];
         const bool pf2 = prof_begin(UVIT_PROF_FC2, ml.n[st]);
@@ -886,6 +898,7 @@ extern "C" void* uvit_engine_ws_ptr(uvit_engine* e, const char* name, int layer)
     if (n == "outputs_cov" && e->S == 2) return e->outputs[1];
     if (n == "count") return e->count;
     if (n == "dx") return e->dXa;
+    if (n == "poisoned") return e->poisoned;
     return nullptr;
 }
 
@@ -926,6 +939,7 @@ extern "C" int uvit_step_begin(uvit_engine* e, const float* images, const int64_
     CHECK(uvit_zero_launch(e->loss, 64 * sizeof(float), ts));
     CHECK(uvit_zero_launch(e->dXa, e->rows_alloc() * C * sizeof(float), ts));
     e->slab_started = false; e->bwd_next = e->cfg.depth - 1;
+    e->ls_saved_step = e->ls_saved_y;
     // the last block's MLP on the masked rows only (see forward_layer): base model, a row bound from the host, and fewer rows than tokens
     e->compact_R = 0;
     if (e->S == 1 && hp->n_rows_hint > 0) {
@@ -1036,10 +1050,12 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
     //  rides in the LayerNorm 1 backward of the layer above; in the two-stream model that kernel is launched once per stream, because
     //  drop-path scales and the proj bias differ per stream)
     // the MLP branch of layer `layer` as the rider of a row-wise backward over stream st: its dY1 is compact by the branch's rows `br`
+    const bool saved_y = e->ls_saved_step;      // false: the riders leave dgamma to ls_dgamma (below, behind the wgrad)
     auto mlp_rider = [&](int layer, int st, const BranchRows& br, bf16* dY) {
         const LayerOff& L = e->lo.L[layer];
-        LsNext n; n.y = e->acts[layer].mlpout + st * Mp * C; n.gamma = pf + L.g2; n.rowscale = dp_ptr(e, dp_on, layer, st, 1, e->B);
-        n.dy = dY + br.off[st] * C; n.dgamma = RP(L.g2); n.dbias = RP(L.fc2b); n.tokens = e->N;
+        LsNext n; n.gamma = pf + L.g2; n.rowscale = dp_ptr(e, dp_on, layer, st, 1, e->B);
+        n.dy = dY + br.off[st] * C; n.dbias = RP(L.fc2b); n.tokens = e->N;
+        if (saved_y) { n.y = e->acts[layer].mlpout + st * Mp * C; n.dgamma = RP(L.g2); }
         return n;
     };
     if (l == e->cfg.depth - 1)
@@ -1060,8 +1076,9 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
         LnBwd b; b.dy = e->dLN + ml.off[st] * C; b.x = e->XM[l] + eo; b.mean = a.mean2 + ml.off[st]; b.rstd = a.rstd2 + ml.off[st]; b.w = pf + o.n2w;
         b.dres = e->dXa + eo; b.dx = e->dXb + eo; b.dw = RP(o.n2w); b.db = RP(o.n2b); b.C = C; b.nrep = NREP; b.rep_stride = e->n_nd;
         LsNext& n = b.next;
-        n.y = a.projout + eo; n.gamma = pf + o.g1; n.rowscale = dp_ptr(e, dp_on, l, st, 0, e->B); n.dy = dY2 + at.off[st] * C;
-        n.dgamma = RP(o.g1); n.dbias = RP(o.projb[st]); n.tokens = e->N; n.pos = at.d[st].pos;
+        n.gamma = pf + o.g1; n.rowscale = dp_ptr(e, dp_on, l, st, 0, e->B); n.dy = dY2 + at.off[st] * C;
+        n.dbias = RP(o.projb[st]); n.tokens = e->N; n.pos = at.d[st].pos;
+        if (saved_y) { n.y = a.projout + eo; n.dgamma = RP(o.g1); }
         if (ln2_samples) { b.M = M; b.pos = ml.d[st].pos; n.cnt = at.d[st].cnt; if (at.mode == ROWS_LIST) { n.pad2 = dqkv; n.pad2_cols = 3 * C; } }
         else { b.M = ml.n[st]; b.rowidx = ml.rowmap[st]; b.count = ml.rowcnt[st]; }
         CHECK(uvit_ln_bwd_launch(b, s));
@@ -1098,6 +1115,19 @@ extern "C" int uvit_step_backward_layer(uvit_engine* e, int l, const uvit_step_p
     e->slab_started = true;
     if (e->dual) { HIPCHECK(hipEventRecord(e->ev_x, s)); HIPCHECK(hipStreamWaitEvent(ws, e->ev_x, 0)); }    // every dY of the block is there
     CHECK(wgrad(e, wg, nwg, ws));
+    if (!saved_y) {
+        // LayerScale gradients of the block from its weight gradients (ls_dgamma_kernel), into replica 0 of gamma's accumulators (which
+        // uvit_reduce_replicas_launch folds with the rest).  Both riders -- the attention branch's in the LayerNorm 2 backward above, the MLP
+        // branch's in the layer above's LayerNorm 1 backward / the top layer's ls_bwd -- precede ev_x, so their dbias sums are complete; W is
+        // this step's bf16 shadow (AdamW rewrites it in uvit_step_update).  proj differs per stream and gamma_1 is shared: both streams' terms
+        // are summed; fc2 and gamma_2 are shared, with one stacked dW.
+        const bf16* wb = (const bf16*)e->buf.params_bf16;
+        LsDgammaSet aset[2];
+        for (int st = 0; st < S; ++st) aset[st] = LsDgammaSet{wb + o.projw[st], g + o.projw[st], pf + o.projb[st], RP(o.projb[st])};
+        CHECK(uvit_ls_dgamma_launch(aset, S, pf + o.g1, RP(o.g1), e->poisoned, C, C, NREP, e->n_nd, ws));
+        const LsDgammaSet mset{wb + o.fc2w, g + o.fc2w, pf + o.fc2b, RP(o.fc2b)};
+        CHECK(uvit_ls_dgamma_launch(&mset, 1, pf + o.g2, RP(o.g2), e->poisoned, C, Hd, NREP, e->n_nd, ws));
+    }
     if (e->dual) HIPCHECK(hipEventRecord(e->ev_wdone[l], ws));
     GemmEpi d4; d4.out = e->dLN; d4.ldo = C;
     CHECK(GEMM_NT(EPI_BF16, dqkv, wt + o.qkvw, at.rows, C, 3 * C, 3 * C, 3 * C, &d4, s));
@@ -1356,7 +1386,8 @@ extern "C" int uvit_op_ln_bwd_walk(const void* dy, const float* x, const float* 
                                    float* dx, float* dw, float* db, int M, int C, int nrep, int64_t rep_stride, const int32_t* rowidx,
                                    const int32_t* count, const int32_t* pos, const uvit_ls_rider* next, uvit_stream st) {
     if (!dy || !x || !mean || !rstd || !w || !dx || !dw || !db || nrep < 1 || rep_stride < 0) return UVIT_ERR_ARG;
-    if (next && next->dy && (!next->y || !next->gamma || !next->dgamma || !next->dbias)) return UVIT_ERR_ARG;
+    // y and dgamma come together or not at all (both NULL: the rider writes dy / dbias only, uvit_op_ls_dgamma supplies dgamma)
+    if (next && next->dy && (!next->gamma || !next->dbias || (!next->y != !next->dgamma))) return UVIT_ERR_ARG;
     LnBwd p; p.dy = (const bf16*)dy; p.x = x; p.mean = mean; p.rstd = rstd; p.w = w; p.dres = dres; p.dx = dx; p.dw = dw; p.db = db;
     p.M = M; p.C = C; p.nrep = nrep; p.rep_stride = (size_t)rep_stride; p.rowidx = rowidx; p.count = count; p.pos = pos;
     p.next = ls_from_abi(next);
@@ -1364,9 +1395,19 @@ extern "C" int uvit_op_ln_bwd_walk(const void* dy, const float* x, const float* 
 }
 extern "C" int uvit_op_ls_bwd(const float* dx, const uvit_ls_rider* r, int M, int C, int nrep, int64_t rep_stride, const int32_t* rowidx,
                               const int32_t* count, uvit_stream st) {
-    if (!dx || !r || !r->y || !r->gamma || !r->dy || !r->dgamma || !r->dbias || nrep < 1 || rep_stride < 0) return UVIT_ERR_ARG;
+    if (!dx || !r || !r->gamma || !r->dy || !r->dbias || (!r->y != !r->dgamma) || nrep < 1 || rep_stride < 0) return UVIT_ERR_ARG;
     if (M <= 0 || C <= 0 || r->tokens <= 0) return UVIT_ERR_SHAPE;
     return uvit_ls_bwd_launch(dx, ls_from_abi(r), M, C, nrep, (size_t)rep_stride, S(st), rowidx, count);
+}
+extern "C" int uvit_op_ls_dgamma(const uvit_ls_dgamma_set* sets, int nsets, const float* gamma, float* dgamma, int32_t* flag, int C, int K,
+                                 int nrep, int64_t rep_stride, uvit_stream st) {
+    if (!sets || nsets < 1 || nsets > 2 || !gamma || !dgamma || !flag || rep_stride < 0) return UVIT_ERR_ARG;
+    LsDgammaSet q[2];
+    for (int i = 0; i < nsets; ++i) {
+        if (!sets[i].W_bf16 || !sets[i].dW || !sets[i].b || !sets[i].db) return UVIT_ERR_ARG;
+        q[i] = LsDgammaSet{(const bf16*)sets[i].W_bf16, sets[i].dW, sets[i].b, sets[i].db};
+    }
+    return uvit_ls_dgamma_launch(q, nsets, gamma, dgamma, flag, C, K, nrep, (size_t)rep_stride, S(st));
 }
 extern "C" int uvit_op_colsum(const void* y, int ld, int col0, int ncols, int M, float* out, int nrep, int64_t rep_stride, uvit_stream st) {
     if (!y || !out || nrep < 1 || rep_stride < 0) return UVIT_ERR_ARG;

@@ -59,18 +59,19 @@ void ln_fwd_kernel(const float* __restrict__ x, const int* __restrict__ rowidx, 
 //     (MI355X_MICROARCH.md, Global float atomics), and they were a large part of this kernel's 108 us.
 #define LNB_WAVES 8
 
-template <int NV, bool LS>
+// LSY: the rider also reads the branch output y and sums dgamma (false: LsNext::y is null, neither the load nor the sum exists)
+template <int NV, bool LS, bool LSY>
 struct LnbRow {                      // operands of one row, as loaded
     float4 x[NV], dres[NV];
-    bf16x4 dy[NV], y[LS ? NV : 1];
+    bf16x4 dy[NV], y[LSY ? NV : 1];
     float mean, rstd, dp;
     int xr;                          // residual-stream row
     int ar;                          // row of dy / mean / rstd (-1: the LayerNorm's own branch dropped the sample, dres passes through)
     int yr;                          // row of dy_next (-1: its branch dropped the sample)
 };
 
-template <int NV, LnWalk WALK, bool LS>
-__device__ __forceinline__ void lnb_load(LnbRow<NV, LS>& r, int row, const bf16* dy, const float* x, const int* map,
+template <int NV, LnWalk WALK, bool LS, bool LSY>
+__device__ __forceinline__ void lnb_load(LnbRow<NV, LS, LSY>& r, int row, const bf16* dy, const float* x, const int* map,
                                          const float* mean_i, const float* rstd_i, const float* dres, const LsNext& ls,
                                          int C, int nv, int lane) {
     const int tokens = ls.tokens;
@@ -102,7 +103,7 @@ __device__ __forceinline__ void lnb_load(LnbRow<NV, LS>& r, int row, const bf16*
                 r.dy[k] = ((const bf16x4*)(dy + (size_t)r.ar * C))[i];
             }
             r.dres[k] = WALK == WALK_SAMPLES || dres ? ((const float4*)(dres + (size_t)r.xr * C))[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (LS) if (WALK == WALK_ROWS || r.yr >= 0) r.y[k] = ((const bf16x4*)(ls.y + (size_t)r.xr * C))[i];
+            if constexpr (LSY) if (WALK == WALK_ROWS || r.yr >= 0) r.y[k] = ((const bf16x4*)(ls.y + (size_t)r.xr * C))[i];
         }
     }
 }
@@ -117,7 +118,7 @@ __device__ __forceinline__ void lnb_pad_fill(const LsNext& ls, int C, int nv, in
     }
 }
 
-template <int NV, LnWalk WALK, bool LS>
+template <int NV, LnWalk WALK, bool LS, bool LSY>
 __global__ __launch_bounds__(LNB_WAVES * 64)
 void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, const int* __restrict__ map /* rowidx | pos */,
                    const int* __restrict__ count, const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
@@ -132,7 +133,8 @@ void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, con
     if constexpr (WALK == WALK_SAMPLES && LS) { if (ls.cnt && blockIdx.x == gridDim.x - 1) lnb_pad_fill<NV>(ls, C, nv, lane, wave); }
     float4 ww[NV], gm[LS ? NV : 1];
     RowVec<NV> aw, ab;
-    RowVec<LS ? NV : 1> ag, ay;
+    RowVec<LSY ? NV : 1> ag;
+    RowVec<LS ? NV : 1> ay;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         aw.v[k] = make_float4(0.f, 0.f, 0.f, 0.f); ab.v[k] = aw.v[k];
@@ -140,16 +142,18 @@ void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, con
     }
 #pragma unroll
     for (int k = 0; k < (LS ? NV : 1); ++k) {
-        ag.v[k] = make_float4(0.f, 0.f, 0.f, 0.f); ay.v[k] = ag.v[k]; gm[k] = ag.v[k];
+        ay.v[k] = make_float4(0.f, 0.f, 0.f, 0.f); gm[k] = ay.v[k];
         if constexpr (LS) { if (lane + 64 * k < nv) gm[k] = ((const float4*)ls.gamma)[lane + 64 * k]; }
     }
+#pragma unroll
+    for (int k = 0; k < (LSY ? NV : 1); ++k) ag.v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     const int row_end = min((int)(blockIdx.x + 1) * rows_per_block, n_valid);
     int row = blockIdx.x * rows_per_block + wave;
-    LnbRow<NV, LS> cur, nxt;
-    if (row < row_end) lnb_load<NV, WALK, LS>(cur, row, dy, x, map, mean_i, rstd_i, dres, ls, C, nv, lane);
+    LnbRow<NV, LS, LSY> cur, nxt;
+    if (row < row_end) lnb_load<NV, WALK, LS, LSY>(cur, row, dy, x, map, mean_i, rstd_i, dres, ls, C, nv, lane);
     for (; row < row_end; row += LNB_WAVES) {
         const bool more = row + LNB_WAVES < row_end;
-        if (more) lnb_load<NV, WALK, LS>(nxt, row + LNB_WAVES, dy, x, map, mean_i, rstd_i, dres, ls, C, nv, lane);
+        if (more) lnb_load<NV, WALK, LS, LSY>(nxt, row + LNB_WAVES, dy, x, map, mean_i, rstd_i, dres, ls, C, nv, lane);
         const bool own = WALK == WALK_ROWS || cur.ar >= 0;      // false: the row passes dres through
         const float mean = cur.mean, rstd = cur.rstd;
         float4 g[NV], h[NV];
@@ -180,8 +184,11 @@ void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, con
                 if (own) o = make_float4(o.x + rstd * (g[k].x - s1 - h[k].x * s2), o.y + rstd * (g[k].y - s1 - h[k].y * s2),
                                          o.z + rstd * (g[k].z - s1 - h[k].z * s2), o.w + rstd * (g[k].w - s1 - h[k].w * s2));
                 ((float4*)(dx + (size_t)cur.xr * C))[i] = o;
-                if constexpr (LS) if (cur.yr >= 0)
-                    ls_apply(o, cur.dp, cur.y[k], gm[k], (bf16x4*)(ls.dy + (size_t)cur.yr * C) + i, ag.v[k], ay.v[k]);
+                if constexpr (LS) if (cur.yr >= 0) {
+                    bf16x4* dyn = (bf16x4*)(ls.dy + (size_t)cur.yr * C) + i;
+                    if constexpr (LSY) ls_apply(o, cur.dp, cur.y[k], gm[k], dyn, ag.v[k], ay.v[k]);
+                    else ls_apply(o, cur.dp, gm[k], dyn, ay.v[k]);
+                }
             }
         }
         if (more) cur = nxt;
@@ -208,7 +215,8 @@ void ln_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, con
         if (64 * k < nv) {
             fold(aw.v[k], dw, k);
             fold(ab.v[k], db, k);
-            if constexpr (LS) { fold(ag.v[k], ls.dgamma, k); fold(ay.v[k], ls.dbias, k); }
+            if constexpr (LSY) fold(ag.v[k], ls.dgamma, k);
+            if constexpr (LS) fold(ay.v[k], ls.dbias, k);
         }
     }
 }
@@ -293,17 +301,21 @@ int uvit_ln_fwd_launch(const LnFwd& p, hipStream_t s) {
 }
 int uvit_ln_bwd_launch(const LnBwd& p, hipStream_t s) {
     const LsNext& n = p.next;
-    const bool ls = n.dy != nullptr, samples = p.pos || n.cnt || (n.pos && !p.rowidx);
+    const bool ls = n.dy != nullptr, lsy = ls && n.y != nullptr, samples = p.pos || n.cnt || (n.pos && !p.rowidx);
     if (ln_shape_ok(p.M, p.C) || (p.rowidx && !p.count) || (samples && (p.rowidx || p.count))) return UVIT_ERR_SHAPE;
     if ((ls || samples) && n.tokens <= 0) return UVIT_ERR_SHAPE;
+    if (lsy && !n.dgamma) return UVIT_ERR_SHAPE;
     if (samples && ((p.M % n.tokens) || !p.dres)) return UVIT_ERR_SHAPE;
     if (((n.pos || n.cnt) && !ls) || n.pad_base < 0 || (n.pad2 && (!n.cnt || n.pad2_cols <= 0 || (n.pad2_cols % 4)))) return UVIT_ERR_SHAPE;
     const int rpb = lnb_rows(p.M, LNB_BLOCKS_PER_CU);
     dispatch_nv(p.C, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
         // samples walk: LS is instantiated both ways, like the rows walk (the parent tested ls.dy at run time there)
-        auto kernel = samples ? (ls ? ln_bwd_kernel<NV, WALK_SAMPLES, true> : ln_bwd_kernel<NV, WALK_SAMPLES, false>)
-                              : (ls ? ln_bwd_kernel<NV, WALK_ROWS, true> : ln_bwd_kernel<NV, WALK_ROWS, false>);
+        // ... and a rider without the branch output (next.y null) is its own instantiation: no y load, no dgamma sum
+        auto kernel = samples ? (lsy ? ln_bwd_kernel<NV, WALK_SAMPLES, true, true> : ls ? ln_bwd_kernel<NV, WALK_SAMPLES, true, false>
+                                                                                         : ln_bwd_kernel<NV, WALK_SAMPLES, false, false>)
+                              : (lsy ? ln_bwd_kernel<NV, WALK_ROWS, true, true> : ls ? ln_bwd_kernel<NV, WALK_ROWS, true, false>
+                                                                                      : ln_bwd_kernel<NV, WALK_ROWS, false, false>);
         hipLaunchKernelGGL(kernel, dim3((p.M + rpb - 1) / rpb), dim3(LNB_WAVES * 64), 0, s, p.dy, p.x, samples ? p.pos : p.rowidx, p.count,
                            p.mean, p.rstd, p.w, p.dres, p.dx, p.dw, p.db, p.M, p.C, p.nrep > 0 ? p.nrep : 1, p.rep_stride, n, rpb);
     });

@@ -97,3 +97,10 @@ __device__ __forceinline__ void ls_apply(const float4& d, float dp, const bf16x4
     *dy = o;
     ab.x += bf2f(o[0]); ab.y += bf2f(o[1]); ab.z += bf2f(o[2]); ab.w += bf2f(o[3]);
 }
+// the same without the branch output: dy and the dbias partial only (dgamma then comes from the weight gradient, ls_dgamma_kernel)
+__device__ __forceinline__ void ls_apply(const float4& d, float dp, const float4& gamma, bf16x4* dy, float4& ab) {
+    const float e0 = d.x * dp, e1 = d.y * dp, e2 = d.z * dp, e3 = d.w * dp;
+    const bf16x4 o = {f2bf(e0 * gamma.x), f2bf(e1 * gamma.y), f2bf(e2 * gamma.z), f2bf(e3 * gamma.w)};
+    *dy = o;
+    ab.x += bf2f(o[0]); ab.y += bf2f(o[1]); ab.z += bf2f(o[2]); ab.w += bf2f(o[3]);
+}

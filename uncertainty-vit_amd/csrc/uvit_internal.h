@@ -192,6 +192,12 @@ int uvit_relpos_scatter_launch(const float* slab, int nslab, const int* index, f
 // LayerScale + DropPath backward on its own (ls.pos / cnt / pad unused); row list: ls.dy is compact, dx / ls.y live at rowidx[row], rows >= *count get zeros
 int uvit_ls_bwd_launch(const float* dx, const LsNext& ls, int M, int C, int nrep, size_t rep_stride, hipStream_t s,
                        const int* rowidx = nullptr, const int* count = nullptr);
+// LayerScale gradient from the weight gradient (elementwise.hip): dgamma[j] += sum over the sets of (sum_k W[j][k] dW[j][k] + b[j] *
+// sum_r db[r * rep_stride + j]) / gamma[j]; W / dW are [C][K] row-major, K % 8 == 0, nrep <= 64, one or two sets.  gamma[j] == 0:
+// dgamma[j] <- 0 and *flag <- 1.
+struct LsDgammaSet { const bf16* W; const float* dW; const float* b; const float* db; };
+int uvit_ls_dgamma_launch(const LsDgammaSet* sets, int nsets, const float* gamma, float* dgamma, int* flag, int C, int K, int nrep,
+                          size_t rep_stride, hipStream_t s);
 int uvit_rows_guard_launch(const int* count, int limit, float* loss, hipStream_t s);   // *count > limit: loss <- NaN (the step is then skipped like any non-finite one)
 int uvit_colsum_launch(const void* y_bf16, int ld, int col0, int ncols, int M, float* out, int nrep, size_t rep_stride,
                        hipStream_t s);

@@ -121,6 +121,12 @@ class NativeEngine:
         # set_drop_path_rows(False) later, runs every branch on every sample as the reference does (same results; bench.py's all-rows line)
         self.drop_path_rows = bool(getattr(model, "drop_path_rows", os.environ.get("UVIT_DP_ROWS", "1") != "0"))
         self.set_drop_path_rows(self.drop_path_rows)
+        # LayerScale gradients (include/uvit.h, uvit_engine_set_ls_saved_y): from the weight gradients by default; `model.ls_saved_y = True`
+        # before the first step, set_ls_saved_y(True) later or UVIT_LS_SAVED_Y=1 saves the branch outputs instead (A/B; a gamma that is 0)
+        # (the library reads the environment variable itself at engine creation: no call unless the model asks for a path)
+        self.ls_saved_y = os.environ.get("UVIT_LS_SAVED_Y", "0")[:1] == "1"
+        if getattr(model, "ls_saved_y", None) is not None:
+            self.set_ls_saved_y(model.ls_saved_y)
         self.sync_shadows(3)
 
     @property
@@ -130,6 +136,10 @@ class NativeEngine:
     def set_drop_path_rows(self, on):
         self.drop_path_rows = bool(on)
         check(lib().uvit_engine_set_drop_path_rows(self.h, 1 if on else 0), "set_drop_path_rows")
+
+    def set_ls_saved_y(self, on):
+        self.ls_saved_y = bool(on)
+        check(lib().uvit_engine_set_ls_saved_y(self.h, 1 if on else 0), "set_ls_saved_y")
 
     def sync_shadows(self, which=3):
         check(lib().uvit_engine_sync_shadows(self.h, which, cur_stream()), "sync_shadows")

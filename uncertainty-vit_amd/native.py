@@ -96,6 +96,11 @@ class LsRider(C.Structure):
                 ("pad2_cols", C.c_int32)]
 
 
+class LsDgammaSet(C.Structure):
+    """uvit_ls_dgamma_set (include/uvit.h): one (W, dW, b, db) set of uvit_op_ls_dgamma."""
+    _fields_ = [("W", C.c_void_p), ("dW", C.c_void_p), ("b", C.c_void_p), ("db", C.c_void_p)]
+
+
 class WgradSplit(C.Structure):
     """uvit_wgrad_split (include/uvit.h): the second stream's bias sums of one uvit_wgrad_problem."""
     _fields_ = [("bias_s1", C.c_void_p), ("bias2_s1", C.c_void_p), ("s1_row", C.c_int32)]
@@ -145,6 +150,7 @@ _PROTOTYPES = {
     "uvit_op_wgrad_group": (_i, [_vp, _i, _vp, _vp]),
     "uvit_engine_set_streams": (_i, [_vp, _i]),
     "uvit_engine_set_drop_path_rows": (_i, [_vp, _i]),
+    "uvit_engine_set_ls_saved_y": (_i, [_vp, _i]),
     "uvit_drop_path_kept_counts": (_i, [_i, _f, _i, _i, _u32, _u32, _vp]),
     "uvit_engine_profile": (_i, [_vp, _i, _i]),
     "uvit_engine_profile_read": (_i, [_vp, _vp, _vp, _vp]),
@@ -170,6 +176,7 @@ _PROTOTYPES = {
     "uvit_op_ln_fwd_walk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _vp]),
     "uvit_op_ln_bwd_walk": (_i, [_vp] * 9 + [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "uvit_op_ls_bwd": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp]),
+    "uvit_op_ls_dgamma": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
     "uvit_op_colsum": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i64, _vp]),
     "uvit_op_reduce_replicas": (_i, [_vp, _vp, _i64, _i, _i64, _vp]),
     "uvit_op_droppath_lists": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
