@@ -942,6 +942,56 @@ int uvit_op_probe_input_grad(const float* dlogits, const float* W, float* dfeat,
 int uvit_op_lw_grad(const float* dfeat, const float* pooled, const float* log_w, float* dlog_w, double* scratch, int B, int L, int C,
                     uvit_stream stream);
 
+/* ---- ImageNet-C-style corruptions generated on the device (csrc/corrupt.hip) ----
+ * The reference's c_evaluate() reads pre-made corrupted folders; here the clean evaluation images are kept on the device as planar
+ * uint8 and every (corruption, severity) set is generated per batch in front of the encoder forward.  IEEE fp32, no contraction, no
+ * atomics: the same input gives the same bits on every run, and tests/corrupt_ref.py restates every kind but the two Box-Muller ones
+ * bit for bit.  Every call checks its arguments before it touches the device (nothing launched on an error):
+ *   UVIT_ERR_ARG        a NULL pointer, an unknown kind, a parameter count that does not fit the kind, a mean or std that is not finite,
+ *                       a std of 0, an index0 outside [0, 2^32 - 1 - 21845]
+ *   UVIT_ERR_SHAPE      B outside [1, 21845], S outside [8, 1024], a blur radius R >= S or R > 24
+ *   UVIT_ERR_WORKSPACE  ws_bytes below uvit_op_corrupt_ws_bytes(kind, B, S)
+ * mean / std: HOST, 3 floats each, as in uvit_op_augment_batch. */
+#define UVIT_CORRUPT_GAUSSIAN_NOISE 0
+#define UVIT_CORRUPT_SPECKLE_NOISE 1
+#define UVIT_CORRUPT_IMPULSE_NOISE 2
+#define UVIT_CORRUPT_SHOT_NOISE 3
+#define UVIT_CORRUPT_BRIGHTNESS 4
+#define UVIT_CORRUPT_SATURATE 5
+#define UVIT_CORRUPT_CONTRAST 6
+#define UVIT_CORRUPT_GAUSSIAN_BLUR 7
+#define UVIT_CORRUPT_DEFOCUS_BLUR 8
+#define UVIT_CORRUPT_KINDS 9
+/* out_u8 (B, 3, S, S) planar uint8 from the normalised fp32 images x (B, 3, S, S) that uvit_op_augment_batch wrote:
+ * q = floor(clip(x * std[c] + mean[c], 0, 1) * 255 + 0.5), the exact inverse of the augmentation's step 4 for values that came from
+ * uint8. */
+int uvit_op_corrupt_pack(const float* x, int B, int S, const float* mean, const float* std, uint8_t* out_u8, uvit_stream stream);
+int64_t uvit_op_corrupt_ws_bytes(int kind, int B, int S);        /* < 0: UVIT_ERR_ARG (kind) or UVIT_ERR_SHAPE; may be 0 (ws may then be NULL) */
+/* out (B, 3, S, S) fp32 = the corrupted in_u8 (B, 3, S, S), quantised to uint8 levels and normalised.  With v = float(u8) / 255.0f
+ * every kind forms v' as below and writes ((q / 255) - mean[c]) / std[c], q = floor(clip(v', 0, 1) * 255 + 0.5) (ImageNet-C truncates;
+ * rounding makes pack followed by an identity exact).  params: DEVICE fp32 table of n_params values, prepared once per set
+ * (corruptions.corruption_params); z: a standard normal, u: a uniform, both below.
+ *   GAUSSIAN_NOISE  [c]                 v + c z
+ *   SPECKLE_NOISE   [c]                 v + (v c) z
+ *   IMPULSE_NOISE   [c]                 h < T/2: 1; h < T: 0; else v, with T = floor(c 2^32) (common.h's uvit_drop_threshold)
+ *   SHOT_NOISE      [c, p0[256], kmax[256]]   min(k / c, 1), k ~ Poisson(lambda = v c) by inversion: k = 0, p = F = p0[u8]; while u > F and
+ *                                       k < kmax[u8]: k = k + 1, p = (p lambda) / k, F = F + p.  p0 = exp(-lambda) and kmax, the smallest k whose
+ *                                       CDF reaches 1 - 2^-25, come from the host in double from the fp32 lambda (kmax is capped at 512 here)
+ *   BRIGHTNESS      [c]                 m = max(r, g, b), m' = min(m + c, 1): rgb (m' / m), or (m', m', m') when m == 0
+ *   SATURATE        [c0, c1]            s = (m - min) / m (0 when m == 0), s' = clip(s c0 + c1, 0, 1): m - (m - x) (s' / s) for s > 0, else
+ *                                       (m, m (1 - s'), m (1 - s'))
+ *   CONTRAST        [c]                 (v - mu) c + mu, mu = float(sum / (255.0 S S)) of the image's channel plane: exact integer sum, division in double
+ *   GAUSSIAN_BLUR   2 R + 1 taps        vertical then horizontal pass, border replicate, the fp32 intermediate in ws
+ *   DEFOCUS_BLUR    (2 R + 1)^2 taps    dense, row-major, border reflect-101
+ * A convolution adds its taps dy ascending, then dx ascending, into one fp32 accumulator from 0, acc = acc + (t x); zero taps are skipped.
+ * Draws: with key = h(h(seed ^ (kind + 1) 0x9E3779B9) ^ (index0 + b + 1) 0x85EBCA6B) of image b (h = uvit_hash32; index0 = the index of
+ * the batch's first image in the SET), k1 = h(key ^ 0x1B873593), k2 = h(key ^ 0xCC9E2D51) and the counter i = (c S + y) S + x:
+ * h1 = h(i ^ k1), h2 = h(i ^ k2), u = u1 = ((h1 >> 8) + 1) 2^-24, u2 = (h2 >> 8) 2^-24, z = sqrtf(-2 logf(u1)) cosf(2 pi u2); impulse
+ * noise compares h1.  `seed` is the set's: the caller mixes the severity into it (corruptions.set_seed).  A set therefore has the same
+ * bytes for every batch size and every split. */
+int uvit_op_corrupt_batch(const uint8_t* in_u8, float* out, int B, int S, int kind, const float* params, int n_params, uint32_t seed,
+                          int64_t index0, const float* mean, const float* std, void* ws, int64_t ws_bytes, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

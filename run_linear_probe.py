@@ -145,6 +145,19 @@ the trained weights say which blocks carry the signal: every epoch and every --e
 l)` after `* Acc@1`, and log.txt gains `test_layer_weights`.  Checkpoints hold `head.weight`, `head.bias` and `layer_log_weights`;
 --resume refuses one without the third key or of another depth.  --calibration, --detection / --ood_data_path, --ts_*, --cp_*,
 --maha_*, --knn_*, --vim_* and --perturbation_path work unchanged on the mixed feature and its logits.
+
+`--eval --corruptions NAME ... | all` (with --eval_data_path) adds the reference's c_evaluate() behind the evaluation, on corruptions
+generated on the device (uncertainty-vit_amd/corruptions.py): the clean evaluation images are decoded once and
+kept on the device as uint8 (`--corruption_cache_images N`, default 65536; a larger folder is read again per set), and every
+(corruption, severity) set -- gaussian_noise, speckle_noise, impulse_noise, shot_noise, brightness, saturate, contrast, gaussian_blur,
+defocus_blur at `--corruption_severities` (default 1 2 3 4 5), noise seeded by `--corruption_seed` (default 0) -- is one evaluation with
+the run's own switches.  The constants are ImageNet-C's as remembered, unverified: the figures are ImageNet-C-style, not the published
+benchmark.  `--corruption_path DIR` (exclusive with --corruptions) reads a pre-made tree DIR/<distortion>/<severity>/<class>/... with
+the evaluation pipeline instead: the reference's DISTORTIONS order first, then the other sub-folders sorted; a missing severity folder
+is an error.  The run prints `Corrupted dataset evaluation :`, `Distortion : <name>`, per severity `* Acc@1 ... CE ... ` (followed by
+the set's calibration line, variance mean and detection lines when the run has them), `mCE (unnormalized) (%): ..., acc :...` and
+`* Severity s Acc@1 ... CE ... rel-CE ... [ECE ... NLL ...]` per severity; log.txt gains `test_c_<name>_<severity>_<key>` per set and
+`test_c_mce`, `test_c_acc`, `test_c_severity_*` (lists).
 """
 import argparse
 import json
@@ -284,6 +297,16 @@ def get_args(argv=None):
       help="with --learn_layer_weights: LayerNorm (no affine, eps 1e-5) of every block's pooled vector before the mix")
     a("--use_cls", action="store_true", default=argparse.SUPPRESS,
       help="with --learn_layer_weights: pool the cls token of every block instead of the mean over all its tokens")
+    a("--corruptions", type=str, nargs="+", default=argparse.SUPPRESS, metavar="NAME",
+      help="with --eval and --eval_data_path: evaluate under these corruptions of the clean evaluation images, generated on the device "
+           "(names of uncertainty_vit_amd.corruptions.CORRUPTIONS, or `all`); the reference's c_evaluate()")
+    a("--corruption_severities", type=int, nargs="+", default=argparse.SUPPRESS, metavar="S", help="the severities to sweep, a subset of 1 .. 5 (default: all five)")
+    a("--corruption_seed", type=int, default=argparse.SUPPRESS, help="seed of the noise corruptions (default 0)")
+    a("--corruption_cache_images", type=int, default=argparse.SUPPRESS, metavar="N",
+      help="keep up to N clean evaluation images on the device as uint8 across the sets (default 65536); a larger folder is read again per set")
+    a("--corruption_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
+      help="with --eval: a pre-made corrupted data set DIR/<distortion>/<severity>/<class>/... (the reference's layout), every folder read "
+           "with the evaluation pipeline; exclusive with --corruptions")
     return p.parse_args(argv)
 
 
@@ -680,6 +703,194 @@ def evaluate_perturbations(args, probe, device):
     return results
 
 
+CORRUPTION_FLAGS = ("corruptions", "corruption_severities", "corruption_seed", "corruption_cache_images", "corruption_path")
+# uncertainty_evaluations.py:846: the order of the reference's sweep over a pre-made tree
+REFERENCE_DISTORTIONS = ("gaussian_noise", "shot_noise", "impulse_noise", "defocus_blur", "glass_blur", "motion_blur", "zoom_blur", "snow",
+                         "frost", "brightness", "contrast", "elastic_transform", "pixelate", "jpeg_compression", "speckle_noise")
+VAR_MEAN_LINES = (("gp_var_mean", gp_variance_line), ("het_var_mean", het_variance_line),
+                  ("lap_var_mean", lambda stats: "* Laplace variance mean {lap_var_mean:.6f}".format(**stats)))
+
+
+def check_corruption_flags(args):
+    """Where the corruption sweep takes its images from: "device" (--corruptions: generated from --eval_data_path), "path"
+    (--corruption_path: a pre-made tree) or None.  All --corruption* flags belong to --eval, the two sources are exclusive,
+    --corruptions needs --eval_data_path, and the seed and the cache belong to the generated sets."""
+    given = [k for k in CORRUPTION_FLAGS if hasattr(args, k)]
+    if not given:
+        return None
+    if not args.eval:
+        raise ValueError("--corruptions / --corruption_* belong to an evaluation: give --eval")
+    if hasattr(args, "corruptions") and hasattr(args, "corruption_path"):
+        raise ValueError("--corruptions generates the corrupted sets and --corruption_path reads them: give one")
+    for s in getattr(args, "corruption_severities", ()):
+        if not 1 <= s <= 5:
+            raise ValueError(f"--corruption_severities takes severities 1 .. 5, got {s}")
+    if len(set(getattr(args, "corruption_severities", ()))) != len(getattr(args, "corruption_severities", ())):
+        raise ValueError("--corruption_severities names a severity twice")
+    if hasattr(args, "corruption_path"):
+        if hasattr(args, "corruption_seed") or hasattr(args, "corruption_cache_images"):
+            raise ValueError("--corruption_seed / --corruption_cache_images steer the sets that --corruptions generates: not with --corruption_path")
+        return "path"
+    if not hasattr(args, "corruptions"):
+        raise ValueError("--corruption_severities / --corruption_seed / --corruption_cache_images steer a sweep: give --corruptions NAME ... "
+                         "or --corruption_path DIR")
+    if not args.eval_data_path:
+        raise ValueError("--corruptions corrupts the clean evaluation images: give --eval_data_path DIR")
+    if getattr(args, "corruption_cache_images", 0) < 0:
+        raise ValueError(f"--corruption_cache_images must be >= 0, got {args.corruption_cache_images}")
+    corruption_names(args)
+    return "device"
+
+
+def corruption_names(args):
+    """--corruptions as a list of kinds in the order given (`all`: every kind, in CORRUPTIONS' order); an unknown or repeated name is refused."""
+    from uncertainty_vit_amd.corruptions import CORRUPTIONS
+    names = list(args.corruptions)
+    if names == ["all"]:
+        return list(CORRUPTIONS)
+    for n in names:
+        if n not in CORRUPTIONS:
+            raise ValueError(f"--corruptions: unknown corruption {n!r}; one of {', '.join(CORRUPTIONS)}, or `all` alone")
+    if len(set(names)) != len(names):
+        raise ValueError("--corruptions names a corruption twice")
+    return names
+
+
+def corruption_severities(args):
+    return list(getattr(args, "corruption_severities", (1, 2, 3, 4, 5)))
+
+
+def corruption_folders(args):
+    """[(distortion, [(severity, folder)])] of --corruption_path: the reference's DISTORTIONS that are there, in its order, then the other
+    sub-folders sorted.  A severity folder that is missing is an error that names it."""
+    root = args.corruption_path
+    have = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d)))
+    if not have:
+        raise FileNotFoundError(f"no distortion folders under --corruption_path {root}")
+    names = [d for d in REFERENCE_DISTORTIONS if d in have] + [d for d in have if d not in REFERENCE_DISTORTIONS]
+    out = []
+    for name in names:
+        sets = []
+        for s in corruption_severities(args):
+            folder = os.path.join(root, name, str(s))
+            if not os.path.isdir(folder):
+                raise FileNotFoundError(f"--corruption_path: severity folder {folder} is missing")
+            sets.append((s, folder))
+        out.append((name, sets))
+    return out
+
+
+def corruption_set_line(stats):
+    """uncertainty_evaluations.py:384-386, the trailing blank included."""
+    return "* Acc@1 {:.4f} CE {:.4f} ".format(stats["acc1"], (100 - stats["acc1"]) / 100)
+
+
+def corruption_set_lines(stats):
+    """The reference's line of one set, then what its stats hold beyond accuracy: the calibration line, the head's variance mean, the
+    misclassification-detection lines."""
+    lines = [corruption_set_line(stats)]
+    if "ECE" in stats:
+        lines.append(calibration_line(stats))
+    lines += [fmt(stats) for key, fmt in VAR_MEAN_LINES if key in stats]
+    if "detection" in stats:
+        lines += detection_lines(stats["detection"])
+    return lines
+
+
+def corruption_log_entries(name, severity, stats):
+    """The set's line of log.txt: test_c_<name>_<severity>_<key>."""
+    out = {"acc1": stats["acc1"], "acc5": stats["acc5"], "loss": stats["loss"], "ce": (100 - stats["acc1"]) / 100}
+    out.update({k: stats[k] for k in CALIB_KEYS if k in stats})
+    out.update({k: stats[k] for k, _ in VAR_MEAN_LINES if k in stats})
+    if "detection" in stats:
+        out.update({k[len("test_"):]: v for k, v in detection_log_entries(stats["detection"]).items()})
+    return {f"test_c_{name}_{severity}_{k}": v for k, v in out.items()}
+
+
+def corruption_summary(results, clean_stats):
+    """{"mce", "acc", "severities", "acc1", "ce", "rel_ce"[, "ECE", "NLL"]} of results = {(name, severity): stats}: the reference's
+    closing figures (the mean CE and the mean accuracy over all sets) and, per severity in ascending order, the means over the
+    corruptions evaluated at it; rel_ce is the CE minus the clean run's."""
+    ce = lambda s: (100 - s["acc1"]) / 100      # noqa: E731
+    sets = list(results.values())
+    out = {"mce": float(np.mean([ce(s) for s in sets])), "acc": float(np.mean([s["acc1"] for s in sets]))}
+    sevs = sorted({sev for _, sev in results})
+    rows = {sev: [s for (_, v), s in results.items() if v == sev] for sev in sevs}
+    out["severities"] = sevs
+    out["acc1"] = [float(np.mean([s["acc1"] for s in rows[v]])) for v in sevs]
+    out["ce"] = [float(np.mean([ce(s) for s in rows[v]])) for v in sevs]
+    out["rel_ce"] = [c - ce(clean_stats) for c in out["ce"]]
+    for key in ("ECE", "NLL"):
+        if all(key in s for s in sets):
+            out[key] = [float(np.mean([s[key] for s in rows[v]])) for v in sevs]
+    return out
+
+
+def corruption_summary_lines(summary):
+    """The reference's closing line (uncertainty_evaluations.py:391), then one line per severity (Ovadia et al. 2019's table)."""
+    lines = ["mCE (unnormalized) (%): {:.4f}, acc :{:.4f}".format(summary["mce"], summary["acc"])]
+    for i, sev in enumerate(summary["severities"]):
+        line = "* Severity {} Acc@1 {:.4f} CE {:.4f} rel-CE {:.4f}".format(sev, summary["acc1"][i], summary["ce"][i], summary["rel_ce"][i])
+        if "ECE" in summary:
+            line += " ECE {:.5f} NLL {:.5f}".format(summary["ECE"][i], summary["NLL"][i])
+        lines.append(line)
+    return lines
+
+
+def corruption_summary_log(summary):
+    out = {"test_c_mce": summary["mce"], "test_c_acc": summary["acc"], "test_c_severity_levels": summary["severities"]}
+    out.update({f"test_c_severity_{k}": summary[k] for k in ("acc1", "ce", "rel_ce", "ECE", "NLL") if k in summary})
+    return out
+
+
+def evaluate_corruptions(args, probe, device, clean_stats, eval_kw=None):
+    """The reference's c_evaluate() (uncertainty_evaluations.py:355-391) behind the main evaluation: per distortion and severity one
+    probe.evaluate with the run's own switches (`eval_kw`: calibration, detection, temperature and the head's), the reference's lines
+    with the additions of corruption_set_lines, its closing mCE line and the per-severity summary.  With --corruptions the sets are
+    generated on the device from the clean evaluation folder (uncertainty_vit_amd/corruptions.py): the first set reads and packs the
+    folder into a CleanCache, the others replay it; a folder over --corruption_cache_images is read again per set.  With
+    --corruption_path every DIR/<distortion>/<severity> is read with the evaluation pipeline.  Returns {"sets": {(name, severity):
+    stats}, "summary": corruption_summary's}."""
+    from uncertainty_vit_amd.corruptions import DEFAULT_CACHE_IMAGES, CleanCache, CorruptedSet
+    from uncertainty_vit_amd.datasets import BEiTAugment
+    from uncertainty_vit_amd.engine_for_cyclical import DevicePrefetcher
+    eval_kw = dict(eval_kw or {})
+    eval_kw.pop("ood_loader", None)          # the sets are compared with themselves: misclassification detection only
+    if hasattr(args, "corruption_path"):
+        # the loaders first: their `Eval data = ...` lines stay out of the reference's block
+        plan = [(name, [(s, build_loader(args, probe.encoder, folder, 1, train=False)[0]) for s, folder in sets])
+                for name, sets in corruption_folders(args)]
+        make = lambda name, s, loader: DevicePrefetcher(loader, device)      # noqa: E731
+    else:
+        aug = BEiTAugment(args.input_size, 1, "bicubic", args.imagenet_default_mean_and_std)
+        loader, _ = build_loader(args, probe.encoder, args.eval_data_path, 1, train=False)
+        cache = CleanCache(getattr(args, "corruption_cache_images", DEFAULT_CACHE_IMAGES), args.batch_size)
+        seed = getattr(args, "corruption_seed", 0)
+        plan = [(name, [(s, None) for s in corruption_severities(args)]) for name in corruption_names(args)]
+
+        def make(name, s, _):
+            if cache.ready:
+                return CorruptedSet(cache, name, s, seed, aug.mean, aug.std)
+            return CorruptedSet(DevicePrefetcher(loader, device), name, s, seed, aug.mean, aug.std, cache=None if cache.overflowed else cache)
+    print("Corrupted dataset evaluation :")
+    results = {}
+    for name, sets in plan:
+        print("Distortion : " + name)
+        for s, loader_c in sets:
+            stats = probe.evaluate(make(name, s, loader_c), **eval_kw)
+            results[(name, s)] = stats
+            print("\n".join(corruption_set_lines(stats)))
+            if args.output_dir:
+                with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
+                    f.write(json.dumps(corruption_log_entries(name, s, stats)) + "\n")
+    summary = corruption_summary(results, clean_stats)
+    print("\n".join(corruption_summary_lines(summary)))
+    if args.output_dir:
+        with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
+            f.write(json.dumps(corruption_summary_log(summary)) + "\n")
+    return {"sets": results, "summary": summary}
+
+
 def encoder_kwargs(checkpoint):
     """Constructor options of the encoder a run_cyclical.py checkpoint was trained with (utils.save_model keeps its args)."""
     a = checkpoint.get("args") if isinstance(checkpoint, dict) else None
@@ -724,6 +935,9 @@ def main(args):
     maha = check_maha_flags(args)
     knn = check_knn_flags(args)
     vim = check_vim_flags(args)
+    corruption_mode = check_corruption_flags(args)
+    if corruption_mode == "path":
+        corruption_folders(args)                  # a missing folder stops the run here, not behind the main evaluation
     detection = detection or maha is not None or knn is not None or vim is not None
     gp_layer = getattr(args, "gp_layer", False)
     if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
@@ -952,6 +1166,8 @@ def main(args):
                                     **(conformal_log_entries(cp_fit, stats["conformal"]) if conformal else {})}) + "\n")
         if hasattr(args, "perturbation_path"):
             stats["stability"] = evaluate_perturbations(args, probe, device)
+        if corruption_mode:
+            stats["corruptions"] = evaluate_corruptions(args, probe, device, stats, eval_kw={"calibration": calibration, **gp_eval})
         return stats
     loader_train, _ = build_loader(args, encoder, args.data_path, 3, train=True)
     steps_per_epoch = len(loader_train)
