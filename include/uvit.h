@@ -802,6 +802,29 @@ int uvit_op_lap_variance(const float* feat, const double* UA, const double* T, d
 int uvit_op_lap_probit(const float* logits, int64_t ld, const double* var, double factor, float* out, int64_t ld_out, float* lap_var,
                        int B, int K, uvit_stream stream);
 
+/* ---- probe of the two-stream (mean, covariance) model, DESIGN.md section 9.17 ----
+ * m (B, C) and c (B, C) are the pooled, normalised features of the mean and the covariance stream.  v = scale (ELU(c) + 1) =
+ * scale (c > 0 ? c + 1 : exp(c)) is read as the variance of a feature f ~ N(m, diag(v)); the linear head z = W f + b carries it to
+ * z ~ N(W m + b, W diag(v) W^T), of which the diagonal var[b, k] = sum_c W[k, c]^2 v[b, c] is built.  The link on var is
+ * uvit_op_lap_probit above.  Limits: C % 4 == 0, 4 <= C <= 2048, 1 <= B <= 65535, N >= 2, 1 <= K <= 65535.  Every call checks its
+ * arguments before it touches the device (UVIT_ERR_ARG for a NULL required pointer or a bad scalar, UVIT_ERR_SHAPE for a size outside
+ * these limits; outputs untouched) and is asynchronous on `stream`.  No atomics; every sum has one owner and a fixed order, so the
+ * same input gives the same bits on every run. */
+/* Workspace of uvit_op_dprobe_pool_norm in bytes: twice uvit_op_probe_pool_ws_bytes(B, N, C) (< 0: the UVIT_ERR_* of the call). */
+int64_t uvit_op_dprobe_pool_ws_bytes(int B, int N, int C);
+/* uvit_op_probe_pool_norm of two residual streams (B, N, C) in one launch pair, the stream index on a grid dimension: feat_mean from
+ * x_mean and feat_cov from x_cov, each bit for bit what uvit_op_probe_pool_norm gives on that stream alone (the same 8 token slices,
+ * the same 4 waves, the same order of every sum).  The two inputs, and the two outputs, are independent pointers. */
+int uvit_op_dprobe_pool_norm(const float* x_mean, const float* x_cov, float* feat_mean, float* feat_cov, float* scratch, int B, int N, int C,
+                             float eps, uvit_stream stream);
+/* var (B, K) double and trace (B) fp32, nullable, from cfeat = c (B, C) fp32 and the head's weights W (K, C) fp32.  v is formed in
+ * double from the fp32 c, (double) w * (double) w is exact, and every var[b, k] is one fma chain over c in ascending order (16 x 32
+ * output tiles, as uvit_op_lap_variance).  trace[b] = (float)(sum_c v[b, c] / C): lane l of one wave adds columns l, l + 64, ... in
+ * ascending order, the lanes meet in the xor tree, the quotient is rounded once.  A NaN in cfeat[b] makes row b of var and trace[b]
+ * NaN and touches no other row.  scale must be finite and greater than 0 (UVIT_ERR_ARG). */
+int uvit_op_dprobe_variance(const float* cfeat, const float* W, double scale, double* var, float* trace, int B, int K, int C,
+                            uvit_stream stream);
+
 /* ---- Mahalanobis and relative Mahalanobis out-of-distribution scores of the probe's feature, DESIGN.md section 9.10 ----
  * f (B, C) is the probe's pooled, normalised feature.  Over the usable rows of a labelled set (every feature finite, the label inside
  * [0, K)): S = sum f f^T (C, C), class_sum[k] = the sum of the rows of class k (K, C), total_sum (C), class_count (K).  From these the

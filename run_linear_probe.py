@@ -158,6 +158,16 @@ is an error.  The run prints `Corrupted dataset evaluation :`, `Distortion : <na
 the set's calibration line, variance mean and detection lines when the run has them), `mCE (unnormalized) (%): ..., acc :...` and
 `* Severity s Acc@1 ... CE ... rel-CE ... [ECE ... NLL ...]` per severity; log.txt gains `test_c_<name>_<severity>_<key>` per set and
 `test_c_mce`, `test_c_acc`, `test_c_severity_*` (lists).
+
+A `--model` that builds the two-stream (mean, covariance) encoder (`dist_beit_base_patch16_224`, `dist_beit_large_patch16_224`) is
+probed by uncertainty-vit_amd/dist_probe.py: the nn.Linear reads the mean stream's pooled feature and trains
+as the linear probe does; the covariance stream's pooled feature c gives a feature variance v = S (ELU(c) + 1) (`--dist_var_scale S`,
+default 1.0) and, through the head, a variance per logit.  `--dist_mean_field FACTOR` (default 0: the reference's logits; pi / 8 =
+0.3927 is the literature's value) evaluates on z / sqrt(1 + FACTOR * var); both flags are refused with a base model.  Every
+evaluation prints `* Dist variance mean <v> trace mean <t>` after `* Acc@1`, log.txt gains `test_dist_var_mean` and
+`test_dist_trace_mean`, and `--detection` gains the columns `dist_var` and `dist_trace`.  --calibration, --ts_*, --cp_*, --maha_*,
+--knn_*, --perturbation_path, --corruptions and --target_layer work as with a base model, --vim_* at FACTOR = 0; the other heads
+(--gp_layer, --het_layer, --ensembles, --laplace, --mc_dropout_forwards, --learn_layer_weights) refuse a two-stream encoder.
 """
 import argparse
 import json
@@ -297,6 +307,11 @@ def get_args(argv=None):
       help="with --learn_layer_weights: LayerNorm (no affine, eps 1e-5) of every block's pooled vector before the mix")
     a("--use_cls", action="store_true", default=argparse.SUPPRESS,
       help="with --learn_layer_weights: pool the cls token of every block instead of the mean over all its tokens")
+    a("--dist_mean_field", type=float, default=argparse.SUPPRESS, metavar="FACTOR",
+      help="two-stream --model: evaluate on z / sqrt(1 + FACTOR * var), var from the covariance stream (default 0: the reference's "
+           "logits; pi / 8 = 0.3927 is the literature's value)")
+    a("--dist_var_scale", type=float, default=argparse.SUPPRESS, metavar="S",
+      help="two-stream --model: the scale s of the feature variance v = s (ELU(c) + 1) (default 1.0)")
     a("--corruptions", type=str, nargs="+", default=argparse.SUPPRESS, metavar="NAME",
       help="with --eval and --eval_data_path: evaluate under these corruptions of the clean evaluation images, generated on the device "
            "(names of uncertainty_vit_amd.corruptions.CORRUPTIONS, or `all`); the reference's c_evaluate()")
@@ -344,6 +359,31 @@ def ens_lines(stats):
     lines.append("* Ens entropy {ens_total:.5f} expected {ens_aleatoric:.5f} MI {ens_mi:.5f} variance {ens_var:.6f} "
                  "disagreement {ens_disagreement:.5f}".format(**stats))
     return lines
+
+
+DIST_FLAGS = ("dist_mean_field", "dist_var_scale")
+
+
+def check_dist_flags(args, two_stream):
+    """The two-stream probe's constructor options {mean_field, var_scale} (`two_stream`: --model built a two-stream encoder), None for
+    a base model.  The --dist_* flags belong to a two-stream model; the factor is finite and >= 0, the scale finite and > 0; ViM needs
+    logits that are affine in the feature, which a factor > 0 ends."""
+    if not two_stream:
+        if any(hasattr(args, k) for k in DIST_FLAGS):
+            raise ValueError("--dist_mean_field / --dist_var_scale read the covariance stream: give a two-stream --model (dist_beit_*)")
+        return None
+    factor, scale = getattr(args, "dist_mean_field", 0.0), getattr(args, "dist_var_scale", 1.0)
+    if not 0.0 <= factor < math.inf:
+        raise ValueError(f"--dist_mean_field must be finite and >= 0, got {factor}")
+    if not 0.0 < scale < math.inf:
+        raise ValueError(f"--dist_var_scale must be finite and > 0, got {scale}")
+    if factor and any(hasattr(args, k) for k in VIM_FLAGS):
+        raise ValueError("--vim_* need logits that are affine in the feature: not with --dist_mean_field > 0")
+    return {"mean_field": factor, "var_scale": scale}
+
+
+def dist_variance_line(stats):
+    return "* Dist variance mean {dist_var_mean:.6f} trace mean {dist_trace_mean:.6f}".format(**stats)
 
 
 def check_mcd_flags(args):
@@ -708,7 +748,8 @@ CORRUPTION_FLAGS = ("corruptions", "corruption_severities", "corruption_seed", "
 REFERENCE_DISTORTIONS = ("gaussian_noise", "shot_noise", "impulse_noise", "defocus_blur", "glass_blur", "motion_blur", "zoom_blur", "snow",
                          "frost", "brightness", "contrast", "elastic_transform", "pixelate", "jpeg_compression", "speckle_noise")
 VAR_MEAN_LINES = (("gp_var_mean", gp_variance_line), ("het_var_mean", het_variance_line),
-                  ("lap_var_mean", lambda stats: "* Laplace variance mean {lap_var_mean:.6f}".format(**stats)))
+                  ("lap_var_mean", lambda stats: "* Laplace variance mean {lap_var_mean:.6f}".format(**stats)),
+                  ("dist_var_mean", dist_variance_line))
 
 
 def check_corruption_flags(args):
@@ -975,6 +1016,8 @@ def main(args):
     unused = load_encoder_checkpoint(encoder, ckpt, args.model_key, args.model_prefix)
     print(f"encoder: {encoder.depth} blocks, {len(unused)} checkpoint entries not part of it")
     encoder.to(device)
+    dist = check_dist_flags(args, encoder._two_stream)
+    other_head = gp_layer or het_layer or ensembles or laplace or mcd or lw      # none reads a two-stream encoder: its constructor says so
     if gp_layer:
         from uncertainty_vit_amd.gp_probe import GPProbe
         probe = GPProbe(encoder, args.nb_classes, smoothing=args.smoothing, num_inducing=getattr(args, "gp_num_inducing", None),
@@ -1008,6 +1051,9 @@ def main(args):
         from uncertainty_vit_amd.lw_probe import LayerWeightedProbe
         probe = LayerWeightedProbe(encoder, args.nb_classes, smoothing=args.smoothing, use_cls=getattr(args, "use_cls", False),
                                    layernorm_before_combine=getattr(args, "layernorm_before_combine", False))
+    elif dist is not None:
+        from uncertainty_vit_amd.dist_probe import DistProbe
+        probe = DistProbe(encoder, args.nb_classes, smoothing=args.smoothing, **dist)
     else:
         probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
     print("Trainable weights: %s" % [n for n, p in probe.named_parameters() if p.requires_grad])
@@ -1027,6 +1073,9 @@ def main(args):
         gp_eval = {"members": True, "uncertainty": True}
     if mcd:
         gp_eval = {"uncertainty": True}
+    dist = dist is not None and not other_head
+    if dist:
+        gp_eval = {"variance": True}
     if detection:
         gp_eval["detection"] = True
         if hasattr(args, "ood_data_path"):
@@ -1113,7 +1162,8 @@ def main(args):
                                      kreg=getattr(args, "cp_kreg", 5) if raps else 0, randomized=getattr(args, "cp_randomized", False),
                                      seed=getattr(args, "cp_seed", 0), **cp_temp, **cp_kw)
     evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration, **gp_eval)      # noqa: E731
-    extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ()) + (("het_var_mean",) if het_layer else ())
+    extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ()) + (("het_var_mean",) if het_layer else ()) + \
+        (("dist_var_mean", "dist_trace_mean") if dist else ())
     if args.eval:
         stats = evaluate()
         if ts_fit is not None:
@@ -1136,6 +1186,8 @@ def main(args):
             print(gp_variance_line(stats))
         if het_layer:
             print(het_variance_line(stats))
+        if dist:
+            print(dist_variance_line(stats))
         if ensembles:
             print("\n".join(ens_lines(stats)))
         if mcd:
@@ -1210,6 +1262,8 @@ def main(args):
             print(gp_variance_line(stats))
         if het_layer:
             print(het_variance_line(stats))
+        if dist:
+            print(dist_variance_line(stats))
         if ensembles:
             print("\n".join(ens_lines(stats)))
         if mcd:

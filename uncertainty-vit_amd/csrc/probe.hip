@@ -14,67 +14,8 @@
 
 #include "../../include/uvit.h"
 #include "probe_common.h"
+#include "probe_pool.h"      // pool + norm: the kernels and their launch, shared with dprobe.hip
 #include "rowwise.h"
-
-#define POOL_SLICES 8        // token slices per sample: B x 8 workgroups stream the residual stream (1024 at B = 128 for 256 CUs)
-#define POOL_WAVES 4
-#define POOL_MAX_B 65535     // samples ride on grid.y
-
-// ---- pool: partial column sums of tokens 1..N-1, one workgroup per (slice, sample); wave w takes the slice's tokens w, w + 4, ... ----
-template <int NV>
-__global__ __launch_bounds__(64 * POOL_WAVES)
-void probe_pool_partial_kernel(const float* __restrict__ x, float* __restrict__ scratch, int N, int C) {
-    __shared__ float4 red[POOL_WAVES - 1][NV * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, slice = blockIdx.x, b = blockIdx.y, nv = C >> 2;
-    const int per = (N - 1 + POOL_SLICES - 1) / POOL_SLICES;
-    const int t0 = 1 + slice * per, t1 = min(N, t0 + per);
-    RowVec<NV> acc, r;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) acc.v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t = t0 + wave; t < t1; t += POOL_WAVES) {
-        load_row(r, x + ((size_t)b * N + t) * C, C, lane);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) { acc.v[k].x += r.v[k].x; acc.v[k].y += r.v[k].y; acc.v[k].z += r.v[k].z; acc.v[k].w += r.v[k].w; }
-    }
-    if (wave > 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[wave - 1][lane + 64 * k] = acc.v[k];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        float* dst = scratch + ((size_t)b * POOL_SLICES + slice) * C;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const int i = lane + 64 * k;
-            if (i < nv) {
-                float4 a = acc.v[k];
-                for (int w = 0; w < POOL_WAVES - 1; ++w) { const float4 o = red[w][i]; a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w; }
-                ((float4*)dst)[i] = a;
-            }
-        }
-    }
-}
-
-// ---- finish: slices added in slice order, mean over the N - 1 patch tokens, affine-free LayerNorm; one wave per sample ----
-template <int NV>
-__global__ __launch_bounds__(256)
-void probe_pool_norm_kernel(const float* __restrict__ scratch, float* __restrict__ feat, int B, int N, int C, float eps) {
-    const int lane = WavePerRow::lane(), b = WavePerRow::row(), nv = C >> 2;
-    if (b >= B) return;
-    RowVec<NV> acc, r;
-    load_row(acc, scratch + (size_t)b * POOL_SLICES * C, C, lane);
-    for (int s = 1; s < POOL_SLICES; ++s) {
-        load_row(r, scratch + ((size_t)b * POOL_SLICES + s) * C, C, lane);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) { acc.v[k].x += r.v[k].x; acc.v[k].y += r.v[k].y; acc.v[k].z += r.v[k].z; acc.v[k].w += r.v[k].w; }
-    }
-    const float inv = 1.0f / (float)(N - 1);
-#pragma unroll
-    for (int k = 0; k < NV; ++k) { acc.v[k].x *= inv; acc.v[k].y *= inv; acc.v[k].z *= inv; acc.v[k].w *= inv; }
-    float mean, rstd;
-    row_stats(acc, C, lane, eps, mean, rstd);
-    normalize_store(acc, mean, rstd, feat + (size_t)b * C, false, nv, lane);
-}
 
 // ---- the two contractions: 64 x 64 output tile, 256 threads with a 4 x 4 micro-tile each, 16 reduction steps per LDS tile ----
 #define PT 64
@@ -233,19 +174,14 @@ void probe_loss_mean_kernel(const float* __restrict__ row_loss, float* __restric
 
 // ---- launchers: arguments are validated before anything touches the device ----
 extern "C" int64_t uvit_op_probe_pool_ws_bytes(int B, int N, int C) {
-    if (B < 1 || B > POOL_MAX_B || N < 2 || C < 4 || (C % 4) || C > ROW_MAXV * 256) return UVIT_ERR_SHAPE;
-    return (int64_t)B * POOL_SLICES * C * (int64_t)sizeof(float);
+    if (probe_pool_bad_shape(B, N, C)) return UVIT_ERR_SHAPE;
+    return probe_pool_stream_bytes(B, C);
 }
 
 extern "C" int uvit_op_probe_pool_norm(const float* x, float* feat, float* scratch, int B, int N, int C, float eps, uvit_stream stream) {
     if (!x || !feat || !scratch) return UVIT_ERR_ARG;
-    if (B < 1 || N < 2 || C < 4 || (C % 4) || C > ROW_MAXV * 256 || B > POOL_MAX_B) return UVIT_ERR_SHAPE;
-    hipStream_t s = (hipStream_t)stream;
-    dispatch_nv(C, [&](auto nv) {
-        constexpr int NV = decltype(nv)::value;
-        hipLaunchKernelGGL((probe_pool_partial_kernel<NV>), dim3(POOL_SLICES, B), dim3(64 * POOL_WAVES), 0, s, x, scratch, N, C);
-        hipLaunchKernelGGL((probe_pool_norm_kernel<NV>), WavePerRow::grid(B), WavePerRow::block(), 0, s, (const float*)scratch, feat, B, N, C, eps);
-    });
+    if (probe_pool_bad_shape(B, N, C)) return UVIT_ERR_SHAPE;
+    probe_pool_launch(PoolStreams{{x, nullptr}, {feat, nullptr}}, 1, scratch, B, N, C, eps, (hipStream_t)stream);
     return uvit_check_launch();
 }
 

@@ -53,11 +53,14 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, VimMethods, 
     # per-sample uncertainty columns of evaluate(detection=True), larger = more uncertain: the three of uvit_op_detect_rows on the
     # logits; a head with an uncertainty of its own appends its columns
     DETECT_COLUMNS = ("msp", "entropy", "energy")
+    TWO_STREAM = False                       # the encoder family the class reads: True in DistProbe (dist_probe.py) alone
 
     def __init__(self, encoder, num_classes, smoothing=0.1, init_scale=0.001):
         super().__init__()
-        if getattr(encoder, "_two_stream", False):
+        if getattr(encoder, "_two_stream", False) and not self.TWO_STREAM:
             raise NotImplementedError("the linear probe reads the base model; the two-stream (mean, covariance) model is not supported")
+        if self.TWO_STREAM and not getattr(encoder, "_two_stream", False):
+            raise TypeError("encoder must be a DistVisionTransformerForCyclicalTraining: the two-stream probe reads the covariance stream")
         if not isinstance(encoder, VisionTransformerForCyclicalTraining):
             raise TypeError("encoder must be a VisionTransformerForCyclicalTraining")
         if encoder.training:

@@ -242,6 +242,9 @@ _PROTOTYPES = {
     "uvit_op_lap_variance_ws_bytes": (_i64, [_i, _i, _i]),
     "uvit_op_lap_variance": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "uvit_op_lap_probit": (_i, [_vp, _i64, _vp, C.c_double, _vp, _i64, _vp, _i, _i, _vp]),
+    "uvit_op_dprobe_pool_ws_bytes": (_i64, [_i, _i, _i]),
+    "uvit_op_dprobe_pool_norm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "uvit_op_dprobe_variance": (_i, [_vp, _vp, C.c_double, _vp, _vp, _i, _i, _i, _vp]),
     "uvit_op_maha_accumulate_ws_bytes": (_i64, [_i, _i, _i]),
     "uvit_op_maha_accumulate": (_i, [_vp] * 8 + [_i64, _i, _i, _i, _vp]),
     "uvit_op_maha_scores_ws_bytes": (_i64, [_i, _i, _i]),
