@@ -1015,6 +1015,53 @@ int64_t uvit_op_corrupt_ws_bytes(int kind, int B, int S);        /* < 0: UVIT_ER
 int uvit_op_corrupt_batch(const uint8_t* in_u8, float* out, int B, int S, int kind, const float* params, int n_params, uint32_t seed,
                           int64_t index0, const float* mean, const float* std, void* ws, int64_t ws_bytes, uvit_stream stream);
 
+/* ---- four more corruptions: pixelate, jpeg_compression, motion_blur, zoom_blur (csrc/corrupt_ext.hip) ----
+ * A second op beside uvit_op_corrupt_batch with the same contract: in_u8 and out as above, every kind forms a whole level q in [0, 255]
+ * and writes ((q / 255) - mean[c]) / std[c]; IEEE fp32 or integer arithmetic in a fixed order, no contraction, no atomics, no
+ * transcendental function on the device, so tests/corrupt_ext_ref.py restates all four bit for bit.  `table`: DEVICE memory of n_table
+ * 4-byte words, int32 or fp32 by kind, prepared once per set (corruptions_ext.ext_params); `arg`: the kind's integer, which fixes
+ * n_table.  Nothing is launched on an error:
+ *   UVIT_ERR_ARG        a NULL pointer, an unknown kind, an arg outside the kind's range, an n_table that does not fit (kind, S, arg), a
+ *                       mean or std that is not finite, a std of 0, an index0 outside [0, 2^32 - 1 - 21845]
+ *   UVIT_ERR_SHAPE      B outside [1, 21845], S outside [8, 1024], motion_blur with R >= S or R > 24
+ *   UVIT_ERR_WORKSPACE  ws_bytes below uvit_op_corrupt_ext_ws_bytes(kind, B, S, arg)
+ * PIXELATE (int32 table, arg = n in [1, S]): Pillow's resize((n, n), BOX) then resize((S, S), BOX), bit for bit.  Each resize is a
+ *   horizontal then a vertical pass with a uint8 intermediate (ws); a pass writes clip8((2^21 + sum_k pix[first + k] coef[k]) >> 22).
+ *   table = down bounds (n, 2) = (first, count) per output, down coefficients (n, kd), kd = 2 ceil(S / 2n) + 1, up bounds (S, 2), up
+ *   coefficients (S, 3): Resample.c's precompute_coeffs for the BOX filter, each coefficient int(0.5 + k 2^22), zero past the count.
+ * JPEG_COMPRESSION (fp32 table of 192, arg = 0): T[8][8], T[u][x] = c(u) / 2 cos((2 x + 1) u pi / 16), then the luminance and the
+ *   chrominance quantisation table, 64 each in natural order.  With P = S rounded up to a multiple of 16 and pixels past the image
+ *   repeating its last column and, for Y, its last row; for Cb and Cr a row y >= S repeats row min(((S - 1) & ~1) + (y & 1), S - 1), the
+ *   last pair of rows, so that the subsampled plane repeats its last row as libjpeg's does; r, g, b = float(u8):
+ *     Y = ((0.299 r + 0.587 g) + 0.114 b), Cb = ((-0.168736 r - 0.331264 g) + 0.5 b) + 128, Cr = ((0.5 r - 0.418688 g) - 0.081312 b) + 128
+ *     each of the three rounded to an 8-bit level, floor(clip(x, 0, 255) + 0.5), as a JPEG sample is
+ *     Cb, Cr subsampled 4:2:0 by libjpeg's integer mean: floor((((a00 + a01) + (a10 + a11)) + bias) 0.25), bias 1 in the even and 2 in
+ *     the odd chroma columns
+ *     per 8 x 8 block of p - 128: t[y][u] = sum_x T[u][x] p[y][x], F[v][u] = sum_y T[v][y] t[y][u], F' = rintf(F / Q[v][u]) Q[v][u],
+ *     s[y][u] = sum_v T[v][y] F'[v][u], p'[y][x] = (sum_u T[u][x] s[y][u]) + 128; every sum one accumulator from 0, index ascending
+ *     chroma back to P x P: 0.75 near + 0.25 far per axis (far = the other neighbour of the fine pixel, clamped to the image's
+ *     ceil(S / 2) samples), first
+ *     vertically on both columns, then horizontally; cb = Cb - 128, cr = Cr - 128
+ *     R = Y + 1.402 cr, G = (Y - 0.344136 cb) - 0.714136 cr, B = Y + 1.772 cb; q = floor(clip(x, 0, 255) + 0.5), cropped to S
+ *   The fp32 planes Y (P, P), Cb, Cr (P/2, P/2) of every image live in ws between the two launches.
+ * MOTION_BLUR (fp32 table of (R + 1) 183, arg = R): w[R + 1], then per direction a = 0 .. 90 (theta = a - 45 degrees) ox[R + 1] and
+ *   oy[R + 1], the whole numbers rint(i cos theta), rint(i sin theta).  v = float(u8) / 255;
+ *   v'(y, x) = sum_i w_i v(clamp(y - oy_i), clamp(x - ox_i)), i ascending, acc = acc + (w x); q as in uvit_op_corrupt_batch.
+ *   a = ((h(key ^ 0x1B873593) >> 8) 91) >> 24 with key = h(h(seed ^ (9 + kind + 1) 0x9E3779B9) ^ (index0 + b + 1) 0x85EBCA6B): the image
+ *   key of uvit_op_corrupt_batch with the kinds numbered on from its nine.  The only kind that reads seed and index0.
+ * ZOOM_BLUR (fp32 table of n, arg = n in [1, 32]): 1 / z_j.  v' = (v + sum_j zoom_j(v)) / float(n + 1), j ascending, one accumulator
+ *   that starts at v; zoom_j(v)(y, x) samples at sx = c + (x - c) (1 / z_j), sy likewise, c = (S - 1) / 2: x0 = floor(sx), fx = sx - x0,
+ *   x1 = min(x0 + 1, S - 1), top = v00 + (v01 - v00) fx, bot = v10 + (v11 - v10) fx, top + (bot - top) fy. */
+#define UVIT_CORRUPT_EXT_PIXELATE 0
+#define UVIT_CORRUPT_EXT_JPEG_COMPRESSION 1
+#define UVIT_CORRUPT_EXT_MOTION_BLUR 2
+#define UVIT_CORRUPT_EXT_ZOOM_BLUR 3
+#define UVIT_CORRUPT_EXT_KINDS 4
+int64_t uvit_op_corrupt_ext_ws_bytes(int kind, int B, int S, int arg);      /* < 0: UVIT_ERR_ARG (kind, arg) or UVIT_ERR_SHAPE; may be 0 */
+int uvit_op_corrupt_ext_batch(const uint8_t* in_u8, float* out, int B, int S, int kind, const void* table, int n_table, int arg,
+                              uint32_t seed, int64_t index0, const float* mean, const float* std, void* ws, int64_t ws_bytes,
+                              uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

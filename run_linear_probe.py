@@ -146,13 +146,15 @@ l)` after `* Acc@1`, and log.txt gains `test_layer_weights`.  Checkpoints hold `
 --resume refuses one without the third key or of another depth.  --calibration, --detection / --ood_data_path, --ts_*, --cp_*,
 --maha_*, --knn_*, --vim_* and --perturbation_path work unchanged on the mixed feature and its logits.
 
-`--eval --corruptions NAME ... | all` (with --eval_data_path) adds the reference's c_evaluate() behind the evaluation, on corruptions
+`--eval --corruptions NAME ... | all | full` (with --eval_data_path) adds the reference's c_evaluate() behind the evaluation, on corruptions
 generated on the device (uncertainty-vit_amd/corruptions.py): the clean evaluation images are decoded once and
 kept on the device as uint8 (`--corruption_cache_images N`, default 65536; a larger folder is read again per set), and every
 (corruption, severity) set -- gaussian_noise, speckle_noise, impulse_noise, shot_noise, brightness, saturate, contrast, gaussian_blur,
-defocus_blur at `--corruption_severities` (default 1 2 3 4 5), noise seeded by `--corruption_seed` (default 0) -- is one evaluation with
-the run's own switches.  The constants are ImageNet-C's as remembered, unverified: the figures are ImageNet-C-style, not the published
-benchmark.  `--corruption_path DIR` (exclusive with --corruptions) reads a pre-made tree DIR/<distortion>/<severity>/<class>/... with
+defocus_blur (`all`: these nine) and pixelate, jpeg_compression, motion_blur, zoom_blur (uncertainty-vit_amd/corruptions_ext.py, section
+9.18; `full`: the nine followed by these four) at `--corruption_severities` (default 1 2 3 4 5), noise and motion_blur's direction
+seeded by `--corruption_seed` (default 0) -- is one evaluation with the run's own switches.  The constants are ImageNet-C's as
+remembered, unverified, and jpeg_compression, motion_blur and zoom_blur are this project's definitions, not libjpeg's, ImageMagick's or
+scipy's bytes: the figures are ImageNet-C-style, not the published benchmark.  `--corruption_path DIR` (exclusive with --corruptions) reads a pre-made tree DIR/<distortion>/<severity>/<class>/... with
 the evaluation pipeline instead: the reference's DISTORTIONS order first, then the other sub-folders sorted; a missing severity folder
 is an error.  The run prints `Corrupted dataset evaluation :`, `Distortion : <name>`, per severity `* Acc@1 ... CE ... ` (followed by
 the set's calibration line, variance mean and detection lines when the run has them), `mCE (unnormalized) (%): ..., acc :...` and
@@ -314,7 +316,8 @@ def get_args(argv=None):
       help="two-stream --model: the scale s of the feature variance v = s (ELU(c) + 1) (default 1.0)")
     a("--corruptions", type=str, nargs="+", default=argparse.SUPPRESS, metavar="NAME",
       help="with --eval and --eval_data_path: evaluate under these corruptions of the clean evaluation images, generated on the device "
-           "(names of uncertainty_vit_amd.corruptions.CORRUPTIONS, or `all`); the reference's c_evaluate()")
+           "(names of uncertainty_vit_amd.corruptions.CORRUPTIONS and corruptions_ext.CORRUPTIONS_EXT, or `all`: the former, or `full`: "
+           "both); the reference's c_evaluate()")
     a("--corruption_severities", type=int, nargs="+", default=argparse.SUPPRESS, metavar="S", help="the severities to sweep, a subset of 1 .. 5 (default: all five)")
     a("--corruption_seed", type=int, default=argparse.SUPPRESS, help="seed of the noise corruptions (default 0)")
     a("--corruption_cache_images", type=int, default=argparse.SUPPRESS, metavar="N",
@@ -784,14 +787,18 @@ def check_corruption_flags(args):
 
 
 def corruption_names(args):
-    """--corruptions as a list of kinds in the order given (`all`: every kind, in CORRUPTIONS' order); an unknown or repeated name is refused."""
+    """--corruptions as a list of kinds in the order given (`all`: the nine of CORRUPTIONS in their order; `full`: those followed by the
+    four of CORRUPTIONS_EXT); an unknown or repeated name is refused."""
     from uncertainty_vit_amd.corruptions import CORRUPTIONS
+    from uncertainty_vit_amd.corruptions_ext import CORRUPTIONS_EXT
     names = list(args.corruptions)
     if names == ["all"]:
         return list(CORRUPTIONS)
+    if names == ["full"]:
+        return list(CORRUPTIONS + CORRUPTIONS_EXT)
     for n in names:
-        if n not in CORRUPTIONS:
-            raise ValueError(f"--corruptions: unknown corruption {n!r}; one of {', '.join(CORRUPTIONS)}, or `all` alone")
+        if n not in CORRUPTIONS + CORRUPTIONS_EXT:
+            raise ValueError(f"--corruptions: unknown corruption {n!r}; one of {', '.join(CORRUPTIONS + CORRUPTIONS_EXT)}, or `all` or `full` alone")
     if len(set(names)) != len(names):
         raise ValueError("--corruptions names a corruption twice")
     return names

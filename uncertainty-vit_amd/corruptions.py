@@ -226,16 +226,19 @@ class CleanCache:
 
 class CorruptedSet:
     """One (corruption, severity) set as a loader of LinearProbe.evaluate: yields (images, labels), both on the device, the images
-    corrupted by uvit_op_corrupt_batch.  `source` is a DevicePrefetcher over the evaluation loader -- each of its batches is packed to
+    corrupted by uvit_op_corrupt_batch, or by uvit_op_corrupt_ext_batch for a kind of corruptions_ext.CORRUPTIONS_EXT.  `source` is a DevicePrefetcher over the evaluation loader -- each of its batches is packed to
     uint8 (uvit_op_corrupt_pack) and appended to `cache` when one is given, which is marked complete behind the last batch -- or a
     ready CleanCache.  Both launches go on the current stream.  The bytes of a set depend on (kind, severity, seed) and the image's
     position in the set, not on the batch size or on which of the two sources it is read from."""
 
     def __init__(self, source, kind, severity, seed, mean, std, cache=None):
+        from . import corruptions_ext as ext
         self.source, self.kind, self.severity, self.cache = source, kind, int(severity), cache
         self.seed, self.mean, self.std = set_seed(seed, severity), tuple(mean), tuple(std)
-        self._params, self._params_size, self._corrupt_ws = None, None, None
-        constant(kind, self.severity)
+        self._params, self._params_size, self._params_device, self._corrupt_ws = None, None, None, None
+        # the family: the nine of this module, or the four of corruptions_ext.py (a table object with .to(device), another op)
+        self._ext = ext if kind in ext.CORRUPTIONS_EXT else None
+        (ext.ext_constant if self._ext else constant)(kind, self.severity)
 
     def __len__(self):
         return len(self.source)
@@ -264,7 +267,11 @@ class CorruptedSet:
     def __iter__(self):
         for u8, labels, index0 in self._batches():
             S = u8.shape[-1]
-            if self._params is None or self._params.device != u8.device or self._params_size != S:
-                self._params = torch.from_numpy(corruption_params(self.kind, self.severity, S)).to(u8.device)
-                self._params_size = S
-            yield corrupt(self, u8, self.kind, self._params, self.seed, index0, self.mean, self.std), labels
+            if self._params is None or self._params_device != u8.device or self._params_size != S:
+                if self._ext:
+                    self._params = self._ext.ext_params(self.kind, self.severity, S).to(u8.device)
+                else:
+                    self._params = torch.from_numpy(corruption_params(self.kind, self.severity, S)).to(u8.device)
+                self._params_size, self._params_device = S, u8.device
+            op = self._ext.corrupt_ext if self._ext else corrupt
+            yield op(self, u8, self.kind, self._params, self.seed, index0, self.mean, self.std), labels

@@ -38,7 +38,6 @@ __device__ __forceinline__ float quantise(float v) { return floorf(fminf(fmaxf(v
 __device__ __forceinline__ float normalise(float q, float m, float s) { return (q / 255.0f - m) / s; }
 
 // ---- counter-based draws ----
-__host__ __device__ __forceinline__ uint32_t image_key(uint32_t kseed, uint32_t index) { return uvit_hash32(kseed ^ ((index + 1u) * 0x85EBCA6Bu)); }
 __device__ __forceinline__ uint32_t draw_key1(uint32_t ikey) { return uvit_hash32(ikey ^ 0x1B873593u); }
 __device__ __forceinline__ uint32_t draw_key2(uint32_t ikey) { return uvit_hash32(ikey ^ 0xCC9E2D51u); }
 __device__ __forceinline__ float uniform_open(uint32_t h) { return (float)((h >> 8) + 1u) * 5.9604644775390625e-08f; }    // (0, 1], exact
@@ -123,7 +122,7 @@ void corrupt_point_kernel(const uint8_t* __restrict__ in, float* __restrict__ ou
     const int b = blockIdx.y;
     const uint8_t* src = in + (size_t)b * 3 * plane + p0;
     float* dst = out + (size_t)b * 3 * plane + p0;
-    const uint32_t ikey = image_key(kseed, index0 + (uint32_t)b), k1 = draw_key1(ikey), k2 = draw_key2(ikey);
+    const uint32_t ikey = corrupt_image_key(kseed, index0 + (uint32_t)b),k1 = draw_key1(ikey), k2 = draw_key2(ikey);
     uint8_t u[3][VEC];
     float res[3][VEC];
 #pragma unroll

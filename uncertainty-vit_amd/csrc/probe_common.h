@@ -1,4 +1,4 @@
-// Shared helpers of the probe translation units (probe, calib, stability, gp, het, ens, detect, tscale, conformal, laplace, maha, knn, vim, mcd, layerweights, corrupt, dprobe),
+// Shared helpers of the probe translation units (probe, calib, stability, gp, het, ens, detect, tscale, conformal, laplace, maha, knn, vim, mcd, layerweights, corrupt, corrupt_ext, dprobe),
 // on top of common.h.  These files are built WITHOUT -ffast-math: each states in its own header which IEEE property it relies on and
 // refuses to compile under __FAST_MATH__.  Nothing here reorders a sum: a wave sum is the xor tree from distance 32 down to 1.
 #pragma once
@@ -65,6 +65,11 @@ __device__ __forceinline__ float fold_zero(float v) { return v == 0.f ? 0.f : v;
     }
 __device__ __forceinline__ void cmpx(unsigned long long& a, unsigned long long& b, bool asc) {
     if ((a > b) == asc) { const unsigned long long t = a; a = b; b = t; }
+}
+
+// ---- the corruption ops' key of image `index` of a set (corrupt.hip, corrupt_ext.hip): kseed carries the set's seed and the kind ----
+__host__ __device__ __forceinline__ uint32_t corrupt_image_key(uint32_t kseed, uint32_t index) {
+    return uvit_hash32(kseed ^ ((index + 1u) * 0x85EBCA6Bu));
 }
 
 // ---- one wave per row: workgroups of four waves, wave w of workgroup g owns row 4 g + w ----
