@@ -696,6 +696,45 @@ int64_t uvit_op_detect_ws_bytes(int N, int S);
 int uvit_op_detect_metrics(const float* scores, int64_t ld, const uint8_t* flags, int N, int S, int32_t* order, double* out, void* ws,
                            int64_t ws_bytes, uvit_stream stream);
 
+/* ---- set-level calibration of an evaluation set: ECE / MCE / OE, NLL, Brier, SCE, ACE, TACE and per-class AUROC, DESIGN.md section
+ * 9.19 ----
+ * The store of an evaluation is row-major: row n of the fp32 probabilities starts at probs + n ld, ld >= K, beside one int64 label per
+ * row.  Every call checks its arguments before it touches the device (UVIT_ERR_ARG for a NULL required pointer, a misaligned
+ * workspace or a NaN threshold, UVIT_ERR_SHAPE for a size outside the stated limits, UVIT_ERR_WORKSPACE, outputs untouched), is
+ * asynchronous on `stream` and never reads back.  No atomics; every sum has one owner and an order that depends on (N, K, the bin
+ * counts) and the values alone -- not on ld, on timing or on the batches that filled the store -- so the same set gives the same bits.
+ * All bin accuracies are the mean over the rows of the bin (the reading positional_acc = 0 of the per-batch ops). */
+/* Per batch, one wave per row of logits z (N, K) fp32, N >= 1 (no upper limit), K >= 1: row n of softmax(z) to probs + n ld, with the
+ * arithmetic of uvit_op_calib_softmax (the same bytes at ld == K).  The caller offsets `probs` to the batch's first row of the store. */
+int uvit_op_scal_probs(const float* logits, float* probs, int64_t ld, int N, int K, uvit_stream stream);
+/* Set level, 1 <= N <= 2^20 rows, 1 <= K, N K <= 2^30, every bin count in 1 .. 64.  ece_bounds / cw_bounds: host arrays of bins + 1
+ * doubles (np.linspace(0, 1, bins + 1)); they travel by value.  Every comparison is the fp32 probability widened to double against a
+ * double bound.
+ * Per row: conf = max_k p_k, pred = the lowest index attaining it, correct = [pred == y], nll = -log(clamp(p_y / sum_k p_k, eps,
+ * 1 - eps)) as uvit_op_calib_confidence, brier = sum_k (p_k - [k == y])^2 in double.
+ * Top label, over ece_bins equal-width bins lo < conf <= up: top_table (ece_bins, 3) = (prop, acc, conf) per bin (zeros for an empty
+ * bin); ECE = sum prop |conf - acc|, MCE = max |conf - acc|, OE = sum prop conf max(conf - acc, 0); NLL and Brier are row means.
+ * Per class c, on the column p[:, c] with hit = [y == c]: SCE_c over cw_bins equal-width bins; ACE_c (threshold 0, ace_bins) and
+ * TACE_c (tace_threshold, tace_bins) over adaptive bins -- values under the threshold become 0, the bounds are every (N / bins)-th
+ * sorted value plus 1.0, bin i holds lo_i < v <= up_i with weight count / N; AUROC_c = P(p_pos > p_neg) + P(p_pos == p_neg) / 2
+ * from int64 pair counts, NaN without a positive or without a negative row.
+ * per_class (K, 6) = SCE_c, ACE_c, TACE_c, AUROC_c, n_pos, #{v >= tace_threshold}.
+ * out[16] = ECE, MCE, OE, NLL, Brier, SCE, ACE, TACE (means over all K classes), mean AUROC_c over the classes that have one, how
+ * many have one, accuracy, mean confidence, N, bad rows, 0, 0.  A row is bad when its label lies outside [0, K) (nothing is read at
+ * it) or one of its probabilities is not finite; one bad row makes out[0 .. 11] NaN.  For the sort alone a value is clamped to
+ * [0, 1], so no input makes a kernel index out of range.
+ * One bitonic sort of 32-bit keys (value bits << 1 | hit) serves every per-class metric and, with the confidence column as column
+ * K, the top-label bins: every bin is a contiguous run of a sorted column.  8192-key chunks in LDS, one launch per compare-exchange
+ * distance >= 8192, every column of a group in the same launch.  ws: 16-byte aligned; uvit_op_scal_ws_bytes(N, K) (< 0: the
+ * UVIT_ERR_* of the call) is 21 N bytes rounded up plus the keys of one group of columns, at most 2^26 keys = 256 MB, all K + 1
+ * columns when they fit.  A smaller workspace is accepted down to one column of keys (uvit_op_scal_ws_bytes(N, 1) holds two): the
+ * groups get smaller, the launches more, the results keep their bits.  uvit_op_scal_launches: the kernel launches of the call. */
+int64_t uvit_op_scal_ws_bytes(int N, int K);
+int64_t uvit_op_scal_launches(int N, int K, int64_t ws_bytes);
+int uvit_op_scal_metrics(const float* probs, int64_t ld, const int64_t* labels, int N, int K, const double* ece_bounds, int ece_bins,
+                         const double* cw_bounds, int cw_bins, int ace_bins, int tace_bins, double tace_threshold, double* out,
+                         double* top_table, double* per_class, void* ws, int64_t ws_bytes, uvit_stream stream);
+
 /* ---- post-hoc temperature scaling, fitted and applied on the device, DESIGN.md section 9.7 ----
  * s = 1 / T minimises f(s) = (1 / n) sum_i [ log sum_k exp(s z_ik) - s z_i,y_i ], the mean NLL of softmax(z / T), over
  * [1 / t_max, 1 / t_min]; g = f' = (1 / n) sum_i [ sum_k p_ik z_ik - z_i,y_i ] is non-decreasing and h = f'' = (1 / n) sum_i Var_p_i[z_i].

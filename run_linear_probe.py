@@ -15,6 +15,16 @@ with resize + center crop (level 1), both augmented on the device.  Single GPU. 
 metrics to every evaluation: a second line `* ECE ... TACE ... NLL ... AUROC ...` and `test_ECE`, `test_TACE`, `test_NLL`,
 `test_AUROC` in log.txt (with --eval: one entry of the test figures, when --output_dir is given).
 
+`--set_calibration` (an addition to the reference; beside --calibration or without it) reports the calibration of the evaluation set
+as a whole instead of means of per-batch values: every labelled batch's probabilities and labels go into a device store, one call
+behind the last batch (csrc/setcalib.hip) gives top-label ECE, MCE and OE with the reliability table, NLL, the
+Brier score and per class SCE, ACE, TACE and AUROC, all with the textbook bin accuracy.  Every evaluation prints `* Set ECE .. MCE ..
+OE .. NLL .. Brier .. SCE .. ACE .. TACE .. AUROC .. on <n> images (<c> classes with an AUROC)` behind the `* Acc@1` (and `* ECE`)
+line; log.txt gains `test_set_{ECE,MCE,OE,NLL,Brier,SCE,ACE,TACE,AUROC}` and `test_set_reliability`, --output_dir with --eval gains
+`reliability.json`; every set of a corruption sweep gains the line and `test_c_<name>_<severity>_set_<key>`, the per-severity summary
+`set-ECE .. Brier ..` and `test_c_severity_set_{ECE,NLL,Brier}`.  `--scal_ece_bins` (15), `--scal_cw_bins` (15), `--scal_ace_bins` (15),
+`--scal_tace_bins` (30), `--scal_tace_threshold` (0.01) steer it and are refused without it.
+
 `--eval --perturbation_path DIR [--perturbations NAME ...]` adds the reference's p_evaluate() behind the evaluation: every `DIR/NAME.npy`
 (without --perturbations: every `DIR/*.npy`, sorted) is an (N, F, H, W, 3) uint8 array of N sequences of F frames (the CIFAR-100-P
 layout).  Per perturbation the flipping probability, the top-5 distance and the Zipf distance are printed in the reference's format
@@ -215,6 +225,15 @@ def get_args(argv=None):
     # absent unless given (SUPPRESS): without the flag the parsed arguments, and so the first line printed, are what they were
     a("--calibration", action="store_true", default=argparse.SUPPRESS,
       help="also report ECE, TACE, NLL and AUROC of the evaluation (the reference's evaluate() beside Acc@1 / Acc@5)")
+    a("--set_calibration", action="store_true", default=argparse.SUPPRESS,
+      help="also report the calibration of the evaluation set as a whole: ECE, MCE, OE, NLL, Brier, SCE, ACE, TACE and per-class AUROC "
+           "from one set-level call on the device (textbook bin accuracies), with the reliability table")
+    a("--scal_ece_bins", type=int, default=argparse.SUPPRESS, metavar="N", help="with --set_calibration: top-label bins, 1 .. 64 (default 15)")
+    a("--scal_cw_bins", type=int, default=argparse.SUPPRESS, metavar="N", help="with --set_calibration: SCE's bins per class, 1 .. 64 (default 15)")
+    a("--scal_ace_bins", type=int, default=argparse.SUPPRESS, metavar="N", help="with --set_calibration: ACE's adaptive bins, 1 .. 64 (default 15)")
+    a("--scal_tace_bins", type=int, default=argparse.SUPPRESS, metavar="N", help="with --set_calibration: TACE's adaptive bins, 1 .. 64 (default 30)")
+    a("--scal_tace_threshold", type=float, default=argparse.SUPPRESS, metavar="T",
+      help="with --set_calibration: probabilities under T count as 0 in TACE (default 0.01)")
     a("--perturbation_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
       help="with --eval: directory of perturbation sequences, NAME.npy of shape (N, F, H, W, 3) uint8 (the reference's p_evaluate())")
     a("--perturbations", type=str, nargs="+", default=argparse.SUPPRESS, metavar="NAME",
@@ -339,6 +358,48 @@ MCD_KEYS = ("mcd_total", "mcd_aleatoric", "mcd_mi", "mcd_var", "mcd_disagreement
 
 def calibration_line(stats):
     return "* ECE {ECE:.5f} TACE {TACE:.5f} NLL {NLL:.5f} AUROC {AUROC:.5f}".format(**stats)
+
+
+SCAL_FLAGS = ("scal_ece_bins", "scal_cw_bins", "scal_ace_bins", "scal_tace_bins", "scal_tace_threshold")
+SCAL_LINE_KEYS = ("ECE", "MCE", "OE", "NLL", "Brier", "SCE", "ACE", "TACE", "AUROC")
+SCAL_SUMMARY_KEYS = ("ECE", "NLL", "Brier")
+
+
+def check_scal_flags(args):
+    """The settings of --set_calibration (a dict for enable_set_calibration), or None without the flag; the --scal_* flags steer it
+    and are refused without it, as is a value outside the kernels' limits."""
+    given = [f for f in SCAL_FLAGS if hasattr(args, f)]
+    if not getattr(args, "set_calibration", False):
+        if given:
+            raise ValueError("--" + " / --".join(given) + " steer the set-level calibration: give --set_calibration")
+        return None
+    out = {f[len("scal_"):]: getattr(args, f) for f in given}
+    for k, v in out.items():
+        if k.endswith("_bins") and not 1 <= v <= 64:
+            raise ValueError(f"--scal_{k} must be in 1 .. 64, got {v}")
+    if not 0.0 <= out.get("tace_threshold", 0.01) <= 1.0:
+        raise ValueError(f"--scal_tace_threshold must be in [0, 1], got {out['tace_threshold']}")
+    return out
+
+
+def set_calibration_line(sc):
+    return ("* Set ECE {ECE:.5f} MCE {MCE:.5f} OE {OE:.5f} NLL {NLL:.5f} Brier {Brier:.5f} SCE {SCE:.5f} ACE {ACE:.5f} TACE {TACE:.5f} "
+            "AUROC {AUROC:.5f} on {n} images ({auroc_classes} classes with an AUROC)").format(**sc)
+
+
+def set_calibration_log_entries(sc, prefix="test_set_"):
+    """What log.txt gains: the nine set-level numbers and, for the evaluation itself, the reliability table [[prop, acc, conf], ...]."""
+    out = {prefix + k: sc[k] for k in SCAL_LINE_KEYS}
+    if prefix == "test_set_":
+        out["test_set_reliability"] = sc["reliability"]
+    return out
+
+
+def write_reliability(output_dir, sc):
+    """reliability.json: the bin table and the per-class arrays of the evaluation."""
+    with open(os.path.join(output_dir, "reliability.json"), mode="w", encoding="utf-8") as f:
+        json.dump({"n": sc["n"], "n_bad": sc["n_bad"], "reliability": sc["reliability"], "per_class": sc["per_class"]}, f)
+        f.write("\n")
 
 
 def gp_variance_line(stats):
@@ -839,6 +900,8 @@ def corruption_set_lines(stats):
     lines = [corruption_set_line(stats)]
     if "ECE" in stats:
         lines.append(calibration_line(stats))
+    if "set_calibration" in stats:
+        lines.append(set_calibration_line(stats["set_calibration"]))
     lines += [fmt(stats) for key, fmt in VAR_MEAN_LINES if key in stats]
     if "detection" in stats:
         lines += detection_lines(stats["detection"])
@@ -850,6 +913,8 @@ def corruption_log_entries(name, severity, stats):
     out = {"acc1": stats["acc1"], "acc5": stats["acc5"], "loss": stats["loss"], "ce": (100 - stats["acc1"]) / 100}
     out.update({k: stats[k] for k in CALIB_KEYS if k in stats})
     out.update({k: stats[k] for k, _ in VAR_MEAN_LINES if k in stats})
+    if "set_calibration" in stats:
+        out.update(set_calibration_log_entries(stats["set_calibration"], prefix="set_"))
     if "detection" in stats:
         out.update({k[len("test_"):]: v for k, v in detection_log_entries(stats["detection"]).items()})
     return {f"test_c_{name}_{severity}_{k}": v for k, v in out.items()}
@@ -871,6 +936,9 @@ def corruption_summary(results, clean_stats):
     for key in ("ECE", "NLL"):
         if all(key in s for s in sets):
             out[key] = [float(np.mean([s[key] for s in rows[v]])) for v in sevs]
+    if all("set_calibration" in s for s in sets):
+        for key in SCAL_SUMMARY_KEYS:
+            out["set_" + key] = [float(np.mean([s["set_calibration"][key] for s in rows[v]])) for v in sevs]
     return out
 
 
@@ -881,13 +949,15 @@ def corruption_summary_lines(summary):
         line = "* Severity {} Acc@1 {:.4f} CE {:.4f} rel-CE {:.4f}".format(sev, summary["acc1"][i], summary["ce"][i], summary["rel_ce"][i])
         if "ECE" in summary:
             line += " ECE {:.5f} NLL {:.5f}".format(summary["ECE"][i], summary["NLL"][i])
+        if "set_ECE" in summary:
+            line += " set-ECE {:.5f} Brier {:.5f}".format(summary["set_ECE"][i], summary["set_Brier"][i])
         lines.append(line)
     return lines
 
 
 def corruption_summary_log(summary):
     out = {"test_c_mce": summary["mce"], "test_c_acc": summary["acc"], "test_c_severity_levels": summary["severities"]}
-    out.update({f"test_c_severity_{k}": summary[k] for k in ("acc1", "ce", "rel_ce", "ECE", "NLL") if k in summary})
+    out.update({f"test_c_severity_{k}": summary[k] for k in ("acc1", "ce", "rel_ce", "ECE", "NLL", "set_ECE", "set_NLL", "set_Brier") if k in summary})
     return out
 
 
@@ -984,6 +1054,7 @@ def main(args):
     knn = check_knn_flags(args)
     vim = check_vim_flags(args)
     corruption_mode = check_corruption_flags(args)
+    scal = check_scal_flags(args)
     if corruption_mode == "path":
         corruption_folders(args)                  # a missing folder stops the run here, not behind the main evaluation
     detection = detection or maha is not None or knn is not None or vim is not None
@@ -1168,6 +1239,8 @@ def main(args):
                                      score=getattr(args, "cp_score", "aps"), lam=getattr(args, "cp_lambda", 0.01) if raps else 0.0,
                                      kreg=getattr(args, "cp_kreg", 5) if raps else 0, randomized=getattr(args, "cp_randomized", False),
                                      seed=getattr(args, "cp_seed", 0), **cp_temp, **cp_kw)
+    if scal is not None:
+        probe.enable_set_calibration(**scal)      # behind the fits: their passes over the calibration folders store nothing
     evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration, **gp_eval)      # noqa: E731
     extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ()) + (("het_var_mean",) if het_layer else ()) + \
         (("dist_var_mean", "dist_trace_mean") if dist else ())
@@ -1204,18 +1277,23 @@ def main(args):
             print(layer_weights_line(stats["layer_weights"]))
         if calibration:
             print(calibration_line(stats))
+        if scal is not None:
+            print(set_calibration_line(stats["set_calibration"]))
+            if args.output_dir:
+                write_reliability(args.output_dir, stats["set_calibration"])
         if detection:
             print("\n".join(detection_lines(stats["detection"])))
         if conformal:
             stats["conformal_fit"] = cp_fit
             stats["conformal"] = probe.evaluate_conformal(DevicePrefetcher(loader_val, device), **cp_temp, **cp_kw)["conformal"]
             print("\n".join(conformal_lines(cp_fit, stats["conformal"])))
-        if (extra_keys or ensembles or mcd or lw or detection or ts_mode or conformal or laplace) and args.output_dir:
+        if (extra_keys or ensembles or mcd or lw or detection or ts_mode or conformal or laplace or scal is not None) and args.output_dir:
             with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
                 f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
                                     **(ens_log_entries(stats) if ensembles else {}),
                                     **(mcd_log_entries(stats) if mcd else {}),
                                     **({"test_layer_weights": stats["layer_weights"]} if lw else {}),
+                                    **(set_calibration_log_entries(stats["set_calibration"]) if scal is not None else {}),
                                     **(detection_log_entries(stats["detection"]) if detection else {}),
                                     **(temperature_log_entries(stats, ts_fit) if ts_mode else {}),
                                     **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {}),
@@ -1280,6 +1358,8 @@ def main(args):
             print(layer_weights_line(stats["layer_weights"]))
         if calibration:
             print(calibration_line(stats))
+        if scal is not None:
+            print(set_calibration_line(stats["set_calibration"]))
         print(f"Epoch {epoch}: loss: {log.loss.global_avg:.4f}  lr: {log.lr.value:.8f}  acc1: {stats['acc1']:.3f}  acc5: {stats['acc5']:.3f}")
         if args.output_dir:
             save_probe(args, probe, epoch)
@@ -1289,6 +1369,7 @@ def main(args):
                                     **(ens_log_entries(stats) if ensembles else {}),
                                     **(mcd_log_entries(stats) if mcd else {}),
                                     **({"test_layer_weights": stats["layer_weights"]} if lw else {}),
+                                    **(set_calibration_log_entries(stats["set_calibration"]) if scal is not None else {}),
                                     **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {})})
                         + "\n")
     print("Training time %.0f s" % (time.time() - t0))

@@ -23,6 +23,7 @@ from .probe_conformal import CP_KINDS, CP_MAX_A, CP_MAX_K, CP_MAX_N, CP_TABLE, C
 from .probe_density import MAHA_COLUMNS, MAHA_MAX_C, MAHA_MAX_K, MAHA_SHRINKAGE, DensityMethods, FeatureDensity           # noqa: F401
 from .probe_detect import DETECT_KEYS, DETECT_MAX_N, DETECT_MAX_S, DetectionMixin                                         # noqa: F401
 from .probe_neighbours import KNN_COLUMNS, KNN_K, KNN_MAX_C, KNN_MAX_K, KNN_MAX_N, KNN_TEMPERATURE, NeighbourBank, NeighbourMethods  # noqa: F401
+from .probe_setcalib import SCAL_CLASS_KEYS, SCAL_DEFAULTS, SCAL_KEYS, SCAL_MAX_BINS, SCAL_MAX_N, SCAL_MAX_NK, SetCalibrationMixin  # noqa: F401
 from .probe_stability import STABILITY_MAX_FRAMES, StabilityMixin                                                         # noqa: F401
 from .probe_temperature import TS_MAX_ITER, TS_MAX_N, TS_STATUS, TS_T_MAX, TS_T_MIN, TS_TOL, TemperatureMixin             # noqa: F401
 from .probe_util import column_mean, labelled_batches, ws_size
@@ -43,10 +44,10 @@ def _timm_trunc_normal_(t, std):
     return t
 
 
-class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, VimMethods, TemperatureMixin, ConformalMixin, StabilityMixin, nn.Module):
+class LinearProbe(DetectionMixin, SetCalibrationMixin, DensityMethods, NeighbourMethods, VimMethods, TemperatureMixin, ConformalMixin, StabilityMixin, nn.Module):
     """`encoder`: a VisionTransformerForCyclicalTraining in .eval() (it is NOT a sub-module: state_dict() holds `head.weight`
     (K, C) and `head.bias` (K,), the reference's keys).  Owns the head, gradient and Adam moment arenas.  The post-hoc families are
-    the mixins of probe_detect.py, probe_temperature.py, probe_conformal.py and probe_stability.py; the three feature-side scores
+    the mixins of probe_detect.py, probe_setcalib.py, probe_temperature.py, probe_conformal.py and probe_stability.py; the three feature-side scores
     are objects (probe_density.py, probe_neighbours.py, probe_vim.py) that `_scores` holds in the order of their detection columns."""
 
     BETAS, EPS = (0.9, 0.999), 1e-8          # create_optimizer's adamw defaults (optim_factory.py:133-134)
@@ -73,6 +74,8 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, VimMethods, 
         object.__setattr__(self, "encoder", encoder)
         self.num_classes, self.embed_dim, self.smoothing = K, Cd, float(smoothing)
         self._det, self._det_ws, self._in_ood = None, None, False
+        # set-level calibration: the settings while it is enabled, the store of the running evaluation, the metrics' workspace
+        self._scal, self._scal_eval, self._scal_ws = None, None, None
         # post-hoc temperature: host (T, s) of the fitted or set value, its device table, the table of the running evaluation, the
         # fit's workspace.  Plain attributes: state_dict() does not see them
         self._ts, self._ts_table, self._ts_on, self._ts_ws = None, None, None, None
@@ -123,7 +126,7 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, VimMethods, 
         self._arena = new.contiguous()
         self._grad_arena, self.exp_avg, self.exp_avg_sq = (fn(t).contiguous() for t in (self._grad_arena, self.exp_avg, self.exp_avg_sq))
         self._buf_batch = self._calib_batch = self._rank_rows = self._seq_rows = 0
-        self._det_ws = self._ts_table = self._ts_ws = self._cp = self._cp_ws = None
+        self._det_ws = self._scal_ws = self._ts_table = self._ts_ws = self._cp = self._cp_ws = None
         for score in self._scores:                   # a density and a ViM fit stay float64 (their host parts stay on the host), a bank bf16
             score.moved(new.device)
         self._rebind()
@@ -325,18 +328,24 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, VimMethods, 
         table, so loss, accuracy counters, the calibration ops and the three detection columns of the logits (msp, entropy, energy)
         see z / T, and stats gains "temperature".  Not scaled, because they are formed before the combination or do not depend on the
         scale of the logits: the members' own lines and the ens_* columns of an ensemble, gp_var, het_var, and everything
-        evaluate_stability reports (ranks do not depend on T)."""
+        evaluate_stability reports (ranks do not depend on T).
+        While set-level calibration is enabled (enable_set_calibration), every labelled batch also writes softmax of its logits --
+        behind the temperature and a head's own link -- and its labels into a device store, one uvit_op_scal_metrics call runs behind
+        the last batch, and stats gains "set_calibration" = {ECE, MCE, OE, NLL, Brier, SCE, ACE, TACE, AUROC, auroc_classes, acc,
+        mean_conf, n, n_bad, "reliability": [[prop, acc, conf], ...], "per_class": {SCE, ACE, TACE, AUROC, n_pos,
+        n_over_threshold}}: the values of the evaluation set itself, textbook bin accuracies.  OOD images take no part."""
         detection = bool(detection) or ood_loader is not None
         with self._ts_scope(temperature) as ts_value:
             self._det = {"scores": None, "flags": None, "cap": 0, "n": 0} if detection else None
             self._score_eval = [(score, {"correct": None, "slabs": []}) for score in self._scores if detection and score.state is not None]
+            self._scal_eval = {"probs": None, "labels": None, "cap": 0, "n": 0} if self._scal is not None else None
             try:
                 stats = self._evaluate(loader, calibration, ood_loader)
                 if ts_value is not None:
                     stats["temperature"] = ts_value
                 return stats
             finally:
-                self._det, self._in_ood, self._score_eval = None, False, ()
+                self._det, self._in_ood, self._score_eval, self._scal_eval = None, False, (), None
 
     def _evaluate_with_mean(self, key, want, loader, **kw):
         """LinearProbe.evaluate for a head with a per-sample column of its own (_own_column(..., self._var_slabs)): with `want`, the
@@ -378,8 +387,11 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, VimMethods, 
                 calib.append((cslab, len(calib) % 256))
             if detection:
                 self._det_rows(B, labels)
+            if self._scal_eval is not None:
+                self._scal_rows(B, labels)
             losses.append((slab, len(losses) % 256))
             sizes.append(B)
+        scal = self._scal_launch() if self._scal_eval is not None else None       # before the OOD images reuse self._logits
         if detection:
             mis, ood, n_ood = self._det_launch(sum(sizes), ood_loader)
         if not sizes:
@@ -390,6 +402,8 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, VimMethods, 
                 empty["detection"] = self._det_stats(mis, ood, 0, 0, n_ood, ood_loader is not None)
             for score, ev in self._score_eval:
                 empty.update(score.eval_stats(ev, 0))
+            if self._scal_eval is not None:
+                empty["set_calibration"] = self._scal_stats(None)
             return empty
         slabs = {id(s): s for s, _ in losses}
         host = {k: v.cpu() for k, v in slabs.items()}                       # the one read
@@ -409,6 +423,8 @@ class LinearProbe(DetectionMixin, DensityMethods, NeighbourMethods, VimMethods, 
             stats["detection"] = self._det_stats(mis, ood, n, n - c1, n_ood, ood_loader is not None)
         for score, ev in self._score_eval:                                  # read with the counters, after the last batch
             stats.update(score.eval_stats(ev, n))
+        if self._scal_eval is not None:
+            stats["set_calibration"] = self._scal_stats(scal)
         return stats
 
     # ---- optimizer state beside the head's parameters in a checkpoint ----

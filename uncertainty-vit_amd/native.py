@@ -227,6 +227,10 @@ _PROTOTYPES = {
     "uvit_op_detect_column": (_i, [_vp, _i, _i64, _vp, _i, _vp]),
     "uvit_op_detect_ws_bytes": (_i64, [_i, _i]),
     "uvit_op_detect_metrics": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "uvit_op_scal_probs": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
+    "uvit_op_scal_ws_bytes": (_i64, [_i, _i]),
+    "uvit_op_scal_launches": (_i64, [_i, _i, _i64]),
+    "uvit_op_scal_metrics": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp]),
     "uvit_op_ts_ws_bytes": (_i64, [_i, _i]),
     "uvit_op_ts_fit": (_i, [_vp, _i64, _vp, _i, _i, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _i64, _vp]),
     "uvit_op_ts_scale": (_i, [_vp, _vp, _i64, _i64, _vp, _i, _i, _vp]),
