@@ -187,12 +187,18 @@ import math
 import os
 import sys
 import time
+from dataclasses import dataclass
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from uncertainty_vit_amd import utils
+from uncertainty_vit_amd.corruptions import CORRUPTIONS, DEFAULT_CACHE_IMAGES, CleanCache, CorruptedSet
+from uncertainty_vit_amd.corruptions_ext import CORRUPTIONS_EXT
+from uncertainty_vit_amd.datasets import FOLDER_DATA_SETS, BEiTAugment, ImageFolderPretrain, PerturbationSequences, collate_packed, collate_sequences
+from uncertainty_vit_amd.engine_for_cyclical import DevicePrefetcher
+from uncertainty_vit_amd import dist_probe, ens_probe, gp_probe, het_probe, lap_probe, linear_probe, lw_probe, mcd_probe, utils
 
 
 def get_args(argv=None):
@@ -347,6 +353,16 @@ def get_args(argv=None):
     return p.parse_args(argv)
 
 
+def given(args, prefix, names):
+    """{name: args.<prefix><name>} of the names whose flag was given: the others keep the default of the library call they go to."""
+    return {n: getattr(args, prefix + n) for n in names if hasattr(args, prefix + n)}
+
+
+def append_log(output_dir, entries):
+    with open(os.path.join(output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
+        f.write(json.dumps(entries) + "\n")
+
+
 CALIB_KEYS = ("ECE", "TACE", "NLL", "AUROC")
 GP_FLAGS = ("gp_num_inducing", "gp_cov_momentum", "gp_cov_ridge_penalty", "gp_kernel_scale", "gp_mean_field")
 HET_FLAGS = ("het_num_factors", "het_temperature", "het_train_mc_samples", "het_test_mc_samples", "het_seed")
@@ -452,16 +468,12 @@ def dist_variance_line(stats):
 
 def check_mcd_flags(args):
     """The number of MC-dropout passes (--mc_dropout_forwards; 0: off).  The --mc_* flags and --attn_drop_rate belong to it, it needs a rate > 0,
-    and it samples the linear head: --gp_layer, --het_layer, --ensembles and --laplace are other heads."""
+    and it samples the linear head: the heads in front of it in HEADS are other heads (check_head)."""
     T = getattr(args, "mc_dropout_forwards", 0)
     if T < 0:
         raise ValueError(f"--mc_dropout_forwards must be >= 0, got {T}")
-    if not T:
-        if any(hasattr(args, k) for k in MCD_FLAGS + ("attn_drop_rate",)):      # the probe's forward is dropout-free without it
-            raise ValueError("--mc_* options and --attn_drop_rate belong to MC-dropout: give --mc_dropout_forwards T")
+    if not check_head(MCD, args):
         return 0
-    if any(getattr(args, k, False) for k in ("gp_layer", "het_layer", "ensembles", "laplace")):
-        raise ValueError("--mc_dropout_forwards samples the linear head: give it without --gp_layer / --het_layer / --ensembles / --laplace")
     if not getattr(args, "attn_drop_rate", 0.0) > 0.0:
         raise ValueError("--mc_dropout_forwards samples the attention dropout: give --attn_drop_rate P > 0")
     if getattr(args, "mc_dropout_layers", 0) < 0:
@@ -471,16 +483,8 @@ def check_mcd_flags(args):
 
 def check_lw_flags(args):
     """Whether the run learns layer weights (--learn_layer_weights).  --layernorm_before_combine and --use_cls belong to it; it mixes
-    the features of the linear head: --gp_layer, --het_layer, --ensembles, --laplace and --mc_dropout_forwards are other heads."""
-    if not getattr(args, "learn_layer_weights", False):
-        if getattr(args, "layernorm_before_combine", False) or getattr(args, "use_cls", False):
-            raise ValueError("--layernorm_before_combine / --use_cls belong to the layer-weighted probe: give --learn_layer_weights "
-                             "(--use_cls alone needs a trained final norm, which is not built)")
-        return False
-    if any(getattr(args, k, False) for k in ("gp_layer", "het_layer", "ensembles", "laplace", "mc_dropout_forwards")):
-        raise ValueError("--learn_layer_weights mixes the features of the linear head: give it without --gp_layer / --het_layer / "
-                         "--ensembles / --laplace / --mc_dropout_forwards")
-    return True
+    the features of the linear head: the heads in front of it in HEADS are other heads (check_head)."""
+    return check_head(LW, args)
 
 
 def layer_weights_line(weights):
@@ -539,8 +543,7 @@ def check_ts_flags(args):
 
 def temperature_line(fit):
     """The line in front of `* Acc@1`, from fit_temperature's result."""
-    from uncertainty_vit_amd.linear_probe import TS_STATUS
-    word = TS_STATUS[fit["status"]] if 0 <= fit["status"] < len(TS_STATUS) else "failed"
+    word = linear_probe.TS_STATUS[fit["status"]] if 0 <= fit["status"] < len(linear_probe.TS_STATUS) else "failed"
     return "* Temperature {T:.5f} NLL {nll_before:.5f} -> {nll_after:.5f} on {n} calibration images ({iterations} passes, {0})".format(word, **fit)
 
 
@@ -590,15 +593,11 @@ def lap_prior_precision(args):
 
 
 def check_lap_flags(args):
-    """Whether the run is a Laplace probe (--laplace).  The --lap_* flags belong to it; it is a linear head, so --gp_layer,
-    --het_layer and --ensembles are refused; an evaluation needs the data to fit on or a saved fit, and not both; a saved fit
+    """Whether the run is a Laplace probe (--laplace).  The --lap_* flags belong to it; it is a linear head, so the heads in front of
+    it in HEADS are refused (check_head); an evaluation needs the data to fit on or a saved fit, and not both; a saved fit
     belongs to a head that no longer trains."""
-    if not getattr(args, "laplace", False):
-        if any(hasattr(args, k) for k in LAP_FLAGS):
-            raise ValueError("--lap_* options belong to the Laplace probe: give --laplace")
+    if not check_head(LAP, args):
         return False
-    if getattr(args, "gp_layer", False) or getattr(args, "het_layer", False) or getattr(args, "ensembles", False):
-        raise ValueError("--laplace is a post-hoc fit of the linear head: give it without --gp_layer / --het_layer / --ensembles")
     lap_prior_precision(args)
     if hasattr(args, "lap_data_path") and hasattr(args, "lap_state"):
         raise ValueError("--lap_data_path fits the Laplace factors and --lap_state loads them: give one")
@@ -694,8 +693,7 @@ def check_vim_flags(args):
         raise ValueError("--vim_data_path fits ViM and --vim_state loads it: give one")
     if hasattr(args, "vim_dim") and args.vim_dim < 1:
         raise ValueError(f"--vim_dim must lie in [1, C - 1], got {args.vim_dim}")
-    if getattr(args, "gp_layer", False) or getattr(args, "het_layer", False) or \
-            (getattr(args, "ensembles", False) and getattr(args, "ens_combine", "logits") == "probs"):
+    if not all(head.affine(args) for head in HEADS if getattr(args, head.switch or "", False)):
         raise ValueError("--vim_* need logits that are affine in the feature: not with --gp_layer, --het_layer or --ens_combine probs")
     if hasattr(args, "vim_state"):
         if hasattr(args, "vim_dim"):
@@ -740,9 +738,7 @@ def conformal_log_entries(fit, conformal):
     """What log.txt gains: the per-alpha lists in --cp_alpha order and the number of calibration images used."""
     rows = [conformal[a] for a in fit["alpha"]]
     out = {"test_cp_alpha": list(fit["alpha"]), "test_cp_qhat": list(fit["qhat"])}
-    for key, col in (("coverage", "coverage"), ("size", "size"), ("empty", "empty"), ("singleton", "singleton"), ("sscv", "sscv"),
-                     ("worst_class", "worst_class")):
-        out[f"test_cp_{key}"] = [r[col] for r in rows]
+    out.update({f"test_cp_{key}": [r[key] for r in rows] for key in ("coverage", "size", "empty", "singleton", "sscv", "worst_class")})
     out["test_cp_n_cal"] = fit["n"]
     return out
 
@@ -775,11 +771,17 @@ def perturbation_files(args):
     return [(n, os.path.join(root, n + ".npy")) for n in names]
 
 
-def evaluate_perturbations(args, probe, device):
+def check_perturbation_flags(args):
+    """Whether the run evaluates perturbation sequences: --perturbation_path, which belongs to --eval, as --perturbations does to it."""
+    if (hasattr(args, "perturbation_path") or hasattr(args, "perturbations")) and not (args.eval and hasattr(args, "perturbation_path")):
+        raise ValueError("--perturbation_path / --perturbations belong to an evaluation: give --eval and --perturbation_path DIR")
+    return hasattr(args, "perturbation_path")
+
+
+def evaluate_perturbations(args, probe, device, logit_kw=None):
     """The reference's p_evaluate() (uncertainty_evaluations.py:614-658) over perturbation_files(args), V = max(1, batch_size // F)
-    sequences per forward; prints its lines and returns {name: evaluate_stability's result}."""
-    from uncertainty_vit_amd.datasets import BEiTAugment, PerturbationSequences, collate_sequences
-    from uncertainty_vit_amd.engine_for_cyclical import DevicePrefetcher
+    sequences per forward (`logit_kw`: the head's own keywords of its logits); prints its lines and returns {name: evaluate_stability's
+    result}."""
     aug = BEiTAugment(args.input_size, 1, "bicubic", args.imagenet_default_mean_and_std)
     print("Perturbed dataset evaluation :")
     results, flip_list = {}, []
@@ -788,8 +790,7 @@ def evaluate_perturbations(args, probe, device):
         ds = PerturbationSequences(path, aug)
         loader = torch.utils.data.DataLoader(ds, batch_size=max(1, args.batch_size // ds.frames), shuffle=False, drop_last=False,
                                              num_workers=args.num_workers, pin_memory=True, collate_fn=collate_sequences)
-        gp = {"mean_field": args.gp_mean_field} if getattr(args, "gp_layer", False) and hasattr(args, "gp_mean_field") else {}
-        r = probe.evaluate_stability(DevicePrefetcher(loader, device), ds.frames, "noise" in name, n_sequences=len(ds), **gp)
+        r = probe.evaluate_stability(DevicePrefetcher(loader, device), ds.frames, "noise" in name, n_sequences=len(ds), **(logit_kw or {}))
         results[name] = r
         flip_list.append(r["flip_prob"])
         print("\n" + name, "Flipping Prob")
@@ -799,9 +800,7 @@ def evaluate_perturbations(args, probe, device):
         if r["nan_sequences"]:
             print("%d of %d sequences hold a NaN logit and are left out" % (r["nan_sequences"], r["n_sequences"]))
         if args.output_dir:
-            with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
-                f.write(json.dumps({f"test_flip_{name}": r["flip_prob"], f"test_top5_{name}": r["top5_dist"],
-                                    f"test_zipf_{name}": r["zipf_dist"]}) + "\n")
+            append_log(args.output_dir, {f"test_flip_{name}": r["flip_prob"], f"test_top5_{name}": r["top5_dist"], f"test_zipf_{name}": r["zipf_dist"]})
     print(flip_list)
     print("\nMean Flipping Prob\t{:.5f}".format(np.mean(flip_list)))
     return results
@@ -811,9 +810,6 @@ CORRUPTION_FLAGS = ("corruptions", "corruption_severities", "corruption_seed", "
 # uncertainty_evaluations.py:846: the order of the reference's sweep over a pre-made tree
 REFERENCE_DISTORTIONS = ("gaussian_noise", "shot_noise", "impulse_noise", "defocus_blur", "glass_blur", "motion_blur", "zoom_blur", "snow",
                          "frost", "brightness", "contrast", "elastic_transform", "pixelate", "jpeg_compression", "speckle_noise")
-VAR_MEAN_LINES = (("gp_var_mean", gp_variance_line), ("het_var_mean", het_variance_line),
-                  ("lap_var_mean", lambda stats: "* Laplace variance mean {lap_var_mean:.6f}".format(**stats)),
-                  ("dist_var_mean", dist_variance_line))
 
 
 def check_corruption_flags(args):
@@ -850,8 +846,6 @@ def check_corruption_flags(args):
 def corruption_names(args):
     """--corruptions as a list of kinds in the order given (`all`: the nine of CORRUPTIONS in their order; `full`: those followed by the
     four of CORRUPTIONS_EXT); an unknown or repeated name is refused."""
-    from uncertainty_vit_amd.corruptions import CORRUPTIONS
-    from uncertainty_vit_amd.corruptions_ext import CORRUPTIONS_EXT
     names = list(args.corruptions)
     if names == ["all"]:
         return list(CORRUPTIONS)
@@ -969,9 +963,6 @@ def evaluate_corruptions(args, probe, device, clean_stats, eval_kw=None):
     folder into a CleanCache, the others replay it; a folder over --corruption_cache_images is read again per set.  With
     --corruption_path every DIR/<distortion>/<severity> is read with the evaluation pipeline.  Returns {"sets": {(name, severity):
     stats}, "summary": corruption_summary's}."""
-    from uncertainty_vit_amd.corruptions import DEFAULT_CACHE_IMAGES, CleanCache, CorruptedSet
-    from uncertainty_vit_amd.datasets import BEiTAugment
-    from uncertainty_vit_amd.engine_for_cyclical import DevicePrefetcher
     eval_kw = dict(eval_kw or {})
     eval_kw.pop("ood_loader", None)          # the sets are compared with themselves: misclassification detection only
     if hasattr(args, "corruption_path"):
@@ -999,13 +990,11 @@ def evaluate_corruptions(args, probe, device, clean_stats, eval_kw=None):
             results[(name, s)] = stats
             print("\n".join(corruption_set_lines(stats)))
             if args.output_dir:
-                with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
-                    f.write(json.dumps(corruption_log_entries(name, s, stats)) + "\n")
+                append_log(args.output_dir, corruption_log_entries(name, s, stats))
     summary = corruption_summary(results, clean_stats)
     print("\n".join(corruption_summary_lines(summary)))
     if args.output_dir:
-        with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
-            f.write(json.dumps(corruption_summary_log(summary)) + "\n")
+        append_log(args.output_dir, corruption_summary_log(summary))
     return {"sets": results, "summary": summary}
 
 
@@ -1017,7 +1006,6 @@ def encoder_kwargs(checkpoint):
 
 
 def build_loader(args, encoder, root, aug_level, train):
-    from uncertainty_vit_amd.datasets import FOLDER_DATA_SETS, BEiTAugment, ImageFolderPretrain, collate_packed
     if args.data_set not in FOLDER_DATA_SETS:
         raise NotImplementedError(f"--data_set {args.data_set} needs torchvision's archive format; use an image folder")
     aug = BEiTAugment(args.input_size, aug_level, "bicubic", args.imagenet_default_mean_and_std)
@@ -1034,106 +1022,282 @@ def save_probe(args, probe, epoch):
     return path
 
 
-def main(args):
-    from uncertainty_vit_amd.engine_for_cyclical import DevicePrefetcher
-    from uncertainty_vit_amd.linear_probe import LinearProbe, build_probe_encoder, load_encoder_checkpoint
-    print(args)
-    if not torch.cuda.is_available():
-        raise RuntimeError("the linear probe runs as HIP kernels: a GPU is required")
-    if args.nb_classes < 1:
-        raise ValueError("--nb_classes is required")
-    if not args.finetune:
-        raise ValueError("--finetune <pre-training checkpoint> is required")
-    if (hasattr(args, "perturbation_path") or hasattr(args, "perturbations")) and not (args.eval and hasattr(args, "perturbation_path")):
-        raise ValueError("--perturbation_path / --perturbations belong to an evaluation: give --eval and --perturbation_path DIR")
-    detection = check_detection_flags(args)
-    ts_mode = check_ts_flags(args)
-    conformal = check_cp_flags(args)
-    laplace = check_lap_flags(args)
-    maha = check_maha_flags(args)
-    knn = check_knn_flags(args)
-    vim = check_vim_flags(args)
-    corruption_mode = check_corruption_flags(args)
-    scal = check_scal_flags(args)
-    if corruption_mode == "path":
-        corruption_folders(args)                  # a missing folder stops the run here, not behind the main evaluation
-    detection = detection or maha is not None or knn is not None or vim is not None
-    gp_layer = getattr(args, "gp_layer", False)
-    if not gp_layer and any(hasattr(args, k) for k in GP_FLAGS):
-        raise ValueError("--gp_* options belong to the GP head: give --gp_layer")
-    het_layer = getattr(args, "het_layer", False)
-    if not het_layer and any(hasattr(args, k) for k in HET_FLAGS):
-        raise ValueError("--het_* options belong to the heteroscedastic head: give --het_layer")
-    if het_layer and gp_layer:
-        raise ValueError("--het_layer and --gp_layer are two heads: give one")
-    ensembles = getattr(args, "ensembles", False)
-    if not ensembles and any(hasattr(args, k) for k in ENS_FLAGS):
-        raise ValueError("--ens_* options belong to the ensemble: give --ensembles")
-    if ensembles and (gp_layer or het_layer):
-        raise ValueError("--ensembles is an ensemble of linear heads: give it without --gp_layer / --het_layer")
-    mcd = check_mcd_flags(args)
-    lw = check_lw_flags(args)
-    if lw and args.target_layer != -1:            # run_class_finetuning.py:520: the flag supersedes --target_layer, the encoder is not cut
-        print("--learn_layer_weights supersedes --target_layer %d: the encoder keeps every block" % args.target_layer)
-    ens_heads =getattr(args, "ens_heads", None)
-    if ens_heads is not None:
+@dataclass(frozen=True)
+class Head:
+    build: callable                               # (args, encoder) -> the probe
+    switch: str = None                            # the args attribute that selects it; None: a fallback, taken when no switch is given
+    two_stream: bool = False                      # a fallback: for which kind of encoder
+    flags: tuple = ()                             # the options that belong to it
+    orphan: str = ""                              # the refusal of an option without the switch
+    beside: str = ""                              # the refusal beside a head earlier in HEADS; {}: the switches in front of its own
+    check: callable = None                        # (args): what it validates beyond check_head
+    encoder_kw: callable = lambda args: {}        # the constructor options it asks of the encoder (asked of every head: {} where its flags are absent)
+    check_encoder: callable = None                # (args, encoder): runs for every head once the encoder is built
+    eval_kw: callable = lambda args: {}           # its own keywords of probe.evaluate
+    logit_kw: callable = lambda args: {}          # those of every call that forms logits: temperature fit, conformal sets, perturbations
+    affine: callable = lambda args: True          # whether its logits are affine in the feature
+    extend: callable = None                       # (args, probe, ctx, stats): adds to an evaluation's stats
+    lines: callable = lambda stats, dims: []      # its lines behind `* Acc@1`
+    log: callable = lambda stats: {}              # its entries of log.txt
+    var_mean: tuple = None                        # (stats key, line) of the variance mean that a corrupted set reports
+    epoch_start: callable = None                  # (probe): in front of a training epoch
+
+
+def check_head(head, args):
+    """Whether `head` is selected.  Its options are refused without its switch, and so is the head beside one that stands earlier in
+    HEADS: the later head speaks, and names every switch in front of its own."""
+    if not getattr(args, head.switch, False):
+        if any(hasattr(args, k) for k in head.flags):
+            raise ValueError(head.orphan)
+        return False
+    earlier = [h.switch for h in HEADS[:HEADS.index(head)] if h.switch]
+    if any(getattr(args, k, False) for k in earlier):
+        raise ValueError(head.beside.format(" / ".join("--" + k for k in earlier)))
+    return True
+
+
+def check_ens_heads(args):
+    """check_head, and --ens_heads: it assembles an ensemble for an evaluation, in place of --resume, and sets the member count."""
+    heads = getattr(args, "ens_heads", None)
+    if check_head(ENS, args) and heads is not None:
         if not args.eval:
             raise ValueError("--ens_heads assembles an ensemble for an evaluation: give --eval")
         if args.resume:
             raise ValueError("--ens_heads and --resume both name the heads: give one")
-        if hasattr(args, "ens_members") and args.ens_members != len(ens_heads):
-            raise ValueError(f"--ens_members {args.ens_members} but --ens_heads names {len(ens_heads)} files")
+        if hasattr(args, "ens_members") and args.ens_members != len(heads):
+            raise ValueError(f"--ens_members {args.ens_members} but --ens_heads names {len(heads)} files")
+
+
+def build_ens(args, encoder):
+    kw = dict(smoothing=args.smoothing, **given(args, "ens_", ("combine", "bagging", "seed")))
+    if not hasattr(args, "ens_heads"):
+        return ens_probe.EnsembleProbe(encoder, args.nb_classes, members=ens_member_count(args), **kw)
+    heads = [torch.load(path, map_location="cpu", weights_only=False)["model"] for path in args.ens_heads]
+    probe = ens_probe.EnsembleProbe.from_heads(encoder, heads, **kw)
+    if probe.num_classes != args.nb_classes:
+        raise ValueError(f"--ens_heads hold {probe.num_classes} classes, --nb_classes is {args.nb_classes}")
+    print("Ensemble of %d heads: %s" % (probe.members, list(args.ens_heads)))
+    return probe
+
+
+GP = Head(lambda args, enc: gp_probe.GPProbe(enc, args.nb_classes, smoothing=args.smoothing,
+                                             **given(args, "gp_", ("num_inducing", "kernel_scale", "cov_momentum", "cov_ridge_penalty"))),
+          switch="gp_layer", flags=GP_FLAGS, orphan="--gp_* options belong to the GP head: give --gp_layer",
+          eval_kw=lambda args: {"variance": True, **given(args, "gp_", ("mean_field",))}, logit_kw=lambda args: given(args, "gp_", ("mean_field",)),
+          affine=lambda args: False, lines=lambda stats, dims: [gp_variance_line(stats)], log=lambda stats: {"test_gp_var_mean": stats["gp_var_mean"]},
+          var_mean=("gp_var_mean", gp_variance_line),      # the exact sum counts the data once: it starts again with every epoch
+          epoch_start=lambda probe: probe.reset_cov() if probe.cov_momentum <= 0 else None)
+HET = Head(lambda args, enc: het_probe.HetProbe(enc, args.nb_classes, smoothing=args.smoothing,
+                                                **given(args, "het_", ("num_factors", "temperature", "train_mc_samples", "test_mc_samples", "seed"))),
+           switch="het_layer", flags=HET_FLAGS, orphan="--het_* options belong to the heteroscedastic head: give --het_layer",
+           beside="--het_layer and --gp_layer are two heads: give one", eval_kw=lambda args: {"variance": True}, affine=lambda args: False,
+           lines=lambda stats, dims: [het_variance_line(stats)], log=lambda stats: {"test_het_var_mean": stats["het_var_mean"]},
+           var_mean=("het_var_mean", het_variance_line))
+ENS = Head(build_ens, switch="ensembles", flags=ENS_FLAGS, orphan="--ens_* options belong to the ensemble: give --ensembles",
+           beside="--ensembles is an ensemble of linear heads: give it without {}", check=check_ens_heads,
+           eval_kw=lambda args: {"members": True, "uncertainty": True}, affine=lambda args: getattr(args, "ens_combine", "logits") != "probs",
+           lines=lambda stats, dims: ens_lines(stats), log=ens_log_entries)
+# its fit, and with it its lines and its part of log.txt, is the family of the same name; variance=True is an evaluation's alone
+LAP = Head(lambda args, enc: lap_probe.LaplaceProbe(enc, args.nb_classes, smoothing=args.smoothing), switch="laplace", flags=LAP_FLAGS,
+           orphan="--lap_* options belong to the Laplace probe: give --laplace", eval_kw=lambda args: {"variance": True} if args.eval else {},
+           beside="--laplace is a post-hoc fit of the linear head: give it without {}",
+           var_mean=("lap_var_mean", lambda stats: "* Laplace variance mean {lap_var_mean:.6f}".format(**stats)))
+MCD = Head(lambda args, enc: mcd_probe.MCDropoutProbe(enc, args.nb_classes, smoothing=args.smoothing, passes=args.mc_dropout_forwards,
+                                                      **given(args, "mc_dropout_", ("layers",)), **given(args, "mc_", ("combine", "seed"))),
+           switch="mc_dropout_forwards", flags=MCD_FLAGS + ("attn_drop_rate",),      # the probe's forward is dropout-free without it
+           orphan="--mc_* options and --attn_drop_rate belong to MC-dropout: give --mc_dropout_forwards T", check=check_mcd_flags,
+           beside="--mc_dropout_forwards samples the linear head: give it without {}", eval_kw=lambda args: {"uncertainty": True},
+           encoder_kw=lambda args: given(args, "", ("attn_drop_rate",)),             # check_head has refused the rate without the switch
+           lines=lambda stats, dims: mcd_lines(stats, dims.depth, dims.attn_drop_rate), log=mcd_log_entries)
+LW = Head(lambda args, enc: lw_probe.LayerWeightedProbe(enc, args.nb_classes, smoothing=args.smoothing,
+                                                        **given(args, "", ("use_cls", "layernorm_before_combine"))),
+          switch="learn_layer_weights", flags=("layernorm_before_combine", "use_cls"),
+          orphan="--layernorm_before_combine / --use_cls belong to the layer-weighted probe: give --learn_layer_weights "
+                 "(--use_cls alone needs a trained final norm, which is not built)",
+          beside="--learn_layer_weights mixes the features of the linear head: give it without {}",
+          check=lambda args: check_lw_flags(args) and args.target_layer != -1 and print(
+              "--learn_layer_weights supersedes --target_layer %d: the encoder keeps every block" % args.target_layer),      # run_class_finetuning.py:520
+          encoder_kw=lambda args: {"target_layer": -1} if getattr(args, "learn_layer_weights", False) else {},
+          extend=lambda args, probe, ctx, stats: stats.update(layer_weights=probe.layer_weights().cpu().tolist()),
+          lines=lambda stats, dims: [layer_weights_line(stats["layer_weights"])], log=lambda stats: {"test_layer_weights": stats["layer_weights"]})
+# check_dist_flags runs for every head: it refuses the --dist_* flags of a base model, and a factor > 0 beside ViM, which needs affine logits
+DIST = Head(lambda args, enc: dist_probe.DistProbe(enc, args.nb_classes, smoothing=args.smoothing, **given(args, "dist_", ("mean_field", "var_scale"))),
+            two_stream=True, check_encoder=lambda args, encoder: check_dist_flags(args, encoder._two_stream), eval_kw=lambda args: {"variance": True},
+            lines=lambda stats, dims: [dist_variance_line(stats)], var_mean=("dist_var_mean", dist_variance_line),
+            log=lambda stats: {"test_dist_var_mean": stats["dist_var_mean"], "test_dist_trace_mean": stats["dist_trace_mean"]})
+LINEAR = Head(lambda args, enc: linear_probe.LinearProbe(enc, args.nb_classes, smoothing=args.smoothing))
+HEADS = (GP, HET, ENS, LAP, MCD, LW, DIST, LINEAR)      # the order is the precedence, and who speaks when two switches are given
+VAR_MEAN_LINES = tuple(h.var_mean for h in HEADS if h.var_mean)
+
+
+@dataclass(frozen=True)
+class Family:
+    name: str
+    check: callable                               # its check_*_flags: None or False leaves the family out of the run, anything else is its mode
+    implies: tuple = ()                           # the families that a mode of this one switches on
+    prepare: callable = None                      # (args, probe, ctx) -> the fit, made or loaded in front of the evaluation; without: the mode
+    per_epoch: bool = False                       # the fit is of the head as it stands: a training run repeats it behind every epoch's steps
+    eval_kw: callable = None                      # (args, fit) -> its keywords of probe.evaluate
+    returned_as: str = None                       # the key of the fit in an --eval run's stats
+    extend: callable = None                       # (args, probe, ctx, stats): adds to an evaluation's stats
+    front: callable = None                        # (fit, stats, dims) -> its lines in front of `* Acc@1`
+    behind: callable = None                       # (fit, stats, dims) -> its lines behind it, after the head's
+    log: callable = None                          # (fit, stats) -> its entries of log.txt
+    log_leads: bool = False                       # ... in front of the head's, where the four calibration keys have always stood
+    after: callable = None                        # (args, probe, ctx, stats): follows an --eval run's report
+
+
+def fit_or_load(args, ctx, prefix, names, fit, save, file, load, what):
+    """The two sources of a saved fit, `own` being the --<prefix>_<name> given: --<prefix>_data_path DIR gives fit(loader of DIR, **own), with
+    --output_dir saved as `file` (save(fit): what goes into it); --<prefix>_state FILE gives load(what FILE holds, overridden by own)."""
+    own = given(args, prefix + "_", names)
+    if hasattr(args, prefix + "_data_path"):
+        out = fit(ctx.loader(getattr(args, prefix + "_data_path")), **own)
+        if args.output_dir:
+            torch.save(save(out), os.path.join(args.output_dir, file))
+        return out
+    if hasattr(args, prefix + "_state"):
+        out = load({**torch.load(getattr(args, prefix + "_state"), map_location="cpu", weights_only=False), **own})
+        print("Load %s %s" % (what, getattr(args, prefix + "_state")))
+        return out
+
+
+def prepare_laplace(args, probe, ctx):
+    """The fit on --lap_data_path for the head as it stands, or the one of --lap_state, under --lap_prior_precision when it is given."""
+    prior = lap_prior_precision(args)
+    source = "marglik" if prior == "marglik" else "given"
+
+    def load(saved):
+        out = {**probe.load_laplace_state(saved), "source": saved.get("source", "given"), "on_grid_edge": bool(saved.get("on_grid_edge", False))}
+        return out if prior is None else {**probe.set_prior_precision(prior), "source": source}
+
+    return fit_or_load(args, ctx, "lap", (), lambda loader: {**probe.fit_laplace(loader, prior_precision=1.0 if prior is None else prior), "source": source},
+                       lambda out: {**probe.laplace_state_dict(), "source": out["source"], "on_grid_edge": out["on_grid_edge"]}, "laplace.pth",
+                       load, "Laplace state")
+
+
+def prepare_vim(args, probe, ctx):
+    def fit(loader, **own):
+        same = hasattr(args, "maha_data_path") and os.path.realpath(args.maha_data_path) == os.path.realpath(args.vim_data_path)
+        return probe.fit_vim(loader, moments=probe.density_state_dict() if same else None, **own)      # the density's pass has read this folder
+
+    return fit_or_load(args, ctx, "vim", ("dim",), fit, lambda out: probe.vim_state_dict(), "vim.pth", probe.load_vim_state, "ViM state")
+
+
+def prepare_conformal(args, probe, ctx):
+    raps = getattr(args, "cp_score", "aps") == "raps"
+    # what the fit and evaluate_conformal share with probe.evaluate: the post-hoc temperature and the head's own keywords
+    ctx.conformal_kw = {**{k: v for k, v in ctx.eval_kw.items() if k == "temperature"}, **ctx.head.logit_kw(args)}
+    return probe.fit_conformal(ctx.loader(args.cp_data_path), **given(args, "cp_", ("alpha", "score", "randomized", "seed")),
+                               lam=getattr(args, "cp_lambda", 0.01) if raps else 0.0, kreg=getattr(args, "cp_kreg", 5) if raps else 0,
+                               **ctx.conformal_kw)
+
+
+def check_corruption_sets(args):
+    mode = check_corruption_flags(args)
+    if mode == "path":
+        corruption_folders(args)                  # a missing folder stops the run here, not behind the main evaluation
+    return mode
+
+
+# the order of the lines in front of `* Acc@1`, of those behind it, of log.txt's keys and of what follows the report
+FAMILIES = (
+    Family("calibration", lambda args: getattr(args, "calibration", False), eval_kw=lambda args, fit: {"calibration": True},
+           behind=lambda fit, stats, dims: [calibration_line(stats)], log=lambda fit, stats: {f"test_{k}": stats[k] for k in CALIB_KEYS}, log_leads=True),
+    Family("set_calibration", check_scal_flags,      # last in FIT_ORDER: the fits' passes over the calibration folders store nothing
+           prepare=lambda args, probe, ctx: probe.enable_set_calibration(**ctx.modes["set_calibration"]),
+           behind=lambda fit, stats, dims: [set_calibration_line(stats["set_calibration"])],
+           log=lambda fit, stats: set_calibration_log_entries(stats["set_calibration"]),
+           after=lambda args, probe, ctx, stats: write_reliability(args.output_dir, stats["set_calibration"]) if args.output_dir else None),
+    Family("detection", check_detection_flags, eval_kw=lambda args, fit: fit,      # the OOD images go through the evaluation's own forward
+           behind=lambda fit, stats, dims: detection_lines(stats["detection"]), log=lambda fit, stats: detection_log_entries(stats["detection"]),
+           prepare=lambda args, probe, ctx: {"detection": True, **({"ood_loader": ctx.loader(args.ood_data_path)} if hasattr(args, "ood_data_path") else {})}),
+    Family("temperature", check_ts_flags, returned_as="temperature_fit",      # --ts_temperature: no fit, and the figure is the keyword
+           prepare=lambda args, probe, ctx: probe.fit_temperature(ctx.loader(args.ts_data_path), **given(args, "ts_", ("tol", "max_iter")),
+                                                                  **ctx.head.logit_kw(args)) if hasattr(args, "ts_data_path") else None,
+           eval_kw=lambda args, fit: {"temperature": args.ts_temperature if fit is None else True},
+           front=lambda fit, stats, dims: [temperature_line(fit)] if fit else [], log=lambda fit, stats: temperature_log_entries(stats, fit)),
+    Family("laplace", check_lap_flags, prepare=prepare_laplace, per_epoch=True, returned_as="laplace_fit",
+           front=lambda fit, stats, dims: laplace_lines(fit, stats) if fit else [],
+           log=lambda fit, stats: laplace_log_entries(fit, stats) if fit else {}),
+    Family("maha", check_maha_flags, implies=("detection",), returned_as="density_fit",
+           prepare=lambda args, probe, ctx: fit_or_load(args, ctx, "maha", ("shrinkage",), probe.fit_density, lambda out: probe.density_state_dict(),
+                                                        "density.pth", probe.load_density_state, "Mahalanobis state"),
+           front=lambda fit, stats, dims: maha_lines(fit, stats), log=maha_log_entries),
+    Family("knn", check_knn_flags, implies=("detection",), returned_as="neighbour_fit",
+           prepare=lambda args, probe, ctx: fit_or_load(args, ctx, "knn", ("k", "temperature"), probe.fit_neighbours, lambda out: probe.neighbour_state_dict(),
+                                                        "neighbours.pth", probe.load_neighbour_state, "neighbour bank"),
+           front=lambda fit, stats, dims: knn_lines(fit, stats), log=knn_log_entries),
+    Family("vim", check_vim_flags, implies=("detection",), prepare=prepare_vim, returned_as="vim_fit",
+           front=lambda fit, stats, dims: vim_lines(fit, stats, dims.embed_dim), log=vim_log_entries),
+    Family("conformal", check_cp_flags, prepare=prepare_conformal, returned_as="conformal_fit",
+           extend=lambda args, probe, ctx, stats: stats.update(conformal=probe.evaluate_conformal(ctx.evaluation(), **ctx.conformal_kw)["conformal"]),
+           behind=lambda fit, stats, dims: conformal_lines(fit, stats["conformal"]), log=lambda fit, stats: conformal_log_entries(fit, stats["conformal"])),
+    Family("perturbations", check_perturbation_flags,
+           after=lambda args, probe, ctx, stats: stats.update(stability=evaluate_perturbations(args, probe, ctx.device, ctx.head.logit_kw(args)))),
+    Family("corruptions", check_corruption_sets,
+           after=lambda args, probe, ctx, stats: stats.update(corruptions=evaluate_corruptions(args, probe, ctx.device, stats, eval_kw=ctx.eval_kw))),
+)
+# the order of the fits and of the evaluate keywords: the temperature is fitted on the probit-scaled logits and reported in front of them
+FIT_ORDER = ("calibration", "detection", "laplace", "maha", "knn", "vim", "temperature", "conformal", "set_calibration")
+
+
+def validate(args):
+    """Every refusal that needs no checkpoint; {family: mode} of the families the run uses."""
+    if args.nb_classes < 1:
+        raise ValueError("--nb_classes is required")
+    if not args.finetune:
+        raise ValueError("--finetune <pre-training checkpoint> is required")
+    modes = {f.name: mode for f in FAMILIES for mode in [f.check(args)] if mode is not None and mode is not False}
+    for f in FAMILIES:
+        modes.update({name: True for name in f.implies if f.name in modes and name not in modes})
+    for head in (h for h in HEADS if h.switch):
+        head.check(args) if head.check else check_head(head, args)
+    return modes
+
+
+def run_fits(args, probe, ctx, fits, families):
+    """prepare() and the evaluate keywords of `families`, in FIT_ORDER: `fits` gains every fit, ctx.eval_kw every keyword."""
+    for f in sorted((f for f in families if f.name in FIT_ORDER), key=lambda f: FIT_ORDER.index(f.name)):
+        if f.prepare:
+            fits[f.name] = f.prepare(args, probe, ctx)
+        if f.eval_kw:
+            ctx.eval_kw.update(f.eval_kw(args, fits[f.name]))
+
+
+def report(stats, fits, head, families, dims):
+    """What an evaluation reports, from its stats, {family: fit} of the families in use, the head's record and `dims` (depth, attn_drop_rate,
+    embed_dim): the lines in front of `* Acc@1`, the lines behind it, log.txt's entries (the three figures first).  No I/O, no device."""
+    on = [(f, fits[f.name]) for f in families if f.name in fits]
+    front = [line for f, fit in on if f.front for line in f.front(fit, stats, dims)]
+    behind = head.lines(stats, dims) + [line for f, fit in on if f.behind for line in f.behind(fit, stats, dims)]
+    logs = [(f.log_leads, f.log(fit, stats)) for f, fit in on if f.log]
+    entries = {f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5")}
+    for part in [log for leads, log in logs if leads] + [head.log(stats)] + [log for leads, log in logs if not leads]:
+        entries.update(part)
+    return front, behind, entries
+
+
+def main(args):
+    print(args)
+    if not torch.cuda.is_available():
+        raise RuntimeError("the linear probe runs as HIP kernels: a GPU is required")
+    modes = validate(args)
     device = torch.device("cuda")
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
-
     ckpt = torch.load(args.finetune, map_location="cpu", weights_only=False)
     print("Load ckpt from %s" % args.finetune)
-    drop_kw = {"attn_drop_rate": args.attn_drop_rate} if hasattr(args, "attn_drop_rate") else {}
-    encoder = build_probe_encoder(args.model, -1 if lw else args.target_layer, img_size=args.input_size, **encoder_kwargs(ckpt), **drop_kw)
-    unused = load_encoder_checkpoint(encoder, ckpt, args.model_key, args.model_prefix)
+    own = {"target_layer": args.target_layer, **{k: v for h in HEADS for k, v in h.encoder_kw(args).items()}}
+    encoder = linear_probe.build_probe_encoder(args.model, img_size=args.input_size, **encoder_kwargs(ckpt), **own)
+    unused = linear_probe.load_encoder_checkpoint(encoder, ckpt, args.model_key, args.model_prefix)
     print(f"encoder: {encoder.depth} blocks, {len(unused)} checkpoint entries not part of it")
     encoder.to(device)
-    dist = check_dist_flags(args, encoder._two_stream)
-    other_head = gp_layer or het_layer or ensembles or laplace or mcd or lw      # none reads a two-stream encoder: its constructor says so
-    if gp_layer:
-        from uncertainty_vit_amd.gp_probe import GPProbe
-        probe = GPProbe(encoder, args.nb_classes, smoothing=args.smoothing, num_inducing=getattr(args, "gp_num_inducing", None),
-                        kernel_scale=getattr(args, "gp_kernel_scale", 1.0), cov_momentum=getattr(args, "gp_cov_momentum", 0.999),
-                        cov_ridge_penalty=getattr(args, "gp_cov_ridge_penalty", 1e-3))
-    elif het_layer:
-        from uncertainty_vit_amd.het_probe import HetProbe
-        probe = HetProbe(encoder, args.nb_classes, smoothing=args.smoothing, num_factors=getattr(args, "het_num_factors", 10),
-                         temperature=getattr(args, "het_temperature", 1.0), train_mc_samples=getattr(args, "het_train_mc_samples", 1000),
-                         test_mc_samples=getattr(args, "het_test_mc_samples", 1000), seed=getattr(args, "het_seed", 42))
-    elif ensembles:
-        from uncertainty_vit_amd.ens_probe import EnsembleProbe
-        ens_kw = dict(smoothing=args.smoothing, combine=getattr(args, "ens_combine", "logits"), bagging=getattr(args, "ens_bagging", False),
-                      seed=getattr(args, "ens_seed", 0))
-        if ens_heads is not None:
-            heads = [torch.load(path, map_location="cpu", weights_only=False)["model"] for path in ens_heads]
-            probe = EnsembleProbe.from_heads(encoder, heads, **ens_kw)
-            if probe.num_classes != args.nb_classes:
-                raise ValueError(f"--ens_heads hold {probe.num_classes} classes, --nb_classes is {args.nb_classes}")
-            print("Ensemble of %d heads: %s" % (probe.members, list(ens_heads)))
-        else:
-            probe = EnsembleProbe(encoder, args.nb_classes, members=ens_member_count(args), **ens_kw)
-    elif laplace:
-        from uncertainty_vit_amd.lap_probe import LaplaceProbe
-        probe = LaplaceProbe(encoder, args.nb_classes, smoothing=args.smoothing)
-    elif mcd:
-        from uncertainty_vit_amd.mcd_probe import MCDropoutProbe
-        probe = MCDropoutProbe(encoder, args.nb_classes, passes=mcd, layers=getattr(args, "mc_dropout_layers", 0),
-                               combine=getattr(args, "mc_combine", "logits"), seed=getattr(args, "mc_seed", 0), smoothing=args.smoothing)
-    elif lw:
-        from uncertainty_vit_amd.lw_probe import LayerWeightedProbe
-        probe = LayerWeightedProbe(encoder, args.nb_classes, smoothing=args.smoothing, use_cls=getattr(args, "use_cls", False),
-                                   layernorm_before_combine=getattr(args, "layernorm_before_combine", False))
-    elif dist is not None:
-        from uncertainty_vit_amd.dist_probe import DistProbe
-        probe = DistProbe(encoder, args.nb_classes, smoothing=args.smoothing, **dist)
-    else:
-        probe = LinearProbe(encoder, args.nb_classes, smoothing=args.smoothing)
+    for h in (h for h in HEADS if h.check_encoder):
+        h.check_encoder(args, encoder)
+    # the head whose switch is given; without one, the fallback for the encoder's kind
+    head = next(h for h in HEADS if (getattr(args, h.switch, False) if h.switch else h.two_stream == encoder._two_stream))
+    probe = head.build(args, encoder)
     print("Trainable weights: %s" % [n for n, p in probe.named_parameters() if p.requires_grad])
     start_epoch = 0
     if args.resume:
@@ -1142,174 +1306,33 @@ def main(args):
         probe.load_optimizer_state_dict(st["optimizer"])
         start_epoch = int(st["epoch"]) + 1
         print("Resume checkpoint %s" % args.resume)
+    loader_val, _ = build_loader(args, encoder, args.eval_data_path or args.data_path, 1, train=False)
+    ctx = SimpleNamespace(device=device, head=head, modes=modes, eval_kw=head.eval_kw(args), evaluation=lambda: DevicePrefetcher(loader_val, device),
+                          loader=lambda root: DevicePrefetcher(build_loader(args, encoder, root, 1, train=False)[0], device))
+    families, fits = [f for f in FAMILIES if f.name in modes], dict(modes)
+    run_fits(args, probe, ctx, fits, [f for f in families if args.eval or not f.per_epoch])
+    dims = SimpleNamespace(depth=encoder.depth, attn_drop_rate=encoder.attn_drop_rate, embed_dim=probe.embed_dim)
 
-    eval_root = args.eval_data_path or args.data_path
-    loader_val, _ = build_loader(args, encoder, eval_root, 1, train=False)
-    calibration = getattr(args, "calibration", False)
-    gp_eval = {"variance": True, "mean_field": getattr(args, "gp_mean_field", 0.0)} if gp_layer else {"variance": True} if het_layer else {}
-    if ensembles:
-        gp_eval = {"members": True, "uncertainty": True}
-    if mcd:
-        gp_eval = {"uncertainty": True}
-    dist = dist is not None and not other_head
-    if dist:
-        gp_eval = {"variance": True}
-    if detection:
-        gp_eval["detection"] = True
-        if hasattr(args, "ood_data_path"):
-            loader_ood, _ = build_loader(args, encoder, args.ood_data_path, 1, train=False)
-            gp_eval["ood_loader"] = DevicePrefetcher(loader_ood, device)
-    lap_fit = None
+    def evaluate():
+        stats = probe.evaluate(ctx.evaluation(), **ctx.eval_kw)
+        for record in (r for r in [head] + families if r.extend):      # a failure here loses the report of the evaluation that has just run
+            record.extend(args, probe, ctx, stats)
+        return stats
 
-    def fit_laplace():
-        """Fit on --lap_data_path for the head as it stands; with --output_dir the fit is saved as laplace.pth."""
-        prior = lap_prior_precision(args)
-        loader_lap, _ = build_loader(args, encoder, args.lap_data_path, 1, train=False)
-        fit = probe.fit_laplace(DevicePrefetcher(loader_lap, device), prior_precision=1.0 if prior is None else prior)
-        fit["source"] = "marglik" if prior == "marglik" else "given"
-        if args.output_dir:
-            torch.save({**probe.laplace_state_dict(), "source": fit["source"], "on_grid_edge": fit["on_grid_edge"]},
-                       os.path.join(args.output_dir, "laplace.pth"))
-        return fit
-
-    if laplace and args.eval:
-        if hasattr(args, "lap_state"):
-            saved = torch.load(args.lap_state, map_location="cpu", weights_only=False)
-            lap_fit = probe.load_laplace_state(saved)
-            lap_fit["source"], lap_fit["on_grid_edge"] = saved.get("source", "given"), bool(saved.get("on_grid_edge", False))
-            prior = lap_prior_precision(args)
-            if prior is not None:
-                lap_fit = probe.set_prior_precision(prior)
-                lap_fit["source"] = "marglik" if prior == "marglik" else "given"
-            print("Load Laplace state %s" % args.lap_state)
-        else:
-            lap_fit = fit_laplace()
-        gp_eval["variance"] = True
-    maha_fit = None
-    if maha == "fit":
-        loader_maha, _ = build_loader(args, encoder, args.maha_data_path, 1, train=False)
-        maha_fit = probe.fit_density(DevicePrefetcher(loader_maha, device), shrinkage=getattr(args, "maha_shrinkage", 1e-3))
-    elif maha == "state":
-        saved = torch.load(args.maha_state, map_location="cpu", weights_only=False)
-        if hasattr(args, "maha_shrinkage"):
-            saved = {**saved, "shrinkage": args.maha_shrinkage}
-        maha_fit = probe.load_density_state(saved)
-        print("Load Mahalanobis state %s" % args.maha_state)
-    if maha == "fit" and args.output_dir:
-        torch.save(probe.density_state_dict(), os.path.join(args.output_dir, "density.pth"))
-    knn_fit = None
-    if knn == "fit":
-        loader_knn, _ = build_loader(args, encoder, args.knn_data_path, 1, train=False)
-        knn_fit = probe.fit_neighbours(DevicePrefetcher(loader_knn, device), k=getattr(args, "knn_k", 20),
-                                       temperature=getattr(args, "knn_temperature", 0.07))
-        if args.output_dir:
-            torch.save(probe.neighbour_state_dict(), os.path.join(args.output_dir, "neighbours.pth"))
-    elif knn == "state":
-        saved = torch.load(args.knn_state, map_location="cpu", weights_only=False)
-        saved = {**saved, **{key: getattr(args, "knn_" + key) for key in ("k", "temperature") if hasattr(args, "knn_" + key)}}
-        knn_fit = probe.load_neighbour_state(saved)
-        print("Load neighbour bank %s" % args.knn_state)
-    vim_fit = None
-    if vim == "fit":
-        loader_vim, _ = build_loader(args, encoder, args.vim_data_path, 1, train=False)
-        same = maha == "fit" and os.path.realpath(args.maha_data_path) == os.path.realpath(args.vim_data_path)
-        vim_fit = probe.fit_vim(DevicePrefetcher(loader_vim, device), dim=getattr(args, "vim_dim", None),
-                                moments=probe.density_state_dict() if same else None)      # the density's pass has read this folder
-        if args.output_dir:
-            torch.save(probe.vim_state_dict(), os.path.join(args.output_dir, "vim.pth"))
-    elif vim == "state":
-        vim_fit = probe.load_vim_state(torch.load(args.vim_state, map_location="cpu", weights_only=False))
-        print("Load ViM state %s" % args.vim_state)
-    ts_fit = None
-    if ts_mode == "fit":
-        loader_ts, _ = build_loader(args, encoder, args.ts_data_path, 1, train=False)
-        ts_kw = {"mean_field": args.gp_mean_field} if gp_layer and hasattr(args, "gp_mean_field") else {}
-        ts_fit = probe.fit_temperature(DevicePrefetcher(loader_ts, device), tol=getattr(args, "ts_tol", 1e-7),
-                                       max_iter=getattr(args, "ts_max_iter", 16), **ts_kw)
-        gp_eval["temperature"] = True
-    elif ts_mode == "given":
-        gp_eval["temperature"] = args.ts_temperature
-    cp_fit = None
-    if conformal:
-        loader_cp, _ = build_loader(args, encoder, args.cp_data_path, 1, train=False)
-        cp_kw = {"mean_field": args.gp_mean_field} if gp_layer and hasattr(args, "gp_mean_field") else {}
-        cp_temp = {"temperature": gp_eval["temperature"]} if ts_mode else {}
-        raps = getattr(args, "cp_score", "aps") == "raps"
-        cp_fit = probe.fit_conformal(DevicePrefetcher(loader_cp, device), alpha=getattr(args, "cp_alpha", [0.1]),
-                                     score=getattr(args, "cp_score", "aps"), lam=getattr(args, "cp_lambda", 0.01) if raps else 0.0,
-                                     kreg=getattr(args, "cp_kreg", 5) if raps else 0, randomized=getattr(args, "cp_randomized", False),
-                                     seed=getattr(args, "cp_seed", 0), **cp_temp, **cp_kw)
-    if scal is not None:
-        probe.enable_set_calibration(**scal)      # behind the fits: their passes over the calibration folders store nothing
-    evaluate = lambda: probe.evaluate(DevicePrefetcher(loader_val, device), calibration=calibration, **gp_eval)      # noqa: E731
-    extra_keys = (CALIB_KEYS if calibration else ()) + (("gp_var_mean",) if gp_layer else ()) + (("het_var_mean",) if het_layer else ()) + \
-        (("dist_var_mean", "dist_trace_mean") if dist else ())
     if args.eval:
         stats = evaluate()
-        if ts_fit is not None:
-            stats["temperature_fit"] = ts_fit
-            print(temperature_line(ts_fit))
-        if lap_fit is not None:
-            stats["laplace_fit"] = lap_fit
-            print("\n".join(laplace_lines(lap_fit, stats)))
-        if maha_fit is not None:
-            stats["density_fit"] = maha_fit
-            print("\n".join(maha_lines(maha_fit, stats)))
-        if knn_fit is not None:
-            stats["neighbour_fit"] = knn_fit
-            print("\n".join(knn_lines(knn_fit, stats)))
-        if vim_fit is not None:
-            stats["vim_fit"] = vim_fit
-            print("\n".join(vim_lines(vim_fit, stats, probe.embed_dim)))
-        print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images")
-        if gp_layer:
-            print(gp_variance_line(stats))
-        if het_layer:
-            print(het_variance_line(stats))
-        if dist:
-            print(dist_variance_line(stats))
-        if ensembles:
-            print("\n".join(ens_lines(stats)))
-        if mcd:
-            print("\n".join(mcd_lines(stats, encoder.depth, encoder.attn_drop_rate)))
-        if lw:
-            stats["layer_weights"] = probe.layer_weights().cpu().tolist()
-            print(layer_weights_line(stats["layer_weights"]))
-        if calibration:
-            print(calibration_line(stats))
-        if scal is not None:
-            print(set_calibration_line(stats["set_calibration"]))
-            if args.output_dir:
-                write_reliability(args.output_dir, stats["set_calibration"])
-        if detection:
-            print("\n".join(detection_lines(stats["detection"])))
-        if conformal:
-            stats["conformal_fit"] = cp_fit
-            stats["conformal"] = probe.evaluate_conformal(DevicePrefetcher(loader_val, device), **cp_temp, **cp_kw)["conformal"]
-            print("\n".join(conformal_lines(cp_fit, stats["conformal"])))
-        if (extra_keys or ensembles or mcd or lw or detection or ts_mode or conformal or laplace or scal is not None) and args.output_dir:
-            with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
-                f.write(json.dumps({**{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
-                                    **(ens_log_entries(stats) if ensembles else {}),
-                                    **(mcd_log_entries(stats) if mcd else {}),
-                                    **({"test_layer_weights": stats["layer_weights"]} if lw else {}),
-                                    **(set_calibration_log_entries(stats["set_calibration"]) if scal is not None else {}),
-                                    **(detection_log_entries(stats["detection"]) if detection else {}),
-                                    **(temperature_log_entries(stats, ts_fit) if ts_mode else {}),
-                                    **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {}),
-                                    **(maha_log_entries(maha_fit, stats) if maha_fit is not None else {}),
-                                    **(knn_log_entries(knn_fit, stats) if knn_fit is not None else {}),
-                                    **(vim_log_entries(vim_fit, stats) if vim_fit is not None else {}),
-                                    **(conformal_log_entries(cp_fit, stats["conformal"]) if conformal else {})}) + "\n")
-        if hasattr(args, "perturbation_path"):
-            stats["stability"] = evaluate_perturbations(args, probe, device)
-        if corruption_mode:
-            stats["corruptions"] = evaluate_corruptions(args, probe, device, stats, eval_kw={"calibration": calibration, **gp_eval})
+        stats.update({f.returned_as: fits[f.name] for f in families if f.returned_as and fits[f.name] is not None})
+        front, behind, entries = report(stats, fits, head, families, dims)
+        print("\n".join(front + [f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f} on {stats['n']} test images"] + behind))
+        if len(entries) > 3 and args.output_dir:          # --eval alone writes no line
+            append_log(args.output_dir, entries)
+        for f in (f for f in families if f.after):
+            f.after(args, probe, ctx, stats)
         return stats
     loader_train, _ = build_loader(args, encoder, args.data_path, 3, train=True)
-    steps_per_epoch = len(loader_train)
     print("LR = %.8f" % args.lr)
     print("Batch size = %d" % args.batch_size)
+    steps_per_epoch = len(loader_train)
     print("Number of training steps per epoch = %d" % steps_per_epoch)
     lr_values = utils.cosine_scheduler(args.lr, args.min_lr, args.epochs, steps_per_epoch, warmup_epochs=args.warmup_epochs)
 
@@ -1324,10 +1347,9 @@ def main(args):
 
     stats, t0 = None, time.time()
     for epoch in range(start_epoch, args.epochs):
-        log = utils.MetricLogger(delimiter="  ")
-        seen = []
-        if gp_layer and probe.cov_momentum <= 0:
-            probe.reset_cov()                     # the exact sum counts the data once: it starts again with every epoch
+        log, seen = utils.MetricLogger(delimiter="  "), []
+        if head.epoch_start:
+            head.epoch_start(probe)
         for i, ((images, _), labels) in enumerate(log.log_every(DevicePrefetcher(loader_train, device), 10, f"Epoch: [{epoch}]")):
             lr = float(lr_values[epoch * steps_per_epoch + i])
             loss, gnorm = probe.train_step(images, labels.to(device, non_blocking=True), lr, args.weight_decay, args.clip_grad)
@@ -1337,41 +1359,14 @@ def main(args):
             log.update(lr=lr)
         for l0, g0 in seen:
             publish(log, l0, g0)
-        if laplace and hasattr(args, "lap_data_path"):
-            lap_fit = fit_laplace()              # the fit of this epoch's head: train_step dropped the one before
+        run_fits(args, probe, ctx, fits, [f for f in families if f.per_epoch])      # of this epoch's head: train_step dropped the one before
         stats = evaluate()
-        if lap_fit is not None:
-            print("\n".join(laplace_lines(lap_fit, stats)))
-        print(f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f}")
-        if gp_layer:
-            print(gp_variance_line(stats))
-        if het_layer:
-            print(het_variance_line(stats))
-        if dist:
-            print(dist_variance_line(stats))
-        if ensembles:
-            print("\n".join(ens_lines(stats)))
-        if mcd:
-            print("\n".join(mcd_lines(stats, encoder.depth, encoder.attn_drop_rate)))
-        if lw:
-            stats["layer_weights"] = probe.layer_weights().cpu().tolist()
-            print(layer_weights_line(stats["layer_weights"]))
-        if calibration:
-            print(calibration_line(stats))
-        if scal is not None:
-            print(set_calibration_line(stats["set_calibration"]))
+        front, behind, entries = report(stats, fits, head, families, dims)
+        print("\n".join(front + [f"* Acc@1 {stats['acc1']:.3f} Acc@5 {stats['acc5']:.3f} loss {stats['loss']:.3f}"] + behind))
         print(f"Epoch {epoch}: loss: {log.loss.global_avg:.4f}  lr: {log.lr.value:.8f}  acc1: {stats['acc1']:.3f}  acc5: {stats['acc5']:.3f}")
         if args.output_dir:
             save_probe(args, probe, epoch)
-            with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
-                f.write(json.dumps({"epoch": epoch, "train_loss": log.loss.global_avg, "train_lr": log.lr.value,
-                                    **{f"test_{k}": stats[k] for k in ("loss", "acc1", "acc5") + extra_keys},
-                                    **(ens_log_entries(stats) if ensembles else {}),
-                                    **(mcd_log_entries(stats) if mcd else {}),
-                                    **({"test_layer_weights": stats["layer_weights"]} if lw else {}),
-                                    **(set_calibration_log_entries(stats["set_calibration"]) if scal is not None else {}),
-                                    **(laplace_log_entries(lap_fit, stats) if lap_fit is not None else {})})
-                        + "\n")
+            append_log(args.output_dir, {"epoch": epoch, "train_loss": log.loss.global_avg, "train_lr": log.lr.value, **entries})
     print("Training time %.0f s" % (time.time() - t0))
     return stats
 

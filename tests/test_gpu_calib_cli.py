@@ -1,40 +1,16 @@
-"""GPU, end to end: run_linear_probe.main --eval --calibration on the small image folder of tests/test_gpu_probe_cli.py (its helpers
-are copied here): beit_base_patch16_224 cut after block 0, a checkpoint of two blocks, 6 validation images in 3 classes."""
+"""GPU, end to end: run_linear_probe.main --eval --calibration on the small image folder of tests/test_gpu_probe_cli.py (with its
+helpers): beit_base_patch16_224 cut after block 0, a checkpoint of two blocks, 6 validation images in 3 classes."""
 import json
-import os
 import re
-from functools import partial
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
-import torch
+
+from test_gpu_probe_cli import _image_tree, _pretraining_checkpoint
 
 pytestmark = pytest.mark.gpu
 
 CALIB_LINE = re.compile(r"^\* ECE (\S+) TACE (\S+) NLL (\S+) AUROC (\S+)$", re.M)
-
-
-def _image_tree(root, n):
-    from PIL import Image
-    rng = np.random.default_rng(17)
-    sizes = [(240, 320), (300, 200), (224, 224), (180, 260)]
-    for k in range(n):
-        h, w = sizes[k % len(sizes)]
-        p = os.path.join(root, f"class{k % 3}", f"img{k}.{'png' if k % 2 else 'jpg'}")
-        os.makedirs(os.path.dirname(p), exist_ok=True)
-        Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).save(p)
-
-
-def _pretraining_checkpoint(path):
-    """What run_cyclical.py leaves behind (utils.save_model: `model`, `args`, ...), of a two-block ViT-B/16."""
-    from uncertainty_vit_amd.modeling_cyclical import VisionTransformerForCyclicalTraining
-    torch.manual_seed(5)
-    m = VisionTransformerForCyclicalTraining(img_size=224, patch_size=16, embed_dim=768, depth=2, num_heads=12, mlp_ratio=4, qkv_bias=True,
-                                             norm_layer=partial(torch.nn.LayerNorm, eps=1e-6), init_values=0.1,
-                                             use_shared_rel_pos_bias=True, use_abs_pos_emb=False)
-    args = SimpleNamespace(rel_pos_bias=True, abs_pos_emb=False, layer_scale_init_value=0.1)
-    torch.save({"model": m.state_dict(), "optimizer": {}, "epoch": 0, "scaler": {}, "args": args}, path)
 
 
 def test_cli_eval_with_and_without_calibration(tmp_path, capsys):
