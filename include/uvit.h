@@ -1101,6 +1101,65 @@ int uvit_op_corrupt_ext_batch(const uint8_t* in_u8, float* out, int B, int S, in
                               uint32_t seed, int64_t index0, const float* mean, const float* std, void* ws, int64_t ws_bytes,
                               uvit_stream stream);
 
+/* ---- probe training: random erasing, mixup and cutmix of a batch, and the soft-target loss (csrc/mixup.hip) ----
+ * timm's RandomErasing (per-sample transform) followed by timm's Mixup (behind the collate), run_class_finetuning.py:128-149, on the
+ * normalised fp32 images x (B, 3, S, S) that uvit_op_augment_batch wrote, into out (B, 3, S, S), one launch.  1 <= B <= 65535,
+ * 1 <= S <= 4096, 0 <= R <= 8 erase boxes per row.  IEEE fp32 evaluated as written, no contraction, no atomics; the same input gives
+ * the same bits on every run.
+ * desc[b] (HOST, B entries): kind, lam in [0, 1], partner in [0, B), the cutmix box rows [yl, yh) and columns [xl, xh) with
+ * 0 <= yl <= yh <= S and 0 <= xl <= xh <= S (read for every kind, used by CUTMIX).  boxes (HOST, (B, R); NULL when R == 0): the erase
+ * boxes of row b, rows [top, top + h), columns [left, left + w) inside the image; h == 0: none.  Both are validated here and copied
+ * into the workspace by asynchronous copies on `stream`: keep them unchanged until the stream has passed this call (pinned memory,
+ * like any hipMemcpyAsync source).  workspace: uvit_op_mix_ws_bytes(B, R) bytes (< 0: UVIT_ERR_SHAPE).
+ * e(j, c, y, x), sample j behind its erasing: x[j, c, y, x] outside every box of j; inside one, the fill of the LAST box that holds
+ * the pixel (a later box overwrites an earlier one):
+ *   erase_mode CONST   0.0f
+ *              RAND    n(j, q) with q = 3 r + c             one standard normal per (sample, box r, channel)
+ *              PIXEL   n(j, q) with q = (c S + y) S + x     one per (sample, channel, pixel); does not depend on the box
+ * n(j, q), with h = uvit_hash32: kit = h(seed ^ (iteration 0x9E3779B9 + 0x7F4A7C15)), kj = h(kit ^ (j + 1) 0x85EBCA6B),
+ *   k1 = h(kj ^ 0x1B873593), k2 = h(kj ^ 0xCC9E2D51), h1 = h(q ^ k1), h2 = h(q ^ k2), u_i = ((h_i >> 9) + 0.5) 2^-23 (exact in fp32,
+ *   inside (0, 1)), n = sqrtf(-2.0f logf(u1)) cosf(6.2831854820251465f u2), every product in fp32 (all words mod 2^32).  The key holds
+ *   the seed, the iteration and the sample's index j alone: an erased pixel of sample j has the same value as itself and as anybody's
+ *   partner, for every B and every launch shape.
+ * out[b], with p = desc[b].partner and lam = desc[b].lam:
+ *   NONE     e(b)
+ *   MIXUP    fl(fl(lam e(b)) + fl(fl(1.0f - lam) e(p)))
+ *   CUTMIX   e(p) inside the cutmix box, e(b) outside
+ * A row whose partner is itself is legal.  A NONE row does not read its partner, a CUTMIX row reads it inside the box only (16-byte
+ * accesses when S % 4 == 0 and both pointers are 16-byte aligned; any S >= 1 is correct).
+ * Errors (nothing launched, out untouched): UVIT_ERR_ARG for a NULL pointer (boxes with R > 0 included), an unknown kind or
+ * erase_mode, a lam outside [0, 1] (NaN included), a partner outside [0, B), and for out overlapping x anywhere (rows read their
+ * partners); UVIT_ERR_SHAPE for B, S or R outside their limits, a cutmix box or an erase box outside the image, h < 0 or h > 0 with
+ * w < 1; UVIT_ERR_WORKSPACE. */
+#define UVIT_MIX_NONE 0
+#define UVIT_MIX_MIXUP 1
+#define UVIT_MIX_CUTMIX 2
+#define UVIT_MIX_ERASE_CONST 0
+#define UVIT_MIX_ERASE_RAND 1
+#define UVIT_MIX_ERASE_PIXEL 2
+#define UVIT_MIX_MAX_BOXES 8
+typedef struct uvit_mix_desc {
+    int32_t kind;                              /* UVIT_MIX_{NONE, MIXUP, CUTMIX} */
+    float lam;
+    int32_t partner;
+    int32_t yl, yh, xl, xh;                    /* the cutmix box */
+    int32_t reserved;                          /* 0 */
+} uvit_mix_desc;
+typedef struct uvit_mix_box { int32_t top, left, h, w; } uvit_mix_box;
+int64_t uvit_op_mix_ws_bytes(int B, int R);
+int uvit_op_mix_batch(const float* x, float* out, const uvit_mix_desc* desc, const uvit_mix_box* boxes, int B, int S, int R,
+                      int erase_mode, uint32_t seed, uint32_t iteration, void* workspace, int64_t ws_bytes, uvit_stream stream);
+/* timm SoftTargetCrossEntropy on Mixup's two-label target (engine_for_finetuning.py:617-619) without a (B, K) target tensor, one wave
+ * per row: with p = partner[b] (int32[B], device), lam_b = lam[b] (float[B], device), s = smoothing and
+ *   t = lam_b oh(y_b) + (1 - lam_b) oh(y_p),  oh(y)_k = s / K + (1 - s) [k == y]      (mixup_target: off = s / K, on = 1 - s + off)
+ *   row_loss[b] = -sum_k t_k log softmax(z)_k = lam_b L(y_b) + (1 - lam_b) L(y_p),  L(y) = uvit_op_probe_ce's row formula;
+ *   *loss_out = mean_b row_loss[b], summed by one wave in row order;  dlogits (nullable) = (softmax - t) / B.
+ * No accuracy counters: the reference reports no training accuracy under mixup.  A label, own or partner's, outside [0, K), a partner
+ * outside [0, B) or a lam outside [0, 1] makes row_loss[b], the row of dlogits and *loss_out NaN; nothing is read at the bad index.
+ * UVIT_ERR_ARG for a NULL required pointer or a smoothing outside [0, 1); UVIT_ERR_SHAPE for B < 1 or K < 1 (K = 1 is legal). */
+int uvit_op_probe_ce_mix(const float* logits, const int64_t* labels, const int32_t* partner, const float* lam, float smoothing,
+                         float* dlogits, float* row_loss, float* loss_out, int B, int K, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

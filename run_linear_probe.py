@@ -180,6 +180,13 @@ evaluation prints `* Dist variance mean <v> trace mean <t>` after `* Acc@1`, log
 `test_dist_trace_mean`, and `--detection` gains the columns `dist_var` and `dist_trace`.  --calibration, --ts_*, --cp_*, --maha_*,
 --knn_*, --perturbation_path, --corruptions and --target_layer work as with a base model, --vim_* at FACTOR = 0; the other heads
 (--gp_layer, --het_layer, --ensembles, --laplace, --mc_dropout_forwards, --learn_layer_weights) refuse a two-stream encoder.
+
+`--mixup A`, `--cutmix A`, `--cutmix_minmax LO HI`, `--mixup_prob`, `--mixup_switch_prob`, `--mixup_mode batch|pair|elem`, `--reprob P`,
+`--remode const|rand|pixel`, `--recount N` (the reference's flags; absent = off, the reference's default --reprob 0.25 is not adopted)
+erase and mix every training batch on the device in front of the encoder (uncertainty-vit_amd/probe_mix.py, csrc/mixup.hip, DESIGN.md
+section 9.20) and train on the soft-target cross-entropy of the two labels of every row; the run prints `Mixup is activated!` and
+log.txt's `train_loss` is that loss.  `--mix_seed` (default: --seed) seeds the draws, which depend on (seed, step) alone.  Every head
+but --ensembles takes them; --eval refuses them.  Evaluation is untouched.
 """
 import argparse
 import json
@@ -198,7 +205,7 @@ from uncertainty_vit_amd.corruptions import CORRUPTIONS, DEFAULT_CACHE_IMAGES, C
 from uncertainty_vit_amd.corruptions_ext import CORRUPTIONS_EXT
 from uncertainty_vit_amd.datasets import FOLDER_DATA_SETS, BEiTAugment, ImageFolderPretrain, PerturbationSequences, collate_packed, collate_sequences
 from uncertainty_vit_amd.engine_for_cyclical import DevicePrefetcher
-from uncertainty_vit_amd import dist_probe, ens_probe, gp_probe, het_probe, lap_probe, linear_probe, lw_probe, mcd_probe, utils
+from uncertainty_vit_amd import dist_probe, ens_probe, gp_probe, het_probe, lap_probe, linear_probe, lw_probe, mcd_probe, probe_mix, utils
 
 
 def get_args(argv=None):
@@ -350,6 +357,19 @@ def get_args(argv=None):
     a("--corruption_path", type=str, default=argparse.SUPPRESS, metavar="DIR",
       help="with --eval: a pre-made corrupted data set DIR/<distortion>/<severity>/<class>/... (the reference's layout), every folder read "
            "with the evaluation pipeline; exclusive with --corruptions")
+    # the reference's mixup / cutmix / random-erasing flags (run_class_finetuning.py:128-149); absent = off: its own default
+    # --reprob 0.25 is NOT adopted, a run without these flags trains as it always has
+    a("--reprob", type=float, default=argparse.SUPPRESS, metavar="PCT", help="random erase probability per training sample (default 0: off)")
+    a("--remode", type=str, default=argparse.SUPPRESS, help="random erase fill: const, rand or pixel (default pixel)")
+    a("--recount", type=int, default=argparse.SUPPRESS, help="random erase boxes per erased sample, 1 .. 8 (default 1)")
+    a("--mixup", type=float, default=argparse.SUPPRESS, help="mixup alpha, enabled if > 0 (default 0)")
+    a("--cutmix", type=float, default=argparse.SUPPRESS, help="cutmix alpha, enabled if > 0 (default 0)")
+    a("--cutmix_minmax", type=float, nargs="+", default=argparse.SUPPRESS,
+      help="cutmix min / max side ratio, two values in (0, 1] ascending; overrides the alpha and enables cutmix")
+    a("--mixup_prob", type=float, default=argparse.SUPPRESS, help="probability of mixing a batch (or a row) when either is enabled (default 1.0)")
+    a("--mixup_switch_prob", type=float, default=argparse.SUPPRESS, help="probability of cutmix when both are enabled (default 0.5)")
+    a("--mixup_mode", type=str, default=argparse.SUPPRESS, help="how the parameters are drawn: batch, pair or elem (default batch)")
+    a("--mix_seed", type=int, default=argparse.SUPPRESS, help="seed of the mixing and erasing draws (default: --seed)")
     return p.parse_args(argv)
 
 
@@ -379,6 +399,25 @@ def calibration_line(stats):
 SCAL_FLAGS = ("scal_ece_bins", "scal_cw_bins", "scal_ace_bins", "scal_tace_bins", "scal_tace_threshold")
 SCAL_LINE_KEYS = ("ECE", "MCE", "OE", "NLL", "Brier", "SCE", "ACE", "TACE", "AUROC")
 SCAL_SUMMARY_KEYS = ("ECE", "NLL", "Brier")
+
+
+MIX_FLAGS = {"mixup": "mixup_alpha", "cutmix": "cutmix_alpha", "cutmix_minmax": "cutmix_minmax", "mixup_prob": "prob",
+             "mixup_switch_prob": "switch_prob", "mixup_mode": "mode", "reprob": "reprob", "remode": "remode", "recount": "recount"}
+
+
+def build_mixer(args):
+    """The probe_mix.BatchMixer of the mixup / cutmix / random-erasing flags, or None when none of them switches anything on.  Refused
+    (ValueError): a value outside its range (BatchMixer's own checks), and an active mixer beside --eval or --ensembles."""
+    kw = {name: getattr(args, flag) for flag, name in MIX_FLAGS.items() if hasattr(args, flag)}
+    mixer = probe_mix.BatchMixer(seed=getattr(args, "mix_seed", args.seed), **kw)
+    if not mixer.enabled:
+        return None
+    if args.eval:
+        raise ValueError("--mixup / --cutmix / --cutmix_minmax / --reprob change the training batches: give them without --eval")
+    if getattr(args, "ensembles", False):
+        raise ValueError("--mixup / --cutmix / --cutmix_minmax / --reprob are not built under --ensembles: its loss is the members' "
+                         "bagged cross-entropy (uvit_op_ens_ce)")
+    return mixer
 
 
 def check_scal_flags(args):
@@ -1253,6 +1292,7 @@ def validate(args):
         modes.update({name: True for name in f.implies if f.name in modes and name not in modes})
     for head in (h for h in HEADS if h.switch):
         head.check(args) if head.check else check_head(head, args)
+    build_mixer(args)
     return modes
 
 
@@ -1299,6 +1339,10 @@ def main(args):
     head = next(h for h in HEADS if (getattr(args, h.switch, False) if h.switch else h.two_stream == encoder._two_stream))
     probe = head.build(args, encoder)
     print("Trainable weights: %s" % [n for n, p in probe.named_parameters() if p.requires_grad])
+    mixer = build_mixer(args)
+    if mixer is not None:
+        print("Mixup is activated!")                  # run_class_finetuning.py:567; train_loss is the soft-target loss from here on
+        probe.enable_mix(mixer)
     start_epoch = 0
     if args.resume:
         st = torch.load(args.resume, map_location="cpu", weights_only=False)

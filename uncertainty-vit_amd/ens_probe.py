@@ -159,6 +159,11 @@ class EnsembleProbe(LinearProbe):
         """The bagging seed of training step `step` (0-based): fresh weights for every presentation of a sample."""
         return _hash32(self.seed ^ ((step * 0x85EBCA6B + 1) & 0xFFFFFFFF))
 
+    def enable_mix(self, mixer):
+        """Not built: the ensemble's loss is uvit_op_ens_ce with its bagging weights, and no soft-target form of it exists."""
+        if mixer is not None:
+            raise NotImplementedError("mixup / cutmix / random erasing under the ensemble is not built: its loss is uvit_op_ens_ce")
+
     def train_step(self, images, labels, lr, weight_decay, max_norm=None):
         """One step on the M heads, as LinearProbe.train_step: one logits call, the members' cross-entropies (weighted by the bagging
         weights of step_seed(step_count) when bagging), one head-gradient call, the per-member clip (max_norm) and one AdamW over

@@ -179,14 +179,13 @@ class GPProbe(LinearProbe):
         """One step on gamma, beta and W_out, as LinearProbe.train_step; the precision matrix takes this batch's phi (training steps
         only: the reference also updates it on every evaluation forward through a default argument, a side effect that is not
         reproduced).  Returns (loss, grad_norm) as device scalars."""
-        B = self._features(images)
+        B = self._features(self._train_images(images))
         labels = self._labels(labels, B)
         K, Cd, D, L, s = self.num_classes, self.embed_dim, self.num_inducing, lib(), cur_stream()
         self._logits_into(B, keep=True)
         check(L.uvit_op_gp_precision_update(ptr(self._phi), ptr(self._P), B, D, C.c_double(self.cov_momentum), s), "uvit_op_gp_precision_update")
         self._cov_tick += 1
-        check(L.uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(self.smoothing), ptr(self._dlogits), ptr(self._row_loss),
-                                 ptr(self._stats), None, B, K, s), "uvit_op_probe_ce")
+        self._criterion(labels, B)
         g = self._grad_arena.data_ptr()
         check(L.uvit_op_probe_head_grad(ptr(self._dlogits), ptr(self._phi), C.c_void_p(g), ptr(self._dbias), B, K, D, s),
               "uvit_op_probe_head_grad")

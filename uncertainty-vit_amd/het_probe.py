@@ -138,13 +138,12 @@ class HetProbe(LinearProbe):
     def train_step(self, images, labels, lr, weight_decay, max_norm=None):
         """One step on the three layers, as LinearProbe.train_step: per-row draws (share = 0) under step_seed(step_count), the
         smoothed cross-entropy on z, the Monte-Carlo backward, one head-gradient call.  Returns (loss, grad_norm) as device scalars."""
-        B = self._features(images)
+        B = self._features(self._train_images(images))
         labels = self._labels(labels, B)
         K, Cd, R, L, s = self.num_classes, self.embed_dim, self.num_factors, lib(), cur_stream()
         seed = self.step_seed(self.step_count)
         self._mc_into(B, self.train_mc_samples, seed, 0)
-        check(L.uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(self.smoothing), ptr(self._dlogits), ptr(self._row_loss),
-                                 ptr(self._stats), None, B, K, s), "uvit_op_probe_ce")
+        self._criterion(labels, B)
         check(L.uvit_op_het_mc_backward(ptr(self._lin), ptr(self._p), ptr(self._dlogits), ptr(self._dlin), ptr(self._het_scratch), B,
                                         self.train_mc_samples, K, R, f32(self.temperature), f32(EPS), seed, 0, s), "uvit_op_het_mc_backward")
         check(L.uvit_op_probe_head_grad(ptr(self._dlin), ptr(self._feat), ptr(self._grad_arena), self._bias_ptr(self._grad_arena), B, self._rows,

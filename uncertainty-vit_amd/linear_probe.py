@@ -55,6 +55,8 @@ class LinearProbe(DetectionMixin, SetCalibrationMixin, DensityMethods, Neighbour
     # logits; a head with an uncertainty of its own appends its columns
     DETECT_COLUMNS = ("msp", "entropy", "energy")
     TWO_STREAM = False                       # the encoder family the class reads: True in DistProbe (dist_probe.py) alone
+    # training-time mixing (enable_mix): the mixer, and (partner, lam) on the device while the running train_step's batch is mixed
+    _mixer, _mix, _mix_bufs = None, None, None
 
     def __init__(self, encoder, num_classes, smoothing=0.1, init_scale=0.001):
         super().__init__()
@@ -231,18 +233,89 @@ class LinearProbe(DetectionMixin, SetCalibrationMixin, DensityMethods, Neighbour
         return labels
 
     # ---- training ----
+    def enable_mix(self, mixer):
+        """Random erasing, mixup and cutmix of every training batch (probe_mix.BatchMixer; None switches it off): train_step draws
+        with iteration = step_count, runs uvit_op_mix_batch into a buffer of the probe's in front of the encoder and takes
+        uvit_op_probe_ce_mix for its loss.  A step whose draw is not active makes the calls of a probe without a mixer and gives
+        its bits.  Evaluation is untouched."""
+        if mixer is not None and not callable(getattr(mixer, "draw", None)):
+            raise TypeError("enable_mix takes a probe_mix.BatchMixer or None")
+        self._mixer, self._mix = mixer, None
+
+    def mix_images(self, images, draw):
+        """uvit_op_mix_batch on `images` (B, 3, S, S) fp32 on the GPU under a probe_mix.MixDraw, seeded with the mixer's seed and
+        iteration = step_count: the mixed batch, a buffer of the probe's that the next call overwrites.  Leaves (partner, lam) of the
+        draw on the device for the criterion of the running step."""
+        self._check_images(images)
+        if images.dtype != torch.float32 or images.ndim != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3] or \
+                not images.is_contiguous():
+            raise native.UvitError("mixing needs contiguous float32 images of shape (B, 3, S, S)")
+        B, S, R = images.shape[0], images.shape[2], draw.boxes.shape[1]
+        L, dev = lib(), images.device
+        need = L.uvit_op_mix_ws_bytes(B, R)
+        if need < 0:
+            check(need, "uvit_op_mix_ws_bytes")
+        bufs = self._mix_bufs
+        if bufs is None or bufs["out"].shape != images.shape or bufs["out"].device != dev or bufs["ws"].numel() < need:
+            # the host arrays are read by asynchronous copies: four pinned slots, each guarded by the event of the step that used it
+            bufs = self._mix_bufs = {"out": torch.empty_like(images), "ws": torch.empty(need, dtype=torch.uint8, device=dev),
+                                     "labels": torch.empty(8 * B, dtype=torch.uint8, device=dev), "slots": [], "at": 0}
+        if len(bufs["slots"]) < 4:
+            bufs["slots"].append({"event": torch.cuda.Event(), "host": None})
+        slot = bufs["slots"][bufs["at"] % len(bufs["slots"])]
+        bufs["at"] += 1
+        slot["event"].synchronize()                  # returns at once unless the stream is four steps behind
+        # [descriptors | erase boxes | partner int32[B] | lam float32[B]]: the first two are the op's host arguments, the last two
+        # the device arguments of uvit_op_probe_ce_mix
+        parts = [np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in (draw.desc, draw.boxes, draw.partner, draw.lam)]
+        pack = np.concatenate(parts)
+        if slot["host"] is None or slot["host"].numel() < pack.size:
+            slot["host"] = torch.empty(pack.size, dtype=torch.uint8).pin_memory()
+        slot["host"].numpy()[:pack.size] = pack
+        host, off = slot["host"].data_ptr(), parts[0].size + parts[1].size
+        seed = int(getattr(self._mixer, "seed", 0)) & 0xFFFFFFFF
+        check(L.uvit_op_mix_batch(ptr(images), ptr(bufs["out"]), C.c_void_p(host), C.c_void_p(host + parts[0].size) if R else None, B, S, R,
+                                  int(draw.erase_mode), seed, self.step_count & 0xFFFFFFFF, ptr(bufs["ws"]), bufs["ws"].numel(), cur_stream()),
+              "uvit_op_mix_batch")
+        bufs["labels"].copy_(slot["host"][off:off + 8 * B], non_blocking=True)
+        slot["event"].record()
+        self._mix = (bufs["labels"][:4 * B].view(torch.int32), bufs["labels"][4 * B:].view(torch.float32))
+        return bufs["out"]
+
+    def _train_images(self, images):
+        """The batch a train_step feeds the encoder: `images`, or, with a mixer whose draw of this step is active, their mix."""
+        self._mix = None
+        if self._mixer is None:
+            return images
+        self._check_images(images)
+        draw = self._mixer.draw(images.shape[0], images.shape[-1], self.step_count)
+        return self.mix_images(images, draw) if draw.active else images
+
+    def _criterion(self, labels, B):
+        """The training loss of self._logits[:B] into self._dlogits, self._row_loss and self._stats[0]: the smoothed cross-entropy,
+        or, while the step's batch is mixed, the soft-target one of the two labels of every row."""
+        L, K, s = lib(), self.num_classes, cur_stream()
+        if self._mix is None:
+            check(L.uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(self.smoothing), ptr(self._dlogits), ptr(self._row_loss),
+                                     ptr(self._stats), None, B, K, s), "uvit_op_probe_ce")
+            return
+        partner, lam = self._mix
+        self._mix = None
+        check(L.uvit_op_probe_ce_mix(ptr(self._logits), ptr(labels), ptr(partner), ptr(lam), f32(self.smoothing), ptr(self._dlogits),
+                                     ptr(self._row_loss), ptr(self._stats), B, K, s), "uvit_op_probe_ce_mix")
+
     def train_step(self, images, labels, lr, weight_decay, max_norm=None):
         """One step on the head: forward, smoothed cross-entropy, head gradients, global-norm clip (max_norm) + AdamW.  Returns
         (loss, grad_norm) as device scalars, valid until the next step; nothing synchronises with the host.  A non-finite loss
         (an out-of-range label) makes the gradients non-finite and uvit_op_adamw then leaves the head untouched.  `step_count`
         (Adam's bias correction) counts calls: the host cannot know of a skipped update without reading the loss, so a caller that
-        sees a non-finite loss stops, as the reference and run_linear_probe.py do, or takes the call back with `step_count -= 1`."""
-        B = self._features(images)
+        sees a non-finite loss stops, as the reference and run_linear_probe.py do, or takes the call back with `step_count -= 1`.
+        With a mixer (enable_mix) the batch is erased and mixed first and the loss is the soft-target one."""
+        B = self._features(self._train_images(images))
         labels = self._labels(labels, B)
         K, Cd, L, s = self.num_classes, self.embed_dim, lib(), cur_stream()
         self._logits_into(B)
-        check(L.uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(self.smoothing), ptr(self._dlogits), ptr(self._row_loss),
-                                 ptr(self._stats), None, B, K, s), "uvit_op_probe_ce")
+        self._criterion(labels, B)
         check(L.uvit_op_probe_head_grad(ptr(self._dlogits), ptr(self._feat), ptr(self._grad_arena), self._bias_ptr(self._grad_arena), B, K, Cd,
                                         s), "uvit_op_probe_head_grad")
         return self._clip_and_update(lr, weight_decay, max_norm)

@@ -126,12 +126,11 @@ class LayerWeightedProbe(LinearProbe):
     def train_step(self, images, labels, lr, weight_decay, max_norm=None):
         """LinearProbe.train_step plus the gradient of `layer_log_weights`: dfeat = dlogits . W, g_l = <dfeat, p_l>,
         dlog_w_l = w_l (g_l - sum_j w_j g_j), written into the gradient arena before the one clip + AdamW over the whole arena."""
-        B = self._features(images)
+        B = self._features(self._train_images(images))
         labels = self._labels(labels, B)
         K, Cd, L, dl, s = self.num_classes, self.embed_dim, self.depth, lib(), cur_stream()
         self._logits_into(B)
-        check(dl.uvit_op_probe_ce(ptr(self._logits), ptr(labels), f32(self.smoothing), ptr(self._dlogits), ptr(self._row_loss),
-                                  ptr(self._stats), None, B, K, s), "uvit_op_probe_ce")
+        self._criterion(labels, B)
         check(dl.uvit_op_probe_head_grad(ptr(self._dlogits), ptr(self._feat), ptr(self._grad_arena), self._bias_ptr(self._grad_arena), B, K,
                                          Cd, s), "uvit_op_probe_head_grad")
         check(dl.uvit_op_probe_input_grad(ptr(self._dlogits), ptr(self._arena), ptr(self._dfeat), B, K, Cd, s), "uvit_op_probe_input_grad")

@@ -272,6 +272,9 @@ _PROTOTYPES = {
     "uvit_op_corrupt_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _u32, _i64, _vp, _vp, _vp, _i64, _vp]),
     "uvit_op_corrupt_ext_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "uvit_op_corrupt_ext_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _u32, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "uvit_op_mix_ws_bytes": (_i64, [_i, _i]),
+    "uvit_op_mix_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _u32, _u32, _vp, _i64, _vp]),
+    "uvit_op_probe_ce_mix": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
