@@ -1160,6 +1160,83 @@ int uvit_op_mix_batch(const float* x, float* out, const uvit_mix_desc* desc, con
 int uvit_op_probe_ce_mix(const float* logits, const int64_t* labels, const int32_t* partner, const float* lam, float smoothing,
                          float* dlogits, float* row_loss, float* loss_out, int B, int K, uvit_stream stream);
 
+/* ---- probe training: RandAugment of a batch, Pillow's arithmetic bit for bit (csrc/randaug.hip) ----
+ * timm's rand_augment_transform (`--aa rand-m9-mstd0.5-inc1`, run_class_finetuning.py:117) on the normalised fp32 images x (B, 3, S, S)
+ * that uvit_op_augment_batch wrote, into out (B, 3, S, S); out may be x.  1 <= B <= 65535, 1 <= S <= 1024.  mean, std: HOST, 3 floats.
+ * The first stage quantises as uvit_op_corrupt_pack does, q = floor(clip(x * std[c] + mean[c], 0, 1) * 255 + 0.5); the layers of image
+ * b then run in order on the uint8 image the previous layer left; the last stage writes ((u8 / 255) - mean[c]) / std[c], the
+ * augmentation's step 4.  An image whose layers are all NONE comes out with the bits it went in with (for values that came from uint8).
+ * desc (HOST, B entries, validated here and copied into the workspace by an asynchronous copy on `stream`: keep it unchanged until the
+ * stream has passed this call): n_layers in [0, UVIT_RANDAUG_MAX_LAYERS] layers {op, filter, arg0, arg1, factor, fill, matrix[6]}:
+ *   INVERT                    255 - v
+ *   POSTERIZE    arg0 = bits in [0, 8]: v & ~(2^(8 - bits) - 1); 8: the identity, 0: black
+ *   SOLARIZE     arg0 = thresh in [0, 256]: v < thresh ? v : 255 - v
+ *   SOLARIZE_ADD arg0 = add in [0, 255], arg1 = thresh in [0, 256]: v < thresh ? min(255, v + add) : v
+ *   AUTOCONTRAST ImageOps.autocontrast(cutoff 0), per channel from its histogram: lo, hi = the lowest and highest level present;
+ *                hi <= lo: identity; else scale = 255.0 / (hi - lo), offset = -lo * scale, clamp((int)(v * scale + offset)) in double
+ *   EQUALIZE     ImageOps.equalize, per channel, integers: fewer than two levels present: identity; step = (S S - h[last level present])
+ *                / 255; step == 0: identity; else min(255, (step / 2 + sum_{j < v} h[j]) / step)
+ *   COLOR, CONTRAST, BRIGHTNESS, SHARPNESS   ImageEnhance.*.enhance(factor) = Blend.c's float32 d + factor * (v - d), clipped and
+ *                truncated, with d = L (Convert.c's rgb2l of the pixel), (int)(mean of L over the image + 0.5), 0, and ImageFilter.SMOOTH:
+ *                a float32 accumulator that starts at 0.5f and takes the nine products v * (k / 13.0f), k = 1 1 1 1 5 1 1 1 1, in
+ *                row-major order, <= 0: 0, >= 255: 255, else truncated; the one-pixel border is the image's own
+ *   ROTATE, SHEAR_X, SHEAR_Y, TRANSLATE_X_REL, TRANSLATE_Y_REL   Image.transform(AFFINE, matrix, filter, fillcolor = fill): the host
+ *                forms the matrix (probe_randaug.py), the five ops are one mechanism here.  BILINEAR and BICUBIC are Geometry.c's
+ *                ImagingGenericTransform in double: xin = (m0 (x + .5) + m1 (y + .5)) + m2, yin likewise; fill where xin < 0, xin >= S,
+ *                yin < 0 or yin >= S; else subtract 0.5, take floor and the fraction; columns clamped to [0, S); the first row clamped, a
+ *                later row outside the image repeats the previous row's value; bilinear a + (b - a) d truncated; bicubic p1 = v2,
+ *                p2 = -v1 + v3, p3 = 2 (v1 - v2) + v3 - v4, p4 = -v1 + v2 - v3 + v4, v = p1 + d (p2 + d (p3 + d p4)), clamped to
+ *                [0, 255], truncated.  NEAREST is not the generic transform in Pillow and is not here: with m1 == m3 == 0
+ *                (ImagingScaleAffine) the source column is trunc((m2 + m0 0.5) + m0 x), -1 below 0, rows likewise; otherwise
+ *                (affine_fixed) 16.16 fixed point, FIX(v) = floor(v 65536 + 0.5): xin = (FIX(m2 + m0 0.5 + m1 0.5) + x FIX(m0) + y FIX(m1))
+ *                >> 16, yin likewise; fill where the source lies outside the image.  |m0|, |m1|, |m3|, |m4| <= 4 and |m2|, |m5| <= 8192
+ *                keep the fixed-point walk inside 32 bits.
+ *   fill = r | g << 8 | b << 16.  filter: a PIL.Image.Resampling value, read by the affine ops.
+ * workspace: uvit_op_randaug_ws_bytes(B, S) bytes (< 0: UVIT_ERR_SHAPE): the descriptors, a 1 KiB table block per image and two planar
+ * uint8 copies of the batch that the layers write in turn.  Launches: the pack, per layer a statistics pass when an image's op needs a
+ * histogram or the mean of L and an apply pass when an image has an op, then the inverse.  No float atomics: the histograms and the
+ * sum of L are integer LDS atomics; the same input gives the same bits on every run and for every B.
+ * Errors (nothing launched): UVIT_ERR_SHAPE for B, S or an n_layers outside their limits; UVIT_ERR_ARG for a NULL pointer, a mean or
+ * std that is not finite, a std of 0, an unknown op or filter, a factor or a matrix entry that is not finite or a matrix outside the
+ * bounds above, or bits, thresh or add outside their ranges; UVIT_ERR_WORKSPACE. */
+#define UVIT_RANDAUG_MAX_LAYERS 4
+#define UVIT_RA_NONE 0                         /* the layer was not applied; 1 .. 15: timm's _RAND_TRANSFORMS in its order */
+#define UVIT_RA_AUTOCONTRAST 1
+#define UVIT_RA_EQUALIZE 2
+#define UVIT_RA_INVERT 3
+#define UVIT_RA_ROTATE 4
+#define UVIT_RA_POSTERIZE 5
+#define UVIT_RA_SOLARIZE 6
+#define UVIT_RA_SOLARIZE_ADD 7
+#define UVIT_RA_COLOR 8
+#define UVIT_RA_CONTRAST 9
+#define UVIT_RA_BRIGHTNESS 10
+#define UVIT_RA_SHARPNESS 11
+#define UVIT_RA_SHEAR_X 12
+#define UVIT_RA_SHEAR_Y 13
+#define UVIT_RA_TRANSLATE_X_REL 14
+#define UVIT_RA_TRANSLATE_Y_REL 15
+#define UVIT_RA_OPS 16
+#define UVIT_RA_NEAREST 0
+#define UVIT_RA_BILINEAR 2
+#define UVIT_RA_BICUBIC 3
+typedef struct uvit_randaug_layer {
+    int32_t op;                                /* UVIT_RA_* */
+    int32_t filter;                            /* UVIT_RA_{NEAREST, BILINEAR, BICUBIC} */
+    int32_t arg0, arg1;
+    float factor;
+    uint32_t fill;
+    double matrix[6];
+} uvit_randaug_layer;
+typedef struct uvit_randaug_desc {
+    int32_t n_layers;
+    int32_t reserved;                          /* 0 */
+    uvit_randaug_layer layers[UVIT_RANDAUG_MAX_LAYERS];
+} uvit_randaug_desc;
+int64_t uvit_op_randaug_ws_bytes(int B, int S);
+int uvit_op_randaug_batch(const float* x, float* out, const uvit_randaug_desc* desc, int B, int S, const float* mean, const float* std,
+                          void* workspace, int64_t ws_bytes, uvit_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

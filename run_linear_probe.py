@@ -187,6 +187,15 @@ erase and mix every training batch on the device in front of the encoder (uncert
 section 9.20) and train on the soft-target cross-entropy of the two labels of every row; the run prints `Mixup is activated!` and
 log.txt's `train_loss` is that loss.  `--mix_seed` (default: --seed) seeds the draws, which depend on (seed, step) alone.  Every head
 but --ensembles takes them; --eval refuses them.  Evaluation is untouched.
+
+`--aa CONFIG` (the reference's flag, timm's string: `rand-m9-mstd0.5-inc1` is the reference's default; absent = off, that default is
+not adopted) runs RandAugment on every training batch on the device, in front of the erasing and mixing and of the encoder
+(uncertainty-vit_amd/probe_randaug.py, csrc/randaug.hip): per image `n` of timm's fifteen ops, each applied
+with probability 0.5 at a magnitude drawn around `m`, computed as Pillow computes them, bit for bit.  `--aa_interpolation
+bicubic|bilinear|nearest|random` (default bicubic, what the reference's --train_interpolation hands timm) is the filter of the affine
+ops.  The draws take --mix_seed (default: --seed) and depend on (seed, step) alone.  The run prints `RandAugment is activated: ...`
+with the parsed config; log.txt's `train_loss` keeps its meaning.  Every head takes it, --ensembles too; --eval refuses it.  Only
+`rand` configs are built: `original`, `v0`, `augmix` and the weighted choice `w` are refused.
 """
 import argparse
 import json
@@ -205,7 +214,7 @@ from uncertainty_vit_amd.corruptions import CORRUPTIONS, DEFAULT_CACHE_IMAGES, C
 from uncertainty_vit_amd.corruptions_ext import CORRUPTIONS_EXT
 from uncertainty_vit_amd.datasets import FOLDER_DATA_SETS, BEiTAugment, ImageFolderPretrain, PerturbationSequences, collate_packed, collate_sequences
 from uncertainty_vit_amd.engine_for_cyclical import DevicePrefetcher
-from uncertainty_vit_amd import dist_probe, ens_probe, gp_probe, het_probe, lap_probe, linear_probe, lw_probe, mcd_probe, probe_mix, utils
+from uncertainty_vit_amd import dist_probe, ens_probe, gp_probe, het_probe, lap_probe, linear_probe, lw_probe, mcd_probe, probe_mix, probe_randaug, utils
 
 
 def get_args(argv=None):
@@ -369,7 +378,11 @@ def get_args(argv=None):
     a("--mixup_prob", type=float, default=argparse.SUPPRESS, help="probability of mixing a batch (or a row) when either is enabled (default 1.0)")
     a("--mixup_switch_prob", type=float, default=argparse.SUPPRESS, help="probability of cutmix when both are enabled (default 0.5)")
     a("--mixup_mode", type=str, default=argparse.SUPPRESS, help="how the parameters are drawn: batch, pair or elem (default batch)")
-    a("--mix_seed", type=int, default=argparse.SUPPRESS, help="seed of the mixing and erasing draws (default: --seed)")
+    a("--mix_seed", type=int, default=argparse.SUPPRESS, help="seed of the mixing, erasing and RandAugment draws (default: --seed)")
+    # the reference's --aa (run_class_finetuning.py:117); absent = off: its default rand-m9-mstd0.5-inc1 is NOT adopted
+    a("--aa", type=str, default=argparse.SUPPRESS, metavar="CONFIG",
+      help="RandAugment of the training batches on the device, timm's config string, e.g. rand-m9-mstd0.5-inc1 (default: off)")
+    a("--aa_interpolation", type=str, default=argparse.SUPPRESS, help="filter of RandAugment's affine ops: bicubic, bilinear, nearest or random (default bicubic)")
     return p.parse_args(argv)
 
 
@@ -418,6 +431,21 @@ def build_mixer(args):
         raise ValueError("--mixup / --cutmix / --cutmix_minmax / --reprob are not built under --ensembles: its loss is the members' "
                          "bagged cross-entropy (uvit_op_ens_ce)")
     return mixer
+
+
+def build_augmenter(args):
+    """The probe_randaug.RandAugmenter of --aa / --aa_interpolation, or None without --aa.  Refused (ValueError, NotImplementedError): a
+    config that is not a `rand` one or cannot be read, an unknown interpolation, --aa_interpolation without --aa, and --aa beside --eval."""
+    if not hasattr(args, "aa"):
+        if hasattr(args, "aa_interpolation"):
+            raise ValueError("--aa_interpolation steers --aa: give --aa CONFIG")
+        return None
+    norm = BEiTAugment(args.input_size, 1, "bicubic", args.imagenet_default_mean_and_std)       # the normalisation of build_loader's batches
+    aug = probe_randaug.RandAugmenter(args.aa, norm.mean, getattr(args, "aa_interpolation", "bicubic"), getattr(args, "mix_seed", args.seed),
+                                      std=norm.std)
+    if args.eval:
+        raise ValueError("--aa changes the training batches: give it without --eval")
+    return aug
 
 
 def check_scal_flags(args):
@@ -1293,6 +1321,7 @@ def validate(args):
     for head in (h for h in HEADS if h.switch):
         head.check(args) if head.check else check_head(head, args)
     build_mixer(args)
+    build_augmenter(args)
     return modes
 
 
@@ -1343,6 +1372,10 @@ def main(args):
     if mixer is not None:
         print("Mixup is activated!")                  # run_class_finetuning.py:567; train_loss is the soft-target loss from here on
         probe.enable_mix(mixer)
+    augmenter = build_augmenter(args)
+    if augmenter is not None:
+        print("RandAugment is activated: %s" % augmenter)
+        probe.enable_randaug(augmenter)
     start_epoch = 0
     if args.resume:
         st = torch.load(args.resume, map_location="cpu", weights_only=False)

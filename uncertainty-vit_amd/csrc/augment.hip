@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "pil_pixel.h"
 #include "../../include/uvit.h"
 
 #if defined(__FAST_MATH__) || __FINITE_MATH_ONLY__
@@ -121,17 +122,7 @@ __host__ __device__ inline void row_range(const uvit_augment_desc& d, int S, int
     *r1 = lo + n;
 }
 
-// ---- Pillow's pixel arithmetic ----
-__device__ inline int luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }  // Convert.c rgb2l
-
-// Blend.c: float temp = in1 + alpha * (in2 - in1); clipped to [0, 255], truncated
-__device__ inline int blend(int d, int x, float f) {
-    const float t = (float)d + f * (float)(x - d);
-    if (t <= 0.0f) return 0;
-    if (t >= 255.0f) return 255;
-    return (int)t;
-}
-
+// ---- Pillow's pixel arithmetic: luma() and blend() of pil_pixel.h ----
 // jitter steps [0, n) of the sample's order; contrast blends towards `cmean`
 __device__ inline void jitter(const uvit_augment_desc& d, int n, int cmean, int& r, int& g, int& b) {
     for (int i = 0; i < n; ++i) {

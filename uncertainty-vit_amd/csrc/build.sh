@@ -19,8 +19,8 @@ done
     -c augment.hip -o obj/augment.o ) &
 pids+=($!)
 # The strict files: IEEE float semantics, no fast-math.  Each one's header says which property it relies on and refuses __FAST_MATH__.
-STRICT_FILES="probe calib setcalib stability gp het ens detect tscale conformal laplace maha knn vim mcd layerweights corrupt corrupt_ext dprobe mixup"
-declare -A STRICT_EXTRA=([conformal]="-ffp-contract=off" [corrupt]="-ffp-contract=off" [corrupt_ext]="-ffp-contract=off" [mixup]="-ffp-contract=off")    # per-file additions to the strict flag set
+STRICT_FILES="probe calib setcalib stability gp het ens detect tscale conformal laplace maha knn vim mcd layerweights corrupt corrupt_ext dprobe mixup randaug"
+declare -A STRICT_EXTRA=([conformal]="-ffp-contract=off" [corrupt]="-ffp-contract=off" [corrupt_ext]="-ffp-contract=off" [mixup]="-ffp-contract=off" [randaug]="-ffp-contract=off")    # per-file additions to the strict flag set
 for f in $STRICT_FILES; do
   ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC ${STRICT_EXTRA[$f]} -Wall -Wno-unused-function $UVIT_EXTRA_FLAGS -c $f.hip -o obj/$f.o ) &
   pids+=($!)

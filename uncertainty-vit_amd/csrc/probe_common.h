@@ -1,4 +1,4 @@
-// Shared helpers of the probe translation units (probe, calib, setcalib, stability, gp, het, ens, detect, tscale, conformal, laplace, maha, knn, vim, mcd, layerweights, corrupt, corrupt_ext, dprobe, mixup),
+// Shared helpers of the probe translation units (probe, calib, setcalib, stability, gp, het, ens, detect, tscale, conformal, laplace, maha, knn, vim, mcd, layerweights, corrupt, corrupt_ext, dprobe, mixup, randaug),
 // on top of common.h.  These files are built WITHOUT -ffast-math: each states in its own header which IEEE property it relies on and
 // refuses to compile under __FAST_MATH__.  Nothing here reorders a sum: a wave sum is the xor tree from distance 32 down to 1.
 #pragma once

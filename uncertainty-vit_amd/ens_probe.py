@@ -168,8 +168,9 @@ class EnsembleProbe(LinearProbe):
         """One step on the M heads, as LinearProbe.train_step: one logits call, the members' cross-entropies (weighted by the bagging
         weights of step_seed(step_count) when bagging), one head-gradient call, the per-member clip (max_norm) and one AdamW over
         the arena.  Returns (mean of the members' losses, norm of the whole gradient arena after the clip) as device scalars; the
-        members' losses stay in self._member_loss[:M], their gradient norms before the clip in self.member_norms."""
-        B = self._features(images)
+        members' losses stay in self._member_loss[:M], their gradient norms before the clip in self.member_norms.  With an augmenter
+        (enable_randaug) the batch goes through RandAugment first; a mixer is refused (enable_mix)."""
+        B = self._features(self._train_images(images))
         labels = self._labels(labels, B)
         M, K, Cd, L, s = self.members, self.num_classes, self.embed_dim, lib(), cur_stream()
         self._lin_into(B)

@@ -57,6 +57,8 @@ class LinearProbe(DetectionMixin, SetCalibrationMixin, DensityMethods, Neighbour
     TWO_STREAM = False                       # the encoder family the class reads: True in DistProbe (dist_probe.py) alone
     # training-time mixing (enable_mix): the mixer, and (partner, lam) on the device while the running train_step's batch is mixed
     _mixer, _mix, _mix_bufs = None, None, None
+    # training-time RandAugment (enable_randaug): the augmenter and the buffers of uvit_op_randaug_batch
+    _augmenter, _ra_bufs = None, None
 
     def __init__(self, encoder, num_classes, smoothing=0.1, init_scale=0.001):
         super().__init__()
@@ -282,9 +284,57 @@ class LinearProbe(DetectionMixin, SetCalibrationMixin, DensityMethods, Neighbour
         self._mix = (bufs["labels"][:4 * B].view(torch.int32), bufs["labels"][4 * B:].view(torch.float32))
         return bufs["out"]
 
+    def enable_randaug(self, aug):
+        """RandAugment of every training batch (probe_randaug.RandAugmenter; None switches it off): train_step draws with iteration =
+        step_count and runs uvit_op_randaug_batch into a buffer of the probe's in front of the mixer and the encoder -- timm's order,
+        auto-augment in front of RandomErasing and Mixup.  It changes no label, so every head takes it.  A step whose draw is not
+        active makes the calls of a probe without an augmenter and gives its bits.  Evaluation is untouched."""
+        if aug is not None and not (callable(getattr(aug, "draw", None)) and hasattr(aug, "mean") and hasattr(aug, "std")):
+            raise TypeError("enable_randaug takes a probe_randaug.RandAugmenter or None")
+        self._augmenter = aug
+
+    def randaug_images(self, images, draw):
+        """uvit_op_randaug_batch on `images` (B, 3, S, S) fp32 on the GPU under a probe_randaug.RandAugDraw, with the augmenter's mean
+        and std: the augmented batch, a buffer of the probe's that the next call overwrites."""
+        self._check_images(images)
+        if images.dtype != torch.float32 or images.ndim != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3] or \
+                not images.is_contiguous():
+            raise native.UvitError("RandAugment needs contiguous float32 images of shape (B, 3, S, S)")
+        if self._augmenter is None:
+            raise native.UvitError("randaug_images needs an augmenter for its mean and std: call enable_randaug first")
+        B, S = images.shape[0], images.shape[2]
+        L, dev = lib(), images.device
+        need = L.uvit_op_randaug_ws_bytes(B, S)
+        if need < 0:
+            check(need, "uvit_op_randaug_ws_bytes")
+        bufs = self._ra_bufs
+        if bufs is None or bufs["out"].shape != images.shape or bufs["out"].device != dev or bufs["ws"].numel() < need:
+            # the descriptors are read by an asynchronous copy: four pinned slots, each guarded by the event of the step that used it
+            bufs = self._ra_bufs = {"out": torch.empty_like(images), "ws": torch.empty(need, dtype=torch.uint8, device=dev), "slots": [], "at": 0}
+        if len(bufs["slots"]) < 4:
+            bufs["slots"].append({"event": torch.cuda.Event(), "host": None})
+        slot = bufs["slots"][bufs["at"] % len(bufs["slots"])]
+        bufs["at"] += 1
+        slot["event"].synchronize()                  # returns at once unless the stream is four steps behind
+        pack = np.ascontiguousarray(draw.desc).view(np.uint8).reshape(-1)
+        if slot["host"] is None or slot["host"].numel() < pack.size:
+            slot["host"] = torch.empty(pack.size, dtype=torch.uint8).pin_memory()
+        slot["host"].numpy()[:pack.size] = pack
+        mean, std = (C.c_float * 3)(*self._augmenter.mean), (C.c_float * 3)(*self._augmenter.std)
+        check(L.uvit_op_randaug_batch(ptr(images), ptr(bufs["out"]), C.c_void_p(slot["host"].data_ptr()), B, S, mean, std, ptr(bufs["ws"]),
+                                      bufs["ws"].numel(), cur_stream()), "uvit_op_randaug_batch")
+        slot["event"].record()
+        return bufs["out"]
+
     def _train_images(self, images):
-        """The batch a train_step feeds the encoder: `images`, or, with a mixer whose draw of this step is active, their mix."""
+        """The batch a train_step feeds the encoder: `images`, behind RandAugment where an augmenter's draw of this step is active,
+        then, with a mixer whose draw of this step is active, their mix."""
         self._mix = None
+        if self._augmenter is not None:
+            self._check_images(images)
+            draw = self._augmenter.draw(images.shape[0], images.shape[-1], self.step_count)
+            if draw.active:
+                images = self.randaug_images(images, draw)
         if self._mixer is None:
             return images
         self._check_images(images)

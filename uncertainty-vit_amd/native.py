@@ -275,6 +275,8 @@ _PROTOTYPES = {
     "uvit_op_mix_ws_bytes": (_i64, [_i, _i]),
     "uvit_op_mix_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _u32, _u32, _vp, _i64, _vp]),
     "uvit_op_probe_ce_mix": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp]),
+    "uvit_op_randaug_ws_bytes": (_i64, [_i, _i]),
+    "uvit_op_randaug_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
 }
 SYMBOLS = list(_PROTOTYPES)
 
