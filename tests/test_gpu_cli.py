@@ -37,6 +37,34 @@ def test_cli_trains_checkpoints_and_resumes(tmp_path, stochastic):
     assert args.start_epoch == 2
     log = [json.loads(l) for l in open(tmp_path / "log.txt")]
     assert [l["epoch"] for l in log] == [0, 1, 2] and 0 < log[2]["train_loss"] < 10
+    # the resumed epoch continued the run: Adam step count, weights that moved, and the schedules of global iterations 8..11
+    per_epoch = 32 // 8
+    ck2 = torch.load(tmp_path / "checkpoint-2.pth", map_location="cpu", weights_only=False)
+    assert ck2["epoch"] == 2 and {int(float(s["step"])) for s in ck2["optimizer"]["state"].values()} == {3 * per_epoch}
+    assert {int(float(s["step"])) for s in ck["optimizer"]["state"].values()} == {2 * per_epoch}
+    moved = [k for k, v in ck2["model"].items() if v.dtype.is_floating_point and not torch.equal(v, ck["model"][k])]
+    assert len(moved) > 0.8 * len(ck["model"]), moved          # all but the index buffer and the two-stream model's dead cov_qkv weights
+    assert any(not torch.equal(v, ck["model_ema"][k]) for k, v in ck2["model_ema"].items())
+    lr, wd, decay = resumed_epoch_scalars(args, 3, per_epoch)
+    # the log holds means of the host's float64 values, epoch_scalars the float32 values the device reads: 2^-23 apart at most
+    assert log[2]["train_lr"] == pytest.approx(lr, rel=2 ** -23) and log[2]["train_lr"] != pytest.approx(log[1]["train_lr"], rel=1e-2)
+    assert log[2]["train_weight_decay"] == pytest.approx(wd, rel=2 ** -23)
+    assert log[2]["train_cur_decay"] == pytest.approx(decay, rel=2 ** -23)
+
+
+def resumed_epoch_scalars(args, epochs, per_epoch):
+    """Means over the last epoch's iterations of (lr, weight decay, EMA decay), from the schedules run_cyclical.main builds for `epochs`
+    epochs and engine_for_cyclical.epoch_scalars at the global iterations (epochs - 1) * per_epoch ...; computed on the host."""
+    from types import SimpleNamespace
+    from uncertainty_vit_amd import utils
+    from uncertainty_vit_amd.engine_for_cyclical import epoch_scalars
+    assert args.tri_phase_schedule is None and args.epochs == epochs
+    lrs = utils.cosine_scheduler(args.lr, args.min_lr, epochs, per_epoch, warmup_epochs=args.warmup_epochs, warmup_steps=args.warmup_steps)
+    wds = utils.cosine_scheduler(args.weight_decay, args.weight_decay_end, epochs, per_epoch)
+    opt = SimpleNamespace(param_groups=[dict(lr=args.lr, weight_decay=args.weight_decay, lr_scale=1.0)])
+    rows = epoch_scalars(opt, (epochs - 1) * per_epoch, per_epoch, lrs, wds, args.ema_start_at, args.ema_decay_init, args.ema_decay, -1)
+    assert all(d > 0 for _, _, d in rows) and len({r[0] for r in rows}) == per_epoch
+    return tuple(sum(r[k] for r in rows) / per_epoch for k in range(3))
 
 
 def test_cli_config1_plumbing_size(tmp_path):

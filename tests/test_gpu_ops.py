@@ -578,6 +578,52 @@ def test_adamw_skips_a_non_finite_norm(L):
     assert not any(torch.equal(a, b) for a, b in zip((p, m, v, pb), before))
 
 
+# float32 bit patterns whose bf16 image a cast gets wrong first (round to nearest, ties to even, on bit 16)
+CAST_EDGES = [
+    0x00000000, 0x80000000,                             # +-0
+    0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF,     # smallest and largest denormals (the largest rounds up to the smallest normal)
+    0x00400000, 0x00008000, 0x00018000,                 # a denormal that is a bf16 number; denormal ties (to 0, to 0x0002)
+    0x7F800000, 0xFF800000,                             # +-inf
+    0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000,     # ties: down to the even 0x3F80, up to the even 0x3F82
+    0x3F807FFF, 0x3F808001, 0x3F817FFF, 0x3F818001,     # just below and above each tie
+    0x7F7F7FFF, 0xFF7F7FFF,                             # the largest finite floats that round to the bf16 maximum 0x7F7F
+    0x7F7F8000, 0xFF7F8000, 0x7F7FFFFF, 0xFF7FFFFF,     # finite floats that round to +-inf (the first is a tie on an odd mantissa)
+    0x7FC00000, 0xFFC00000,                             # quiet NaNs
+    0x7F800001, 0xFF800001, 0x7FBFFFFF, 0x7FFFFFFF,     # signalling NaNs whose payload sits below bit 16; all mantissa bits (carries into the sign)
+]
+
+
+@pytest.mark.parametrize("n", [4, 4 * 257, 4 * (2048 * 256 + 3)])
+def test_cast_bf16_against_torch(L, n):
+    """uvit_op_cast_bf16 (the cast behind both bf16 shadows) against the host's tensor.to(torch.bfloat16), bit for bit, NaN as NaN: the
+    edge patterns above in front (n = 4: the first four), then random bit patterns (every exponent, denormals, NaNs) and normal draws.
+    n = 4: one float4; 4 x 257: a second workgroup with one live lane; 4 x (2048 x 256 + 3): three float4 past the full 2048-workgroup
+    grid, so the grid-stride loop takes a second pass.  n % 4 != 0 is refused with UVIT_ERR_SHAPE and writes nothing."""
+    g = torch.Generator().manual_seed(90 + n % 89)
+    bits = torch.randint(-2 ** 31, 2 ** 31, (n,), generator=g, dtype=torch.int64).to(torch.int32)
+    src = bits.view(torch.float32).clone()
+    src[n // 2:] = torch.randn(n - n // 2, generator=g) * 3
+    k = min(n, len(CAST_EDGES))
+    src[:k] = torch.from_numpy(np.array(CAST_EDGES[:k], dtype=np.uint32).view(np.float32))
+    assert torch.equal(src[:k].view(torch.int32), torch.from_numpy(np.array(CAST_EDGES[:k], dtype=np.uint32).view(np.int32)))
+    ref = src.to(torch.bfloat16)
+    dst = torch.full((n + 8,), -1.0, dtype=torch.bfloat16, device="cuda")          # 0xBF80 behind the end: must stay
+    ok(L.uvit_op_cast_bf16(P(src.cuda()), P(dst), n, S()))
+    got = dst[:n].cpu()
+    assert torch.equal(dst[n:].cpu(), torch.full((8,), -1.0, dtype=torch.bfloat16)), "the cast wrote behind n"
+    nan = ref.isnan()
+    assert torch.equal(got.isnan(), nan), "NaN in, NaN out (and nothing else)"
+    bad = (got.view(torch.int16) != ref.view(torch.int16)) & ~nan
+    assert not bad.any(), [(hex(int(src[i].view(torch.int32)) & 0xFFFFFFFF), hex(int(got[i].view(torch.int16)) & 0xFFFF),
+                            hex(int(ref[i].view(torch.int16)) & 0xFFFF)) for i in bad.nonzero().flatten()[:8].tolist()]
+    if n == 4:
+        before = dst.clone()
+        for odd in (1, 2, 3, 7):
+            assert L.uvit_op_cast_bf16(P(src.cuda()), P(dst), odd, S()) == -2       # UVIT_ERR_SHAPE
+        torch.cuda.synchronize()
+        assert torch.equal(dst.view(torch.int16), before.view(torch.int16))
+
+
 @pytest.mark.parametrize("beta,l2", [(2.0, 0), (0.12, 0), (1.0, 1)])
 def test_smooth_l1_fwd_bwd(L, beta, l2):
     Mmax, Cd, cnt = 64, 128, 50

@@ -128,6 +128,8 @@ class NativeEngine:
         if getattr(model, "ls_saved_y", None) is not None:
             self.set_ls_saved_y(model.ls_saved_y)
         self.sync_shadows(3)
+        # the teacher's weights version ema_bf16 was cast from (the student's own is model._synced_version): engine() compares
+        self.synced_teacher = getattr(teacher, "_weights_version", None)
 
     @property
     def model(self):
@@ -204,6 +206,9 @@ class VisionTransformerForCyclicalTraining(nn.Module):
         self.init_std = init_std
         self.patch_embed = _PatchEmbedInfo(img_size, patch_size)
         self.stosa = False
+        # bumped by every edit of the arena from outside the native step (mark_weights_changed); _synced_version is the version the
+        # shadows of this model's own engine were cast from, and an engine that reads this model as its teacher keeps its own copy
+        self._weights_version, self._synced_version = 0, -1
         self.use_abs_pos_emb = bool(use_abs_pos_emb)
         if not self.use_abs_pos_emb:
             self.pos_embed = None            # otherwise an arena view registered below (modeling_cyclical.py:80-84)
@@ -300,6 +305,7 @@ class VisionTransformerForCyclicalTraining(nn.Module):
             raise NotImplementedError("master weights stay fp32; bf16 shadows are managed natively")
         moved = new.device != self._arena.device
         self._arena = new.contiguous()
+        self.mark_weights_changed()
         if moved:
             self._grad_arena = None
             self._engine = None
@@ -320,13 +326,13 @@ class VisionTransformerForCyclicalTraining(nn.Module):
         new.train(self.training)
         for p, q in zip(new.parameters(), self.parameters()):
             p.requires_grad_(q.requires_grad)
-        new._shadows_stale = True
+        new.mark_weights_changed()
         memo[id(self)] = new
         return new
 
     def _load_from_state_dict(self, *a, **k):
         super()._load_from_state_dict(*a, **k)
-        self._shadows_stale = True
+        self.mark_weights_changed()
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         out = super().load_state_dict(state_dict, strict=strict, **kw)
@@ -334,8 +340,21 @@ class VisionTransformerForCyclicalTraining(nn.Module):
         return out
 
     def mark_weights_changed(self):
-        """Call after editing parameters outside the native optimizer (bf16 shadows are refreshed lazily)."""
-        self._shadows_stale = True
+        """Call after editing parameters outside the native optimizer.  The bf16 shadows are refreshed lazily, by the next engine() call
+        of every engine that reads this arena: this model's own, and the student's whose teacher this model is."""
+        self._weights_version += 1
+
+    @property
+    def _shadows_stale(self):
+        """True when this model's own engine holds shadows of an older version of the weights."""
+        return self._synced_version != self._weights_version
+
+    @_shadows_stale.setter
+    def _shadows_stale(self, stale):
+        if stale:
+            self.mark_weights_changed()
+        else:
+            self._synced_version = self._weights_version
 
     # ---- init: modeling_cyclical.py:135-161 ----
     def _init_weights(self):
@@ -353,7 +372,7 @@ class VisionTransformerForCyclicalTraining(nn.Module):
             for i in range(self.depth):
                 sd[f"blocks.{i}.attn.proj.weight"].div_(math.sqrt(2.0 * (i + 1)))
                 sd[f"blocks.{i}.mlp.fc2.weight"].div_(math.sqrt(2.0 * (i + 1)))
-        self._shadows_stale = True
+        self.mark_weights_changed()
 
     def _init_weights_dist(self):
         """modeling_cyclical_dist.py:62-90: cls tokens trunc-normal (timm default bounds +-2), Linear weights
@@ -377,7 +396,7 @@ class VisionTransformerForCyclicalTraining(nn.Module):
             for i in range(self.depth):
                 for n in ("attn.proj.weight", "attn.cov_proj.weight", "mlp.fc2.weight"):
                     sd[f"blocks.{i}.{n}"].div_(math.sqrt(2.0 * (i + 1)))
-        self._shadows_stale = True
+        self.mark_weights_changed()
 
     @torch.jit.ignore
     def no_weight_decay(self):
@@ -395,10 +414,19 @@ class VisionTransformerForCyclicalTraining(nn.Module):
             self._engine = e = NativeEngine(self, keep_t, batch, adam_m if adam_m is not None else (e.adam_m if e else None),
                                             adam_v if adam_v is not None else (e.adam_v if e else None))
             self._rebind()
-            self._shadows_stale = False
-        if getattr(self, "_shadows_stale", False):
-            e.sync_shadows(3)
-            self._shadows_stale = False
+            self._synced_version = self._weights_version
+        # Edits from outside the step: the student's shadows (bit 1) follow this model's version, the teacher's bf16 copy (bit 2) follows
+        # the teacher module's -- a flag on the teacher would be cleared by the teacher's own engine.  Without a teacher ema_bf16 is a
+        # cast of this model's arena.
+        t_version = getattr(e.teacher, "_weights_version", None)
+        which = 0
+        if self._synced_version != self._weights_version:
+            which |= 1 if e.teacher is not None else 3
+        if e.teacher is not None and getattr(e, "synced_teacher", None) != t_version:
+            which |= 2
+        if which:
+            e.sync_shadows(which)
+            self._synced_version, e.synced_teacher = self._weights_version, t_version
         return e
 
     def forward_features(self, x, bool_masked_pos, layer_results):
